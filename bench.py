@@ -4,14 +4,19 @@
 One "step" = one complete 360-degree panorama: the 8 fixed 45-degree sectors (each a full reference frame:
 clear, cull, raster, resolve + contour post) rendered from the resident DEM mosaic, plus -- for N > 1 -- the
 RCCL all-gather of the per-rank strips.  Tiles and their normal textures are resident in HBM before the timed
-region (the reference computes normals once per tile load, terrain_renderer.rs:192-202); the load phase is
-timed separately and reported as `load_ms`.
+region (the reference computes normals once per tile load, terrain_renderer.rs:192-202); with --full the load phase
+is timed separately and reported as `load_ms`.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 N GPUs shard the panorama by azimuth sector (rank g renders sectors [8g/N, 8(g+1)/N)), DEM replicated, so
 the total work is fixed: scaling = "strong".
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps (no timing event in them) and
+the result line.  --full adds everything else the benchmark measures: the load phase, the per-kernel breakdown and the
+roofline (with HIP events in the timed region and rocprofv3 --pmc child passes), the two-frames-in-flight figure, the
+host-output path and the CPU baseline.
 """
 import argparse
 import json
@@ -38,6 +43,8 @@ LAT0, LON0 = 40, 10            # mosaic SW corner
 TILE = 1200
 N_SECTORS = 8
 HBM_PEAK_GBPS = 8000.0         # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
+DUMP_PIXELS = 1 << 21          # --dump-outputs: pixels written at most (RGBA 16 B + depth 4 B each as f32: 40 MiB)
+DUMP_SEED = 0x5EED0D0
 
 
 def main():
@@ -49,7 +56,7 @@ def main():
     ap.add_argument("--view-mode", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--check", action="store_true", help="verify sector 0 against the oracle (slow)")
+    ap.add_argument("--check", action="store_true", help="with --full: verify this rank's sectors against the oracle (slow)")
     ap.add_argument("--occlusion-split", type=float, default=None, help="metres; 0 disables the two-phase occlusion filter")
     ap.add_argument("--pipeline", type=int, default=None,
                     help="frames in flight (topo_set_pipeline_depth) in the timed region; default 1 = strictly one panorama "
@@ -63,8 +70,20 @@ def main():
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE, SQ counters) behind roofline.traffic / roofline_valu")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)      # this process IS such a pass: a few frames, no JSON
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: load phase, per-kernel breakdown, roofline (HIP events in the "
+                         "timed region, rocprofv3 --pmc child passes), two frames in flight, host-output path, CPU baseline; the "
+                         "--no-* options above skip parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as float32 DIR/rgba.npy (n, 4) and DIR/depth.npy (n,): "
+                         f"every pixel, or a fixed seeded sample of {DUMP_PIXELS} pixels of a larger output (rank 0; depth at N = 1 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.check and not args.full:
+        ap.error("--check is part of --full")
     if args.pmc_child:
+        args.full = True
         args.no_cpu_baseline = args.no_pmc = args.no_host_path = args.no_pipelined_extra = True
 
     import numpy as np
@@ -124,13 +143,14 @@ def main():
     # ---- load phase (normals K1-K3 over resident heights), timed on its own
     # (every load-time kernel of the resident tiles is inside the bracket: the per-tile tables of the frame phase -- block
     # min/max, cull bounds, sin/cos tables: k_block_tables -- and the normals K1-K3)
-    loads = []
-    for _ in range(3):
-        r.recompute_normals()
-        tm = r.timings()
-        loads.append((tm["load"], tm["load_tables"]))
-    load_ms, load_tables_ms = min(loads)
-    load_normals_ms = load_ms - load_tables_ms
+    if args.full:
+        loads = []
+        for _ in range(3):
+            r.recompute_normals()
+            tm = r.timings()
+            loads.append((tm["load"], tm["load_tables"]))
+        load_ms, load_tables_ms = min(loads)
+        load_normals_ms = load_ms - load_tables_ms
 
     # ---- outputs: the sector-major strip of the C ABI (topo_render_panorama): strip[8][PH][SW][4], rank g's sectors
     # [8g/N, 8(g+1)/N) one contiguous block.  A rank renders ALL its sectors in one submission (one set of kernel launches:
@@ -229,44 +249,51 @@ def main():
     # the roofline uses.  (The frame's GPU span -- an event in front of its first kernel, one behind its last -- comes from a
     # pass of its own: the event in front costs the frame ~7 us.)
     KERNELS = ("clear", "cull", "raster", "occlusion", "raster_big", "resolve")
-    r.set_timing_slots(None)
-    for _ in range(max(1, args.warmup)):       # first launches, buffer growth
-        step()
-    fence()
-    samples = []
-    for _ in range(7 + depth_frames):
-        step()
-        tm = r.timings()
-        if tm["total"] > 0.0:
-            samples.append({k: tm[k] for k in KERNELS + ("total",)})
-    fence()
-    n_detail = len(samples)
-    detail = {k: (sorted(smp[k] for smp in samples)[n_detail // 2] if n_detail else 0.0) for k in KERNELS + ("total",)}   # medians
-    dom = max(("resolve", "raster", "raster_big"), key=lambda k: detail[k])
-    r.set_timing_slots(())
-    n_span = 8 * depth_frames
-    for _ in range(n_span):
-        step()
-    fence()
-    span = sorted(h["total"] for h in r.timing_history(n_span) if h["total"] > 0.0)
-    r.set_timing_slots((dom,), total=False)
-    for _ in range(args.warmup):
-        step()
-    fence()
-    if args.pmc_child:              # a rocprofv3 --pmc pass of this command: the frames above and a few more are all it needs
-        for _ in range(3):
+    if not args.full:
+        # a plain run: no timing event anywhere (each one costs a frame GPU time), only the warm-up in front of the timed region
+        r.set_timing_slots((), total=False)
+        for _ in range(max(1, args.warmup)):       # first launches, buffer growth
             step()
         fence()
-        return
-    # The timed region: exactly `steps` submissions between two fences, nothing in it waits for a frame.  The HIP-event
-    # durations of its frames' kernels (the events sit on the stream the kernels are launched on) are read AFTER the region
-    # from the renderer's event ring (topo_get_timing_history: the last 32 frames per frame in flight).
+    else:
+        r.set_timing_slots(None)
+        for _ in range(max(1, args.warmup)):       # first launches, buffer growth
+            step()
+        fence()
+        samples = []
+        for _ in range(7 + depth_frames):
+            step()
+            tm = r.timings()
+            if tm["total"] > 0.0:
+                samples.append({k: tm[k] for k in KERNELS + ("total",)})
+        fence()
+        n_detail = len(samples)
+        detail = {k: (sorted(smp[k] for smp in samples)[n_detail // 2] if n_detail else 0.0) for k in KERNELS + ("total",)}   # medians
+        dom = max(("resolve", "raster", "raster_big"), key=lambda k: detail[k])
+        r.set_timing_slots(())
+        n_span = 8 * depth_frames
+        for _ in range(n_span):
+            step()
+        fence()
+        span = sorted(h["total"] for h in r.timing_history(n_span) if h["total"] > 0.0)
+        r.set_timing_slots((dom,), total=False)
+        for _ in range(args.warmup):
+            step()
+        fence()
+        if args.pmc_child:              # a rocprofv3 --pmc pass of this command: the frames above and a few more are all it needs
+            for _ in range(3):
+                step()
+            fence()
+            return
+    # The timed region: exactly `steps` submissions between two fences, nothing in it waits for a frame.  With --full the
+    # HIP-event durations of its frames' kernels (the events sit on the stream the kernels are launched on) are read AFTER the
+    # region from the renderer's event ring (topo_get_timing_history: the last 32 frames per frame in flight).
     # Even two events cost a frame 8-10 us of GPU time (markers or the kernel's own start / end times alike), so only every
     # EV_STRIDE-th frame of the region carries them: the dominant kernel's duration is the mean over those frames.
     EV_STRIDE = 4
     t_start = time.perf_counter()
     for i in range(args.steps):
-        if i % EV_STRIDE < 2:
+        if args.full and i % EV_STRIDE < 2:
             r.set_timing_slots((dom,) if i % EV_STRIDE == 0 else (), total=False)
         step()
     fence()
@@ -276,6 +303,47 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     ms_per_step = 1e3 * elapsed / args.steps
+    mpix = PW * PH / 1e6
+    value = mpix / (ms_per_step / 1e3)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # the last step's outputs (`strip` / `depth_all` are those step() used last); at N > 1 every rank holds the whole
+        # RGBA strip but only its own sectors' depth (none through the C-ABI exchange), so the depth is written at N = 1 only
+        outputs = dump_outputs(args.dump_outputs, np, torch, strip, depth_all if world == 1 else None)
+    out = {
+        "metric": "panorama Mpix/s",
+        "value": round(value, 2),
+        "unit": "Mpix/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {deg}x{deg} deg COP90-shaped mosaic ({n_tiles} tiles of 1200x1200 f32), "
+                               f"{PW}x{PH} panorama = 8 sectors of {SW}x{PH}, view_mode {args.view_mode}",
+                   "frames_in_flight": depth_frames,
+                   "sharding": f"azimuth sectors, {per} per GPU in one submission, DEM replicated" +
+                               (", one in-place RCCL all-gather of the sector-major RGBA strip per panorama" +
+                                (" through the C ABI (topo_render_panorama)" if use_capi_comm else " (torch.distributed)") if world > 1 else "")
+                               if not use_capi_comm or world == 1 else
+                               f"azimuth sectors, {per} per GPU in one cull/raster submission, DEM replicated; resolved and exchanged in "
+                               f"{len(T.panorama_slots(world, SW, PH))} slots through the C ABI (topo_render_panorama: grouped ncclSend/ncclRecv of each "
+                               f"slot on a second stream under the next slot's resolve)",
+                   **({"comm_note": comm_note} if comm_note else {})},
+        **({"outputs": outputs} if outputs else {}),
+    }
+    if not args.full:
+        out["setup_s"] = round(setup_s, 1)
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     hist = [h for h in r.timing_history(min(args.steps, 32 * depth_frames)) if h[dom] > 0.0]
     timed_frames = len(hist)
     timed_ms = {dom: (sum(h[dom] for h in hist) / timed_frames if timed_frames else 0.0)}       # mean: what the roofline uses
@@ -284,9 +352,6 @@ def main():
     kernel_ms[dom] = timed_ms[dom]           # ... except the dominant kernel (the timed region's) and the total (the span pass's)
     kernel_ms["total"] = span[len(span) // 2] if span else 0.0
     counters = r.counters()
-
-    mpix = PW * PH / 1e6
-    value = mpix / (ms_per_step / 1e3)
 
     # ---- roofline of the dominant kernel = the frame kernel with the largest mean duration (HIP events on the launch
     # stream).  Algorithmic bytes per launch:
@@ -339,30 +404,7 @@ def main():
     per_kernel["dem_to_visibility_stage"] = {"ms": round(stage_ms, 4), "what": "cull + raster + occlusion + rare + big against the DEM read (4*T*W*H/N)",
                                              "algorithmic_GBps": round(dem_bytes / (stage_ms / 1e3) / 1e9, 1) if stage_ms > 0 else None}
 
-    out = {
-        "metric": "panorama Mpix/s",
-        "value": round(value, 2),
-        "unit": "Mpix/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {deg}x{deg} deg COP90-shaped mosaic ({n_tiles} tiles of 1200x1200 f32), "
-                               f"{PW}x{PH} panorama = 8 sectors of {SW}x{PH}, view_mode {args.view_mode}",
-                   "frames_in_flight": depth_frames,
-                   "sharding": f"azimuth sectors, {per} per GPU in one submission, DEM replicated" +
-                               (", one in-place RCCL all-gather of the sector-major RGBA strip per panorama" +
-                                (" through the C ABI (topo_render_panorama)" if use_capi_comm else " (torch.distributed)") if world > 1 else "")
-                               if not use_capi_comm or world == 1 else
-                               f"azimuth sectors, {per} per GPU in one cull/raster submission, DEM replicated; resolved and exchanged in "
-                               f"{len(T.panorama_slots(world, SW, PH))} slots through the C ABI (topo_render_panorama: grouped ncclSend/ncclRecv of each "
-                               f"slot on a second stream under the next slot's resolve)",
-                   **({"comm_note": comm_note} if comm_note else {})},
+    out.update({
         "roofline": roofline,
         "roofline_valu": roofline_valu,
         "per_kernel": per_kernel,
@@ -398,7 +440,7 @@ def main():
         "host_cores": os.cpu_count(), "usable_cores": usable_cores(),
         "setup_s": round(setup_s, 1),
         "upload_s": round(upload_s, 2),
-    }
+    })
 
     # ---- throughput mode (additive, never `value`): consecutive panoramas with two frames in flight, so that the
     # latency-bound cull/raster phases of one run under the ALU-bound resolve of the previous one
@@ -553,6 +595,30 @@ def collect_pmc(args, kernel):
     return out
 
 
+def dump_outputs(out_dir, np, torch, rgba, depth):
+    """--dump-outputs: the outputs of the last timed step as float32 arrays, rgba.npy (n, 4) and depth.npy (n,), the same pixels
+    in both, in the order of the flattened output.  Up to DUMP_PIXELS pixels that is every pixel; above, a fixed sample: the
+    flattened output cut into DUMP_PIXELS equal runs and one pixel drawn from each (seed DUMP_SEED), so runs with the same
+    arguments write the same pixels.  depth None: rgba.npy only."""
+    n = rgba.numel() // 4
+    flat = rgba.reshape(n, 4)
+    if n > DUMP_PIXELS:
+        edges = np.arange(DUMP_PIXELS + 1, dtype=np.int64) * n // DUMP_PIXELS
+        pick = edges[:-1] + (np.random.default_rng(DUMP_SEED).random(DUMP_PIXELS) * np.diff(edges)).astype(np.int64)
+        idx = torch.from_numpy(pick).to(rgba.device)
+        rgba_s, depth_s = flat[idx], (depth.reshape(n)[idx] if depth is not None else None)
+    else:
+        rgba_s, depth_s = flat, (depth.reshape(n) if depth is not None else None)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rgba.npy"), rgba_s.to(torch.float32).cpu().numpy())
+    files = ["rgba.npy"]
+    if depth_s is not None:
+        np.save(os.path.join(out_dir, "depth.npy"), depth_s.to(torch.float32).cpu().numpy())
+        files.append("depth.npy")
+    return {"dir": out_dir, "files": files, "pixels": min(n, DUMP_PIXELS), "of": n,
+            "what": "the last timed step's outputs as float32" + (f", one seeded pixel from each of {DUMP_PIXELS} equal runs" if n > DUMP_PIXELS else "")}
+
+
 def _splitmix64(x):
     x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
     z = x
@@ -605,10 +671,10 @@ def bench_batch(args, T, np, torch, dist, r, locs, deg, SW, PH, rank, world, set
             dist.barrier()
         torch.cuda.synchronize()
 
-    for _ in range(min(args.warmup, 1)):
+    for _ in range(max(1, args.warmup)):
         step()
     fence()
-    steps = max(1, min(args.steps, 3))
+    steps = args.steps
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
@@ -619,12 +685,16 @@ def bench_batch(args, T, np, torch, dist, r, locs, deg, SW, PH, rank, world, set
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     ms = 1e3 * elapsed / steps
+    outputs = None
+    if args.dump_outputs and rank == 0:      # the last chunk of the last step (this rank's last CHUNK viewpoints)
+        outputs = dump_outputs(args.dump_outputs, np, torch, rgba, depth)
     out = {"metric": "panorama Mpix/s", "value": round(C5_VIEWPOINTS * N_SECTORS * SW * PH / 1e6 / (ms / 1e3), 2), "unit": "Mpix/s",
-           "n_gpus": world, "steps": steps, "warmup": min(args.warmup, 1), "ms_per_step": round(ms, 3), "higher_is_better": True,
+           "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": f"c5: batch of {C5_VIEWPOINTS} viewpoints over the {deg}x{deg} deg mosaic, {N_SECTORS * SW}x{PH} panorama each",
                       "frames_in_flight": in_flight, "viewpoints_per_submission": C5_GROUP, "entry_point": "topo_render_batch",
                       "sharding": f"viewpoints, {per} per GPU, DEM replicated, no collective"},
+           **({"outputs": outputs} if outputs else {}),
            "ms_per_viewpoint": round(ms / per, 4), "setup_s": round(setup_s, 1)}
     if rank == 0:
         print(json.dumps(out))
