@@ -89,7 +89,10 @@ int topo_update(topo_ctx* ctx, uint32_t width, uint32_t height, const topo_unifo
  *                                               terrain_renderer.rs:365-452, render_engine.rs:219-249
  * rgba_out: height rows of width RGBA8 (sRGB-encoded) texels, rgba_pitch bytes apart.  depth_out (nullable):
  * Depth32Float rows depth_pitch bytes apart; the reference uses pad_256(4*width) (data/mod.rs:9-11).
- * Host pointers; synchronous. */
+ * Host pointers; synchronous.  A frame whose rare-triangle queue overflowed is rendered again with a grown queue (with an
+ * explicit topo_debug_set_queue_caps capacity: TOPO_ERR_CAPACITY instead); only the frame handed out counts for
+ * topo_frame_status.  An overflow of a frame queued earlier through the asynchronous entry points is not this call's error:
+ * it stays for the next topo_join / topo_synchronize. */
 int topo_render(topo_ctx* ctx, uint8_t* rgba_out, size_t rgba_pitch, float* depth_out, size_t depth_pitch);
 /* The way out to host memory.  The reference presents its frame without a read-back and maps the depth buffer only when the
  * camera moved (render_engine.rs:219-252); a host that asks topo_render for host images gets them at the link's rate if it
@@ -241,14 +244,16 @@ int topo_synchronize(topo_ctx* ctx);
  * complete after topo_join (waits for the frames in flight) or topo_synchronize.  Depth 1 (default): everything runs
  * in order on the context's stream.  topo_render (host outputs) always waits for its frame. */
 int topo_set_pipeline_depth(topo_ctx* ctx, int32_t depth);
-/* Waits for every frame in flight.  A frame's status word is per frame; if one of the frames waited for overflowed its
- * rare-triangle queue (triangles were dropped: its outputs are incomplete) topo_join -- and likewise topo_synchronize --
- * returns TOPO_ERR_CAPACITY, once per such frame; the frames after it are unaffected.  (topo_render, the synchronous
- * entry point, never hands out such a frame: it grows the queue and renders the frame again.) */
+/* Waits for every frame in flight, on whichever stream it was queued (a slot-by-slot topo_render_panorama runs on the
+ * context's stream at any depth).  A frame's status word is per frame; if one or more of the frames waited for overflowed
+ * its rare-triangle queue (triangles were dropped: its outputs are incomplete) topo_join -- and likewise topo_synchronize --
+ * returns TOPO_ERR_CAPACITY once: the next call reports only frames that finish after this one.  The frames after an
+ * overflowed one are unaffected.  (topo_render, the synchronous entry point, never hands out such a frame: it grows the
+ * queue and renders the frame again.) */
 int topo_join(topo_ctx* ctx);
 /* Status bits of the frames that have completed since the previous call (waits for the frames in flight first; the bits
- * of all of them OR-ed together, so a burst of frames cannot hide an earlier frame's overflow behind a clean last frame; the
- * call clears them): out[0] = status bits (bit 0 big-triangle queue overflowed: handled exactly, slower; bit 1 rare-triangle queue overflowed:
+ * of all of them OR-ed together, so a burst of frames cannot hide an earlier frame's overflow behind a clean last frame; an
+ * attempt topo_render threw away and rendered again is not one of them; the call clears them): out[0] = status bits (bit 0 big-triangle queue overflowed: handled exactly, slower; bit 1 rare-triangle queue overflowed:
  * frame incomplete; bit 2 bounds violation, only ever set by the TOPO_BOUNDS_CHECK build libtopo_hip_check.so),
  * out[1] = site tag and out[2], out[3] = low/high word of the offending value of the first bounds violation. */
 int topo_frame_status(topo_ctx* ctx, uint32_t out[4]);
@@ -283,7 +288,7 @@ int topo_get_timing_history(topo_ctx* ctx, uint32_t n_frames, float* out_ms, uin
 #define TOPO_TIMING_NO_TOTAL 0x80u
 int topo_set_timing_slots(topo_ctx* ctx, uint32_t slot_mask);
 
-/* Counters of the last topo_render* call: [0] near blocks rastered, [1] big-triangle items, [2] that frame's status bits
+/* Counters of the last topo_render* call, its own (waits for that frame on the stream it was queued on): [0] near blocks rastered, [1] big-triangle items, [2] that frame's status bits
  * (bit 0: big-triangle queue overflowed -- handled in-lane, slower, still exact; bit 1: rare-triangle queue
  * overflowed -- triangles dropped, frame incomplete: see topo_join), [3] rare triangles
  * (>= 64 px across or near-clipped), [4] far blocks occlusion-tested, [5] far blocks that survived the test. */

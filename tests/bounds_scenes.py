@@ -85,6 +85,26 @@ def run(T):
     record("in_flight", r, *[t.cpu().numpy() for t in outs])
     r.set_pipeline_depth(1)
 
+    # frames in flight through the pixelise branch (k_post_pixelize over each context's own staging images), with and without
+    # a depth output; one serial submission first, so that no staging image is allocated while frames are in flight
+    def pixelise(k, with_depth):
+        r.update(96, 64, views[8 * k], T.post_uniforms(96, 64, pixelize_n=(50.0, 7.5)[k % 2]))
+        rgba = torch.zeros((8, 64, 96, 4), dtype=torch.uint8, device="cuda")
+        depth = torch.zeros((8, 64, 96), dtype=torch.float32, device="cuda") if with_depth else None
+        r.render_views_device(views[8 * k:8 * k + 8], 96, 64, rgba.data_ptr(), 64 * 96 * 4, 96 * 4,
+                              depth.data_ptr() if with_depth else 0, 64 * 96 * 4, 96 * 4)
+        return [rgba] + ([depth] if with_depth else [])
+
+    pixelise(1, False)
+    r.synchronize()
+    r.set_pipeline_depth(2)
+    outs = []
+    for k in range(4):
+        outs += pixelise(k, k in (0, 3))
+    r.join()
+    record("in_flight_pixelise", r, *[t.cpu().numpy() for t in outs])
+    r.set_pipeline_depth(1)
+
     c2 = Scene(1200, 1, 1, lat0=40, lon0=10, vfrac=(0.623, 0.717))
     r = T.TerrainRenderer(512, 1024)
     c2.load(r)

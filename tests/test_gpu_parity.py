@@ -389,9 +389,12 @@ def test_queue_overflow_paths(topo, orc):
     with pytest.raises(topo.TopoError) as e:
         g.render()
     assert e.value.code == topo.TOPO_ERR_CAPACITY
+    assert g.frame_status()["rare_overflow"]          # the frame the call failed on is reported as incomplete
     g.debug_set_queue_caps(0, 2 | 0x80000000)         # a growable queue (the default, from a tiny start): re-rendered, exact
     assert_same_frame(g.render(), ref, "rare queue grown on demand")
     assert g.counters()["status"] == 0 and g.counters()["rare_items"] > 2
+    st = g.frame_status()                             # the attempts thrown away before the queue grew are no frame of anyone's
+    assert not st["rare_overflow"] and st["status"] == 0
     g.debug_set_queue_caps(0, 0)
     assert_same_frame(g.render(), ref, "defaults restored")
     assert g.counters()["status"] == 0
@@ -463,6 +466,167 @@ def test_overflow_status_is_per_frame_on_the_async_paths(topo, orc):
     o.update(W, H, down, pu)
     ro, do = o.render()
     assert np.array_equal(rgba.cpu().numpy(), ro) and np.array_equal(depth.cpu().numpy().view(np.uint32), do.view(np.uint32))
+
+
+def _overflow_scene(topo, orc, W=320, H=240):
+    """The scene of test_overflow_status_is_per_frame_on_the_async_paths: `down` has hundreds of rare triangles (near-field
+    giants), `up` (from 250 km) none -- it is complete even with a rare-triangle queue of 2."""
+    sc = Scene(12, 2, 2, eye_dh=60.0)
+    g, o = both(topo, orc, W, H)
+    sc.load(g)
+    sc.load(o)
+    down = sc.uniforms(W, H, 10, 35, 110, 0)
+    high = topo.geometry_transform(sc.ground + 250000.0, sc.vlon, sc.vlat)
+    up = topo.camera_uniforms(high, 0.3, np.radians(80.0), np.radians(60.0), W, H, sc.vlon, sc.vlat, 0)
+    return sc, g, o, down, up
+
+
+@pytest.mark.parametrize("depth_frames", [1, 2, 3])
+def test_render_after_an_overflowed_async_frame(topo, orc, depth_frames):
+    """An incomplete frame queued through the asynchronous entry points is the error of the call that waits for it: a
+    topo_render in between -- one that grows its own queue, one that fails on an explicit capacity -- waits for that frame
+    but neither reports its overflow nor swallows it.  The next topo_join reports it, once."""
+    import torch
+    sc, g, o, down, _ = _overflow_scene(topo, orc)
+    W, H = 320, 240
+    pu = topo.post_uniforms(W, H)
+    other = sc.uniforms(W, H, 190, 35, 110, 0)
+    o.update(W, H, other, pu)
+    want = o.render()
+    rgba = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda")
+    depth = torch.empty((H, W), dtype=torch.float32, device="cuda")
+    g.set_pipeline_depth(depth_frames)
+
+    def queue_down():
+        if depth_frames == 1:
+            g.update(W, H, down, pu)
+            g.render_device(rgba.data_ptr(), W * 4, depth.data_ptr(), W * 4)
+        else:
+            g.render_views_device([down], W, H, rgba.data_ptr(), H * W * 4, W * 4, depth.data_ptr(), H * W * 4, W * 4)
+
+    g.debug_set_queue_caps(0, 2 | 0x80000000)         # growable: topo_render may grow it
+    queue_down()
+    g.update(W, H, other, pu)
+    assert_same_frame(g.render(), want, f"topo_render behind an overflowed async frame, depth {depth_frames}")
+    with pytest.raises(topo.TopoError) as e:
+        g.join()
+    assert e.value.code == topo.TOPO_ERR_CAPACITY
+    g.join()                                           # reported once
+    g.debug_set_queue_caps(0, 2)                       # explicit: topo_render fails on its own overflow ...
+    queue_down()
+    g.update(W, H, down, pu)
+    with pytest.raises(topo.TopoError) as e:
+        g.render()
+    assert e.value.code == topo.TOPO_ERR_CAPACITY
+    with pytest.raises(topo.TopoError) as e:           # ... and the async frame's overflow is still the next join's
+        g.join()
+    assert e.value.code == topo.TOPO_ERR_CAPACITY
+    g.join()
+    g.set_pipeline_depth(1)
+
+
+@pytest.mark.parametrize("depth_frames", [1, 2])
+def test_status_ring_and_counters_of_a_burst(topo, orc, depth_frames):
+    """More frames than the status ring holds (64 per context) queued without a wait: the ring-wrap fold carries an early
+    frame's overflow to the join -- one error, then none; topo_frame_status shows it once.  In a burst of two frames the
+    counters are the last frame's own (the alternating counter sets) and the status bits are both frames' OR."""
+    import torch
+    sc, g, o, down, up = _overflow_scene(topo, orc)
+    W, H = 320, 240
+    pu = topo.post_uniforms(W, H)
+    bufs = [(torch.empty((H, W, 4), dtype=torch.uint8, device="cuda"), torch.empty((H, W), dtype=torch.float32, device="cuda"))
+            for _ in range(depth_frames)]                # a buffer per context: frames in flight never write the same one
+    n_frames = [0]
+
+    def frame(u):
+        g.update(W, H, u, pu)
+        s, d = bufs[n_frames[0] % depth_frames]
+        g.render_device(s.data_ptr(), W * 4, d.data_ptr(), W * 4)
+        n_frames[0] += 1
+
+    g.set_pipeline_depth(depth_frames)
+    g.debug_set_queue_caps(0, 2)
+    frame(up)
+    frame(up)
+    frame(down)
+    for _ in range(64 * depth_frames + 6):
+        frame(up)
+    with pytest.raises(topo.TopoError) as e:
+        g.join()
+    assert e.value.code == topo.TOPO_ERR_CAPACITY
+    g.join()
+    g.synchronize()
+    assert g.frame_status()["rare_overflow"]
+    assert g.frame_status()["status"] == 0
+    # `down` with a big-triangle queue of 16 sets bit 0 (exact, slower; which triangles find the queue full -- and go to the
+    # rare queue instead -- depends on the order of the atomics, so its counters are not reproducible); `up` with the default
+    # queues is clean, its counters reproducible
+    g.debug_set_queue_caps(0, 0)
+    frame(up)
+    g.synchronize()
+    c_up, s_up = g.counters(), g.frame_status()["status"]
+    assert s_up == 0 and c_up["status"] == 0 and c_up["blocks_rastered"] > 0
+    g.debug_set_queue_caps(16, 0)
+    frame(down)
+    g.synchronize()
+    c_down, s_down = g.counters(), g.frame_status()["status"]
+    assert s_down & 1 and c_down["status"] == s_down
+    frame(down)
+    g.debug_set_queue_caps(0, 0)                       # (taken at submission: the frame queued keeps its 16)
+    frame(up)
+    assert g.counters() == c_up                        # the last frame's own counters, not the sum and not the other set
+    assert g.frame_status()["status"] == s_down | s_up
+    g.set_pipeline_depth(1)
+
+
+def test_slot_panorama_status_at_pipeline_depth_two(topo):
+    """The slot-by-slot panorama (the N > 1 resolve; TOPO_PANORAMA_FORCE_SLOTS on one GPU) runs on the context's stream at
+    any pipeline depth: with depth 2, topo_join and topo_get_counters must wait for that stream.  The stream is kept busy
+    in front of the panorama, so a call that does not wait reads a status slot the frame has not written yet."""
+    import torch
+    sc = Scene(12, 2, 2, eye_dh=60.0)
+    sw, sh = 64, 128
+    g = topo.TerrainRenderer(sw, sh)
+    sc.load(g)
+    high = topo.geometry_transform(sc.ground + 250000.0, sc.vlon, sc.vlat)
+    strip = torch.zeros((8, sh, sw, 4), dtype=torch.uint8, device="cuda")
+    depth = torch.zeros((8, sh, sw), dtype=torch.float32, device="cuda")
+    g.set_stream(torch.cuda.current_stream().cuda_stream)
+
+    def panorama(eye, pitch_deg):
+        g.render_panorama(None, eye, math.radians(25.0), sw, sh, sc.vlon, sc.vlat, strip.data_ptr(), depth.data_ptr(),
+                          pitch=math.radians(pitch_deg))
+
+    os.environ["TOPO_PANORAMA_FORCE_SLOTS"] = "1"
+    try:
+        g.debug_set_queue_caps(0, 2)
+        panorama(high, 60.0)                             # depth 1: the reference (and ctx 0's buffers at their size)
+        g.synchronize()
+        ref_counters = g.counters()
+        ref_strip, ref_depth = strip.cpu().numpy(), depth.cpu().numpy()
+        assert ref_counters["status"] == 0 and ref_counters["blocks_rastered"] > 0
+        panorama(sc.eye, 35.0)                           # near-field giants: incomplete with a queue of 2
+        with pytest.raises(topo.TopoError) as e:
+            g.synchronize()
+        assert e.value.code == topo.TOPO_ERR_CAPACITY
+        g.set_pipeline_depth(2)
+        torch.cuda._sleep(200_000_000)                   # the stream busy for a while in front of the frame
+        panorama(sc.eye, 35.0)
+        with pytest.raises(topo.TopoError) as e:
+            g.join()
+        assert e.value.code == topo.TOPO_ERR_CAPACITY
+        g.join()
+        strip.zero_()
+        depth.zero_()
+        torch.cuda._sleep(200_000_000)
+        panorama(high, 60.0)
+        assert g.counters() == ref_counters              # no synchronize in between
+        g.join()
+        assert np.array_equal(strip.cpu().numpy(), ref_strip) and np.array_equal(depth.cpu().numpy().view(np.uint32), ref_depth.view(np.uint32))
+    finally:
+        del os.environ["TOPO_PANORAMA_FORCE_SLOTS"]
+        g.set_pipeline_depth(1)
+        g.set_stream(0)
 
 
 @pytest.mark.parametrize("tw,th", [(40, 30), (30, 40), (3, 3), (61, 16), (62, 17)])
@@ -729,6 +893,53 @@ def test_pipelined_frames_equal_serial_frames(topo, orc):
     assert_same_frame(g.render(), o.render(), "topo_render with a pipeline depth of 2")
     with pytest.raises(topo.TopoError):
         g.set_pipeline_depth(9)
+
+
+def test_pipelined_pixelise_frames_equal_serial_frames(topo, orc):
+    """The pixelise branch stages the render target in an image of the frame context's own: frames in flight on two or
+    three contexts give the bytes of the one-at-a-time path (and the oracle's), with and without a depth output (without
+    one, the depth is staged too).  The serial pass comes first, so no staging image is allocated while frames are in flight."""
+    import torch
+    sc = Scene(64, 2, 2, eye_dh=120.0)
+    W, H = 128, 96
+    g, o = both(topo, orc, W, H)
+    sc.load(g)
+    sc.load(o)
+    subs = [(pans, n, with_depth) for pans, (n, with_depth) in
+            zip([sc.panorama(W, H, yaw0_deg=y) for y in (0, 33, 170, 285, 90, 201, 47)],
+                [(7.5, True), (50.0, False), (7.5, False), (50.0, True), (50.0, True), (7.5, False), (50.0, False)])]
+    bufs = [(torch.empty((8, H, W, 4), dtype=torch.uint8, device="cuda"),
+             torch.empty((8, H, W), dtype=torch.float32, device="cuda") if with_depth else None) for _, _, with_depth in subs]
+
+    def run_all():
+        for s, d in bufs:
+            s.zero_()
+            if d is not None:
+                d.zero_()
+        torch.cuda.synchronize()
+        for (views, n, _), (s, d) in zip(subs, bufs):
+            g.update(W, H, views[0], topo.post_uniforms(W, H, pixelize_n=n))
+            g.render_views_device(views, W, H, s.data_ptr(), H * W * 4, W * 4, d.data_ptr() if d is not None else 0, H * W * 4, W * 4)
+        g.join()
+        torch.cuda.synchronize()
+        return [(s.cpu().numpy(), d.cpu().numpy() if d is not None else None) for s, d in bufs]
+
+    serial = run_all()
+    for i, ((views, n, with_depth), (s, d)) in enumerate(zip(subs, serial)):
+        for k in (i % 8, (i + 5) % 8):
+            o.update(W, H, views[k], topo.post_uniforms(W, H, pixelize_n=n))
+            ro, do = o.render()
+            assert np.array_equal(s[k], ro), f"submission {i} view {k}: colour differs from the oracle"
+            if with_depth:
+                assert np.array_equal(d[k].view(np.uint32), do.view(np.uint32)), f"submission {i} view {k}: depth differs from the oracle"
+    for depth_frames in (2, 3):
+        g.set_pipeline_depth(depth_frames)
+        for i, ((s, d), (s1, d1)) in enumerate(zip(run_all(), serial)):
+            for k in range(8):
+                assert np.array_equal(s[k], s1[k]), f"depth {depth_frames} submission {i} view {k}: colour differs from the serial frame"
+                if d is not None:
+                    assert np.array_equal(d[k].view(np.uint32), d1[k].view(np.uint32)), f"depth {depth_frames} submission {i} view {k}"
+    g.set_pipeline_depth(1)
 
 
 GEOTIFF_CASES = [

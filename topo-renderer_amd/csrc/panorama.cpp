@@ -306,6 +306,8 @@ int TerrainRenderer::render_panorama(Comm* comm, const float eye[3], float yaw0,
         if (auto rc = a.GroupEnd()) return fail_nccl("ncclGroupEnd", rc);
         return TOPO_OK;
     };
+    // (on stream_ at any pipeline depth: render_frame records that as the stream of ctx_[0]'s latest frame, and at depth > 1
+    // marks the context pending, so topo_join, topo_get_counters and the status ring wait for stream_)
     last_ctx_ = 0;
     const int rc = render_frame(ctx_[0], stream_, count, views + first, sector_w, sector_h, o, slots.data(), n_slots, world > 1 ? &ship : nullptr);
     if (world == 1) return rc;

@@ -78,11 +78,11 @@ TerrainRenderer::~TerrainRenderer() {
     for (auto& kv : tiles_) {
         (void)hipFree(kv.second.d_pool);
     }
-    void* bufs[] = {d_tiles_, d_views_, d_out_rgba_, d_out_depth_, d_pre_rgba_, d_pre_depth_, d_edge_jobs_, d_corner_jobs_, d_peaks_, d_proj_, d_overlay_geo_, d_overlay_keys_};
+    void* bufs[] = {d_tiles_, d_views_, d_out_rgba_, d_out_depth_, d_edge_jobs_, d_corner_jobs_, d_peaks_, d_proj_, d_overlay_geo_, d_overlay_keys_};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (auto& c : ctx_) {
-        void* cb[] = {c.d_vis, c.d_dirty, c.d_work, c.d_work2, c.d_far, c.d_big, c.d_rare, c.d_counters};
+        void* cb[] = {c.d_vis, c.d_dirty, c.d_work, c.d_work2, c.d_far, c.d_big, c.d_rare, c.d_counters, c.d_pre_rgba, c.d_pre_depth};
         for (void* p : cb)
             if (p) (void)hipFree(p);
         for (auto& set : c.evr)
@@ -362,12 +362,13 @@ int TerrainRenderer::init_ctx(FrameCtx& c, bool own_stream) {
 }
 
 // Frames in flight on the contexts' own streams are not ordered with stream_: everything that frees or rewrites what a
-// frame reads (tiles, the tile table), and every consumer of a frame's outputs, joins them first.
+// frame reads (tiles, the tile table), and every consumer of a frame's outputs, joins them first.  A pending context's
+// latest frame may also sit on stream_ (the slot-by-slot panorama at depth > 1): join waits for the stream it was queued on.
 int TerrainRenderer::join() {
     if (int rc = bind_device()) return rc;
     for (auto& c : ctx_)
-        if (c.pending && c.stream) {
-            TOPO_HIP_TRY(hipStreamSynchronize(c.stream));
+        if (c.pending) {
+            if (c.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(c.last_stream));
             c.pending = false;
         }
     return TOPO_OK;
@@ -376,10 +377,11 @@ int TerrainRenderer::join() {
 // The status word of a frame is per frame (k_clear resets it, render_frame copies the counters to pinned memory behind
 // k_resolve).  Called once the frames' streams have been waited for: a frame whose rare-triangle queue overflowed has
 // dropped triangles -- its outputs are incomplete -- and that is an error of the call that waited for it
-// (topo_join / topo_synchronize / topo_render / topo_get_counters), reported once per frame.
-bool TerrainRenderer::fold_frames(FrameCtx& c) {
+// (topo_join / topo_synchronize; topo_render answers for its own frame), reported once: the first of those calls after the
+// frame finished returns one TOPO_ERR_CAPACITY for all the overflowed frames it waited for.
+bool TerrainRenderer::fold_frames(FrameCtx& c, uint64_t end) {
     bool overflow = false;
-    for (; c.checked < c.submitted; ++c.checked) {
+    for (; c.checked < end; ++c.checked) {
         const uint32_t* w = c.h_status + (c.checked % kStatusRing) * 16;
         // status bits accumulate over the frames folded since the last topo_frame_status (which clears them): a burst of frames
         // cannot hide an earlier frame's overflow or bounds violation behind a clean last frame
@@ -425,7 +427,6 @@ int TerrainRenderer::render_views_device(uint32_t n, const topo_uniforms* views,
     // the tile table (and whatever else the caller queued) was produced on stream_: order the frame after it
     TOPO_HIP_TRY(hipEventRecord(c.done, stream_));
     TOPO_HIP_TRY(hipStreamWaitEvent(c.stream, c.done, 0));
-    c.pending = true;
     return render_frame(c, c.stream, n, views, w, h, out);
 }
 
@@ -468,9 +469,11 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     }
     if (!c.h_status) TOPO_HIP_TRY(hipHostMalloc((void**)&c.h_status, kStatusRing * 16 * sizeof(uint32_t)));
     if (c.submitted - c.checked == kStatusRing) {      // nobody has waited for this context's frames for a whole ring: fold them now
-        TOPO_HIP_TRY(hipStreamSynchronize(stream));
+        if (c.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(c.last_stream));      // (where the latest of them was queued)
         overflow_pending_ |= fold_frames(c);
     }
+    c.last_stream = stream;
+    c.pending = pipeline_depth_ > 1;
     // View constants.  Up to kPackViews views (a panorama's eight sectors) travel as the argument of a one-workgroup kernel
     // (k_put_views: the launch copies them; a copy-engine operation and the event guarding its pinned source cost the GPU 13 us
     // per frame and the host two more calls).  Larger submissions go through a small ring of pinned staging slots, each guarded
@@ -649,19 +652,20 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     if ((ev_need & (1u << 7)) && !own_times) TOPO_HIP_TRY(hipEventRecord(ev[7], stream));
     const hipEvent_t ev_rstart = (ev_need & (1u << 7)) && own_times ? ev[7] : nullptr, ev_rstop = (ev_need & (1u << 8)) && own_times ? ev[8] : nullptr;
     // The pixelise branch of the post shader (pixelize_n < 99.99999; the reference never takes it) samples the render target
-    // away from the pixel's own texel: k_resolve then stores the render-target texels into an image of the context's
-    // (post_off) and k_post_pixelize makes the surface image from it and the depth image.
+    // away from the pixel's own texel: k_resolve then stores the render-target texels into an image of the frame context's
+    // (post_off) and k_post_pixelize makes the surface image from it and the depth image.  The images belong to the context,
+    // like d_vis: frames in flight on other contexts neither share nor reallocate them.
     OutputParams kout = out;
     if (pixelize) {
         if (n_slots) return fail(TOPO_ERR_UNSUPPORTED, "the pixelise branch is not available on the slot-by-slot (multi-GPU) path");
         const size_t img = (size_t)w * h * 4;
-        if (int rc = ensure_on(stream, &d_pre_rgba_, &cap_pre_rgba_, img * n)) return rc;
+        if (int rc = ensure_on(stream, &c.d_pre_rgba, &c.cap_pre_rgba, img * n)) return rc;
         if (!out.depth)
-            if (int rc = ensure_on(stream, &d_pre_depth_, &cap_pre_depth_, img * n)) return rc;
-        kout.rgba = (uint8_t*)d_pre_rgba_;
+            if (int rc = ensure_on(stream, &c.d_pre_depth, &c.cap_pre_depth, img * n)) return rc;
+        kout.rgba = (uint8_t*)c.d_pre_rgba;
         kout.rgba_view_stride = img;
         kout.rgba_pitch = (size_t)w * 4;
-        if (!out.depth) { kout.depth = (float*)d_pre_depth_; kout.depth_view_stride = img; kout.depth_pitch = (size_t)w * 4; }
+        if (!out.depth) { kout.depth = (float*)c.d_pre_depth; kout.depth_view_stride = img; kout.depth_pitch = (size_t)w * 4; }
         p.post_off = 1;
     }
     if (n_slots == 0) {
@@ -670,7 +674,7 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
         launch_resolve(p, kout, stream, ev_rstart, ev_rstop);
         if (pixelize)
             launch_post_pixelize(n, (int32_t)w, (int32_t)h, post_.viewport[0] >= 1.0f ? post_.viewport[0] : (float)w, post_.viewport[1] >= 1.0f ? post_.viewport[1] : (float)h,
-                                 post_.pixelize_n, (const uint8_t*)d_pre_rgba_, out, kout.depth, kout.depth_view_stride, kout.depth_pitch, p.linear_target, p.bgra, stream);
+                                 post_.pixelize_n, (const uint8_t*)c.d_pre_rgba, out, kout.depth, kout.depth_view_stride, kout.depth_pitch, p.linear_target, p.bgra, stream);
     } else {
         for (uint32_t i = 0; i < n_slots; ++i) {
             if ((uint64_t)slots[i].block_first + slots[i].block_count > (uint64_t)p.rblocks_view * n) return fail(TOPO_ERR_INVALID, "resolve slot outside the frame");
@@ -735,14 +739,16 @@ int TerrainRenderer::render(uint8_t* rgba, size_t rgba_pitch, float* depth, size
         if (int rc = join()) return rc;       // (pipelined contexts run on their own streams)
         TOPO_HIP_TRY(hipStreamSynchronize(stream_));
         FrameCtx& fc = ctx_[last_ctx_];
+        overflow_pending_ |= fold_frames(fc, fc.submitted - 1);      // (nothing: the frames in front of this one were folded above)
         const uint32_t* words = fc.h_status + ((fc.submitted - 1) % kStatusRing) * 16;
         const uint32_t status = words[2], wanted = words[3];
         if (!(status & kStatusRareOverflow) || rare_cap_cfg_ != 0 || attempt >= 3) {
-            (void)check_frames();          // (folds this frame's words; its status is answered for right here)
+            // the frame this call answers for: its bits reach topo_frame_status, its overflow is this call's error and not pending
+            (void)fold_frames(fc);
             if (status & kStatusRareOverflow) return fail(TOPO_ERR_CAPACITY, "rare-triangle queue overflowed: frame incomplete");
             break;
         }
-        (void)check_frames();
+        ++fc.checked;      // an attempt thrown away and rendered again: its status describes no frame anyone gets
         rare_cap_auto_ = (uint64_t)wanted + wanted / 4u + 1024u;      // the overflowed frame counted what it needs
         if (rare_cap_auto_ > (1ull << 28)) return fail(TOPO_ERR_CAPACITY, "rare-triangle queue would exceed 2^28 entries");
     }
@@ -949,6 +955,7 @@ int TerrainRenderer::visible_peaks(uint32_t n, const float* peaks, uint8_t* visi
 int TerrainRenderer::set_stream(hipStream_t s) {
     if (int rc = join()) return rc;
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    for (auto& c : ctx_) c.last_stream = nullptr;      // (every frame has finished; the old stream may go away)
     stream_ = s ? s : own_stream_;
     return TOPO_OK;
 }
@@ -960,7 +967,7 @@ int TerrainRenderer::synchronize() {
 }
 
 int TerrainRenderer::join_frames() {
-    if (int rc = join()) return rc;
+    if (int rc = join()) return rc;      // (depth > 1: also a slot-by-slot panorama's frame on stream_)
     if (pipeline_depth_ == 1) TOPO_HIP_TRY(hipStreamSynchronize(stream_));      // one frame in flight: it runs on stream_
     return check_frames();
 }
@@ -1033,7 +1040,7 @@ int TerrainRenderer::get_timings(float out[TOPO_TIMING_SLOTS]) {
     if (c.timed && c.frames) {
         const int ring = (int)((c.frames - 1) % kEvRing);
         if (c.evr_recorded[ring] & 0x100u) TOPO_HIP_TRY(hipEventSynchronize(c.evr[ring][8]));
-        else TOPO_HIP_TRY(hipStreamSynchronize(pipeline_depth_ > 1 ? c.stream : stream_));      // (TOPO_TIMING_NO_TOTAL: no event behind the frame)
+        else if (c.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(c.last_stream));      // (TOPO_TIMING_NO_TOTAL: no event behind the frame)
         if (int rc = frame_durations(c, ring, out)) return rc;
     }
     if (load_timed_) {
@@ -1076,7 +1083,7 @@ int TerrainRenderer::get_counters(uint32_t out[6]) {
     FrameCtx& fc = ctx_[last_ctx_];
     if (!fc.h_status) return TOPO_OK;
     if (int rc = bind_device()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(pipeline_depth_ > 1 ? fc.stream : stream_));
+    if (fc.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(fc.last_stream));      // the stream the frame was queued on
     uint32_t c[16] = {};
     if (fc.submitted) memcpy(c, fc.h_status + ((fc.submitted - 1) % kStatusRing) * 16, sizeof c);
     if (getenv("TOPO_DEBUG_COUNTERS")) {   // raw queue counters, for kernel experiments

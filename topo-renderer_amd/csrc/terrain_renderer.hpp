@@ -151,6 +151,11 @@ class TerrainRenderer {
         uint64_t evr_frame[kEvRing] = {};     // the renderer-wide number of the frame that used the set
         uint64_t frames = 0;                  // frames submitted on this context
         hipEvent_t done = nullptr;
+        // the stream the context's latest frame was queued on: its own stream (depth > 1), stream_ (depth 1, and the slot-by-slot
+        // panorama at any depth); null once a wait has covered it.  A context's frames are ordered (a frame on the own stream waits
+        // for stream_, the panorama joins the contexts first), so waiting for this stream waits for all of them.
+        hipStream_t last_stream = nullptr;
+        // a frame queued with pipeline depth > 1 that join() has not waited for yet (at depth 1 every wait synchronizes stream_)
         bool timed = false, pending = false;
         // pinned ring of the last kStatusRing frames' 16 counter words, each stored by its frame's k_resolve (the bounds-checking build: copied out behind it);
         // frames [checked, submitted) have not been looked at by check_frames yet
@@ -164,6 +169,8 @@ class TerrainRenderer {
         void* d_big = nullptr;      size_t cap_big = 0;
         void* d_rare = nullptr;     size_t cap_rare = 0;
         void* d_counters = nullptr; size_t cap_counters = 0;
+        void* d_pre_rgba = nullptr; size_t cap_pre_rgba = 0;      // the pixelise branch: the render-target image k_post_pixelize samples,
+        void* d_pre_depth = nullptr; size_t cap_pre_depth = 0;    // and a depth image when the caller wants none
     };
     static constexpr int kMaxPipeline = 4;
     static constexpr uint64_t kStatusRing = 64;
@@ -172,7 +179,8 @@ class TerrainRenderer {
     int init_ctx(FrameCtx& c, bool own_stream);
     int check_frames();                        // after a wait: turn a finished frame's overflow status into TOPO_ERR_CAPACITY
     uint32_t last_status_[4] = {};             // status word + bounds record of the last frame looked at
-    bool fold_frames(FrameCtx& c);             // folds the finished, unchecked frames of c into last_status_; true if one overflowed
+    bool fold_frames(FrameCtx& c, uint64_t end);   // folds the finished, unchecked frames [checked, end) of c into last_status_; true if one overflowed
+    bool fold_frames(FrameCtx& c) { return fold_frames(c, c.submitted); }
     bool overflow_pending_ = false;
     int ensure_on(hipStream_t s, void** p, size_t* cap, size_t need);
     // slots: the frame resolved in several launches (k_resolve over block ranges), after_slot(i, stream) called behind each --
@@ -189,8 +197,6 @@ class TerrainRenderer {
     void* d_corner_jobs_ = nullptr; size_t cap_corner_jobs_ = 0;
     void* d_out_rgba_ = nullptr; size_t cap_out_rgba_ = 0;
     void* d_out_depth_ = nullptr; size_t cap_out_depth_ = 0;
-    void* d_pre_rgba_ = nullptr; size_t cap_pre_rgba_ = 0;      // the pixelise branch: the render-target image k_post_pixelize samples,
-    void* d_pre_depth_ = nullptr; size_t cap_pre_depth_ = 0;    // and a depth image when the caller wants none
     // topo_render's way out to host memory: a pinned staging image and the events of its slices; the buffers the caller pinned
     uint8_t* h_stage_ = nullptr; size_t cap_stage_ = 0;
     hipEvent_t stage_ev_[8] = {};
