@@ -1416,10 +1416,12 @@ __device__ __forceinline__ bool resolve_strip_marked(const FrameParams& P, const
     int32_t y = B.by + kRPW * (int32_t)wave + row - 1;
     y = y < 0 ? 0 : (y > P.H - 1 ? P.H - 1 : y);
     const int32_t x0 = B.bx > 0 ? B.bx - 1 : 0, x1 = B.bx + 64 < P.W ? B.bx + 64 : P.W - 1;
-    const size_t first = (size_t)B.view * P.W * P.H + (size_t)y * P.W;
-    const size_t seg = ((first + x0) >> 6) + k;
-    const size_t last = (first + x1) >> 6;
-    const size_t at = seg <= last ? seg : last;      // (always a load, of a mark of this row: no branch around it)
+    // (32-bit key and mark numbers -- a submission has fewer than 2^32 pixels (the host refuses more) --: each of the strip's marks
+    // is loaded with one vector register of offset from the array's scalar address, all of them in flight at once)
+    const uint32_t first = B.view * (uint32_t)P.W * (uint32_t)P.H + (uint32_t)y * (uint32_t)P.W;
+    const uint32_t seg = ((first + (uint32_t)x0) >> 6) + (uint32_t)k;
+    const uint32_t last = (first + (uint32_t)x1) >> 6;
+    const uint32_t at = seg <= last ? seg : last;    // (always a load, of a mark of this row: no branch around it)
     const bool mark = TOPO_CHK(P.counters, at < (((size_t)P.n_views * P.W * P.H + 63) >> 6), 12u, at) ? P.dirty[at] != 0 : false;
     return seg <= last && mark;
 }
@@ -1502,6 +1504,22 @@ __device__ __forceinline__ void wave_lds_fence() {
 // the tables are in place.  (With one depth tile per block, two barriers per block made every wave wait for the block's
 // slowest: 29 % of all wave time.)
 // kSrgb: the targets are *Srgb formats (encode on store, decode on sample); otherwise plain unorm8.  kBgra: channel order.
+struct ResolveArgs {             // k_resolve's parameter list as the argument segment lays it out
+    FrameParams P;
+    OutputParams O;
+};
+// A wave-uniform constant-address-space object behind a pointer the compiler cannot prove to be the same from one call to the
+// next: fields read through it are loaded (s_load, scalar cache) where they are used, instead of being loaded once and held in
+// scalar registers (or their addresses precomputed) across every loop around the use.
+template <typename T>
+__device__ __forceinline__ const T& reload_ref(const __attribute__((address_space(4))) T* p) {
+    asm volatile("" : "+s"(p));
+    return *(const T*)(const void*)p;
+}
+__device__ __forceinline__ const ResolveArgs& resolve_args() {
+    return reload_ref((const __attribute__((address_space(4))) ResolveArgs*)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
 template <bool kSrgb, bool kBgra>
 __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P, OutputParams O) {
     __shared__ float s_thresh[258];    // sRGB code boundaries; [255..257] = NaN: never <= anything (srgb_encode_lut probes up to 256)
@@ -1562,6 +1580,7 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
         // ---- which of these blocks' strips hold anything: lane j looks at block j0 + j, all its marks in one trip to memory
         uint64_t mm, mc;       // strips with / without anything drawn
         {
+            const FrameParams& P = resolve_args().P;
             const ResolveBlock Bl = resolve_block(P, P.rblock_first + blockIdx.x + (j0 + (lane < nj ? lane : 0u)) * stride);
             bool any = false;
 #pragma unroll
@@ -1572,7 +1591,7 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
         }
         const uint32_t n_marked = (uint32_t)__popcll(mm), n_clear = (uint32_t)__popcll(mc);
         TOPO_PROF(0)      // marks
-        auto block_of = [&](uint32_t j) { return resolve_block(P, P.rblock_first + blockIdx.x + (j0 + j) * stride); };      // (j comes out of a wave-uniform mask)
+        auto block_of = [&](const FrameParams& P, uint32_t j) { return resolve_block(P, P.rblock_first + blockIdx.x + (j0 + j) * stride); };      // (j comes out of a wave-uniform mask)
         // the untouched strips are pure stores: spread over the marked strips' iterations, so that their bandwidth hides
         // under the shading
         const uint32_t fills_per_iter = n_marked ? (n_clear + n_marked - 1) / n_marked : n_clear;
@@ -1585,20 +1604,24 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
 #ifndef TOPO_EXP_KEY_PREFETCH      // every strip's keys are requested when the strip starts, none ahead (TOPO_EXP_KEY_PREFETCH: the round-2 form, see below)
         if (have) j_cur = pop_bit(mm);
         while (have) {
-            resolve_load_keys(P, block_of(j_cur), lane, wave, K);
+            // the parameters again for every strip, from the argument segment: held from the kernel's start, ~50 of them filled
+            // the scalar register file and were spilled and restored around every strip's row loop
+            const FrameParams& P = resolve_args().P;
+            const OutputParams& O = resolve_args().O;
+            resolve_load_keys(P, block_of(P, j_cur), lane, wave, K);
             // (this strip's share of the untouched strips -- pure stores -- goes out under the keys' trip to memory)
-            for (uint32_t f = 0; f < fills_per_iter && mc; ++f) resolve_fill_sky<kBgra>(P, O, block_of(pop_bit(mc)), lane, wave);
+            for (uint32_t f = 0; f < fills_per_iter && mc; ++f) resolve_fill_sky<kBgra>(P, O, block_of(P, pop_bit(mc)), lane, wave);
 #else
-        if (have) { j_cur = pop_bit(mm); resolve_load_keys(P, block_of(j_cur), lane, wave, K); }
+        if (have) { j_cur = pop_bit(mm); resolve_load_keys(P, block_of(P, j_cur), lane, wave, K); }
         while (have) {
 #endif
 #ifdef TOPO_RESOLVE_EARLY_PREFETCH      // experiment build: the next strip's keys requested at the top of the iteration, into registers of their own
             ResolveKeys Kn;
             const bool more = mm != 0ull;
             uint32_t j_next = 0;
-            if (more) { j_next = pop_bit(mm); resolve_load_keys(P, block_of(j_next), lane, wave, Kn); }
+            if (more) { j_next = pop_bit(mm); resolve_load_keys(P, block_of(P, j_next), lane, wave, Kn); }
 #endif
-            const ResolveBlock B = block_of(j_cur);
+            const ResolveBlock B = block_of(P, j_cur);
             const int32_t px = B.bx + tx, y0 = B.by + sy0;
             const bool in_x = px < P.W;        // lanes beyond the target's right edge stay: they compute triangle records
             const int32_t n_rows = P.H - y0 < kRPW ? P.H - y0 : kRPW;      // rows of the strip inside the target (>= 1)
@@ -1608,8 +1631,9 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
 #undef TOPO_X
             TOPO_PROF(2)  // wait for this strip's keys
             const bool any_terrain = __ballot(terrain) != 0ull;
-            RowN<uint32_t> n_row;
+            uint64_t n_row = 0;            // byte r: table entries of row r (<= kRecCap + 1; one word instead of kRPW registers)
             uint32_t n_all = 0;            // table entries of the strip
+            bool over = false;             // a row has more entries than the table holds
             if (any_terrain) {
                 wave_lds_fence();              // (the previous strip's reads of the tiles are done)
 #define TOPO_X(r, m) lin_tile[r + 1][tx + 1] = linear_depth(bits_f(K.raw.m));
@@ -1638,12 +1662,14 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
         const uint32_t left = (uint32_t)__shfl_up((int)K.id.m, 1);                                                              \
         const bool leader = valid && (lane == 0 || K.id.m != left);                                                             \
         const uint64_t mask = __ballot(leader);                                                                                 \
-        n_row.m = (uint32_t)__popcll(mask);                                                                                     \
-        if (n_all + n_row.m > 254u) n_row.m = kRecCap + 1u; /* (entry numbers are bytes: such a row is shaded in one step per pixel) */ \
+        uint32_t n = (uint32_t)__popcll(mask);                                                                                  \
+        if (n_all + n > 254u) n = kRecCap + 1u; /* (entry numbers are bytes: such a row is shaded in one step per pixel) */     \
         const uint32_t slot = n_all + (uint32_t)__popcll(mask & ((2ull << lane) - 1ull)) - 1u; /* valid lanes: the last leader at or before them */ \
-        slot_tile[r][tx] = (uint8_t)(valid && n_row.m <= kRecCap ? slot : 0xFFu);                                               \
-        if (leader && n_row.m <= kRecCap && slot < kRecCap) s_uid[wave][slot] = K.id.m; /* the first group's ids (later groups: below) */ \
-        n_all += n_row.m <= kRecCap ? n_row.m : 0u;                                                                             \
+        slot_tile[r][tx] = (uint8_t)(valid && n <= kRecCap ? slot : 0xFFu);                                                     \
+        if (leader && n <= kRecCap && slot < kRecCap) s_uid[wave][slot] = K.id.m; /* the first group's ids (later groups: below) */ \
+        n_all += n <= kRecCap ? n : 0u;                                                                                         \
+        n_row |= (uint64_t)n << (8 * r);                                                                                        \
+        over |= n > kRecCap;                                                                                                    \
     }
                 TOPO_ROWS(TOPO_X)
 #undef TOPO_X
@@ -1663,11 +1689,11 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
 #ifndef TOPO_EXP_KEY_PREFETCH
             if (more) j_next = pop_bit(mm);
 #else
-            if (more) { j_next = pop_bit(mm); resolve_load_keys(P, block_of(j_next), lane, wave, K); }
+            if (more) { j_next = pop_bit(mm); resolve_load_keys(P, block_of(P, j_next), lane, wave, K); }
 #endif
 #endif
 #ifdef TOPO_EXP_KEY_PREFETCH
-            for (uint32_t f = 0; f < fills_per_iter && mc; ++f) resolve_fill_sky<kBgra>(P, O, block_of(pop_bit(mc)), lane, wave);
+            for (uint32_t f = 0; f < fills_per_iter && mc; ++f) resolve_fill_sky<kBgra>(P, O, block_of(P, pop_bit(mc)), lane, wave);
 #endif
             TOPO_PROF(1)  // issue of the next keys + sky fills
             if (!any_terrain) {                // marked, but every key still cleared (a mark covers 64 keys): the cleared texel and depth 1
@@ -1680,7 +1706,6 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
                 continue;
             }
             uint8_t* rgba_p = O.rgba + (size_t)B.view * O.rgba_view_stride + (size_t)y0 * O.rgba_pitch + (size_t)px * 4;
-            const ViewDev& view = P.views[B.view];
             // what fs_main reads of the view, once per strip and wave-uniform: left to the compiler these are re-loaded in every
             // row (it cannot prove the output stores do not alias them) behind an s_waitcnt vmcnt(0) that also waits for the
             // previous row's stores to land
@@ -1703,10 +1728,7 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
             // one step per pixel (resolve_varyings), as every row was in round 1.
             int32_t r0 = 0;
             uint32_t gbase = 0;            // table entries of the groups before this one
-            bool one_group = n_all <= kRecCap;
-#define TOPO_X(r, m) one_group = one_group && n_row.m <= kRecCap;
-            TOPO_ROWS(TOPO_X)
-#undef TOPO_X
+            const bool one_group = n_all <= kRecCap && !over;
 #pragma unroll 1
             while (r0 < n_rows) {
                 int32_t r1;
@@ -1718,10 +1740,15 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
                 } else {
                     r1 = r0;
                     cnt = 0;
-#define TOPO_X(r, m) if (r >= r0 && r == r1 && n_row.m <= kRecCap && cnt + n_row.m <= kRecCap) { cnt += n_row.m; r1 = r + 1; }
-                    TOPO_ROWS(TOPO_X)
-#undef TOPO_X
-                    if (r1 > n_rows) r1 = n_rows;
+                    // (a loop, not unrolled over the rows: unrolled, the compiler decodes every row's count ahead of the group loop
+                    // and holds the results in scalar registers across it)
+#pragma unroll 1
+                    for (int32_t r = r0; r < n_rows; ++r) {
+                        const uint32_t n = (uint32_t)(n_row >> (8 * r)) & 0xFFu;
+                        if (n > kRecCap || cnt + n > kRecCap) break;
+                        cnt += n;
+                        r1 = r + 1;
+                    }
                     if (r1 == r0) {            // the row at r0 alone exceeds the table
                         table = false;
                         r1 = r0 + 1;
@@ -1740,6 +1767,8 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
                 if (table && cnt) {            // one triangle per lane: everything that depends on the triangle alone
                     wave_lds_fence();
                     if (lane < cnt) {
+                        const FrameParams& P = resolve_args().P;
+                        const ViewDev& view = reload_ref(view_c);
                         const uint32_t id = s_uid[wave][lane];
                         const uint32_t draw = id >> 1, fan = id & 1u;
                         const uint32_t rank = fastdiv(draw, P.div_tris), tri = draw - rank * P.tris_per_tile;
@@ -1796,6 +1825,8 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
                                 { const uint32_t n3 = (uint32_t)__popcll(__ballot(rec.kind == 3u)); if (n3 && lane == (uint32_t)__builtin_ctzll(__ballot(true))) atomicAdd(&P.counters[11], n3); }
     #endif
                             } else {
+                                const FrameParams& P = resolve_args().P;
+                                const ViewDev& view = reload_ref(view_c);
                                 const uint32_t draw = sel >> 1, fan = sel & 1u;
                                 const uint32_t rank = fastdiv(draw, P.div_tris), tri = draw - rank * P.tris_per_tile;
                                 ok = TOPO_CHK(P.counters, rank < P.n_tiles, 13u, sel) &&
@@ -1836,7 +1867,10 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
             K = Kn;
 #endif
         }
-        while (mc) resolve_fill_sky<kBgra>(P, O, block_of(pop_bit(mc)), lane, wave);
+        while (mc) {
+            const FrameParams& P = resolve_args().P;
+            resolve_fill_sky<kBgra>(P, resolve_args().O, block_of(P, pop_bit(mc)), lane, wave);
+        }
         TOPO_PROF(1)
     }
 #ifdef TOPO_RESOLVE_PROF
