@@ -294,6 +294,25 @@ int topo_set_timing_slots(topo_ctx* ctx, uint32_t slot_mask);
  * (>= 64 px across or near-clipped), [4] far blocks occlusion-tested, [5] far blocks that survived the test. */
 int topo_get_counters(topo_ctx* ctx, uint32_t out[6]);
 
+/* ---- viewshed: which ground the rendered frames show ------------------------------------------------------------
+ * A tile of w x h texels has (w-1) x (h-1) cells; cell (x, y) is the quad between texels (x, y) and (x+1, y+1), row 0
+ * north.  With accumulation on, every frame the context renders afterwards (topo_render, topo_render_device, every view of
+ * topo_render_views_device, topo_render_batch, topo_render_panorama) marks each cell one of whose two triangles owns at least
+ * one pixel of the frame, OR-ed into a mask per tile that persists until topo_viewshed_reset: eight panorama sectors give the
+ * 360-degree viewshed, a batch of viewpoints what is seen from any of them.  A frame whose rare-triangle queue overflowed
+ * (incomplete: see topo_join) marks nothing.  A tile added while the masks exist starts empty, also when it replaces one;
+ * topo_unload_terrain frees its mask; the masks of tiles that stay survive topo_change_location.  Multi-GPU: each rank's
+ * masks cover the sectors that rank rendered; combining them across ranks is the caller's job. */
+/* on != 0: every later frame ORs the cells that won >= 1 pixel into per-tile masks (allocated on first use, 1 bit per
+ * cell); 0: stop accumulating (the masks are kept). */
+int topo_viewshed_enable(topo_ctx* ctx, int32_t on);
+/* Empties every tile's mask (waits for the frames in flight). */
+int topo_viewshed_reset(topo_ctx* ctx);
+/* The tile's mask as (h-1) rows of (w-1) bytes, 0/1, row 0 north, into host memory with the given row pitch (waits for the
+ * frames in flight); *n_visible_out (may be NULL) = the number of marked cells.  TOPO_ERR_NOT_FOUND for a tile that is not
+ * loaded, TOPO_ERR_INVALID if accumulation was never enabled. */
+int topo_viewshed_read(topo_ctx* ctx, int32_t lat_deg, int32_t lon_deg, uint8_t* mask_out, size_t pitch, uint64_t* n_visible_out);
+
 /* ---- host-side helpers mirroring the reference's CPU code ---------------------------------------------- */
 
 /* Uniforms::new(&camera, bounds) with Camera{eye, yaw, pitch, fov_y, NEAR, FAR, view_mode, sun_angle{theta,phi}}:

@@ -25,6 +25,11 @@ int topo_debug_set_queue_caps(topo_ctx* ctx, uint32_t big_cap, uint32_t rare_cap
  * TOPO_FAR_SKIP=0 in the environment always launches it. */
 int topo_debug_far_phase_launched(topo_ctx* ctx, int32_t* out);
 
+/* Test accessor: what k_viewshed did since accumulation was first enabled or last reset (waits for the frames in flight):
+ * out[0] = terrain keys it read, out[1] = mask-word updates left after combining neighbouring lanes, out[2] = atomics issued
+ * (updates that set at least one new bit).  All 0 before accumulation was ever enabled. */
+int topo_debug_viewshed_stats(topo_ctx* ctx, uint64_t out[3]);
+
 /* Test accessor: the tile's Rgba8Unorm normal texture, w*h*4 bytes, host pointer. */
 int topo_read_normals(topo_ctx* ctx, int32_t lat_deg, int32_t lon_deg, uint8_t* out);
 

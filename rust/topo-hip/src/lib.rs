@@ -45,6 +45,8 @@ pub struct TerrainRenderer {
     /// Depth32Float rows `pad_256(4 * width)` bytes apart: what `RenderEngine::get_visible_labels` indexes
     /// (render_engine.rs:364-370)
     pub depth_read: Vec<u8>,
+    /// (w, h) texels of the loaded tiles (one size for all: mixed sizes are rejected), once one was added
+    tile_size: Option<(u32, u32)>,
 }
 
 impl TerrainRenderer {
@@ -54,7 +56,7 @@ impl TerrainRenderer {
         check(ptr::null_mut(), unsafe {
             sys::topo_create(&mut ctx, hip_device, target_size.0, target_size.1, sys::TOPO_FORMAT_RGBA8_UNORM_SRGB)
         })?;
-        Ok(Self { ctx, target_size, frame: Vec::new(), depth_read: Vec::new() })
+        Ok(Self { ctx, target_size, frame: Vec::new(), depth_read: Vec::new(), tile_size: None })
     }
 
     /// was: `update(device, queue, target_size, &uniforms, &postprocessing_uniforms)` -- :151.
@@ -73,12 +75,20 @@ impl TerrainRenderer {
         check(self.ctx, unsafe {
             sys::topo_add_terrain(self.ctx, location.0, location.1, height_map_data.as_ptr() as *const f32, size.0, size.1,
                                   ct.raster_point.as_ptr(), ct.model_point.as_ptr(), ct.pixel_scale.as_ptr())
-        })
+        })?;
+        self.tile_size = Some(size);
+        Ok(())
     }
 
     /// `fetch_terrain`'s decode step folded in (background_runner.rs:113-136): the downloaded GeoTIFF bytes straight to a tile.
     pub fn add_terrain_geotiff(&mut self, location: (i32, i32), tiff_bytes: &[u8]) -> Result<(), TopoError> {
-        check(self.ctx, unsafe { sys::topo_add_terrain_geotiff(self.ctx, location.0, location.1, tiff_bytes.as_ptr(), tiff_bytes.len()) })
+        check(self.ctx, unsafe { sys::topo_add_terrain_geotiff(self.ctx, location.0, location.1, tiff_bytes.as_ptr(), tiff_bytes.len()) })?;
+        let (mut w, mut h, mut rp, mut mp, mut ps) = (0u32, 0u32, [0f32; 2], [0f32; 2], [0f32; 2]);
+        check(self.ctx, unsafe {
+            sys::topo_geotiff_info(tiff_bytes.as_ptr(), tiff_bytes.len(), &mut w, &mut h, rp.as_mut_ptr(), mp.as_mut_ptr(), ps.as_mut_ptr())
+        })?;
+        self.tile_size = Some((w, h));
+        Ok(())
     }
 
     /// was: `unload_terrain(&location)` -- :361
@@ -128,6 +138,27 @@ impl TerrainRenderer {
 
     pub fn synchronize(&mut self) -> Result<(), TopoError> {
         check(self.ctx, unsafe { sys::topo_synchronize(self.ctx) })
+    }
+
+    /// Viewshed (new): while on, every frame ORs the DEM cells that won at least one pixel into per-tile masks.
+    pub fn viewshed_enable(&mut self, on: bool) -> Result<(), TopoError> {
+        check(self.ctx, unsafe { sys::topo_viewshed_enable(self.ctx, on as i32) })
+    }
+
+    /// Empties every tile's viewshed mask.
+    pub fn viewshed_reset(&mut self) -> Result<(), TopoError> {
+        check(self.ctx, unsafe { sys::topo_viewshed_reset(self.ctx) })
+    }
+
+    /// The viewshed mask of the tile at `location`: (h-1) rows of (w-1) cells, 0/1, row 0 north; and the number of marked
+    /// cells.  The buffer is sized from the tile size this wrapper recorded when the tiles were added, never from the caller.
+    pub fn viewshed(&mut self, location: (i32, i32)) -> Result<(Vec<u8>, u64), TopoError> {
+        let (w, h) = self.tile_size.ok_or_else(|| TopoError { code: sys::TOPO_ERR_NOT_FOUND, message: "no tile loaded".into() })?;
+        let (cw, ch) = (w as usize - 1, h as usize - 1);      // (add_terrain rejects tiles under 3 x 3)
+        let mut mask = vec![0u8; cw * ch];
+        let mut n = 0u64;
+        check(self.ctx, unsafe { sys::topo_viewshed_read(self.ctx, location.0, location.1, mask.as_mut_ptr(), cw, &mut n) })?;
+        Ok((mask, n))
     }
 }
 

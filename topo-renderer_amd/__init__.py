@@ -139,6 +139,10 @@ def lib():
             "topo_to_model": (None, [vp, vp, vp, f32, f32, vp]),
             "topo_to_raster": (None, [vp, vp, vp, f32, f32, vp]),
             "topo_height_value_at": (C.c_int, [vp, u32, u32, vp, vp, vp, C.c_double, C.c_double, vp]),
+            "topo_viewshed_enable": (C.c_int, [vp, i32]),
+            "topo_viewshed_reset": (C.c_int, [vp]),
+            "topo_viewshed_read": (C.c_int, [vp, i32, i32, vp, sz, vp]),
+            "topo_debug_viewshed_stats": (C.c_int, [vp, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -584,6 +588,32 @@ class TerrainRenderer:
         u = np.ascontiguousarray(uniforms).view(np.uint8)
         self._check(lib().topo_visible_peaks_device(self._h, _p(u), width, height, C.c_void_p(depth_ptr), depth_pitch, n,
                                                     C.c_void_p(peaks_ptr), C.c_void_p(visible_ptr), C.c_void_p(xy_ptr)))
+
+    # viewshed: the DEM cells the frames rendered while accumulation is on show (include/topo_hip.h)
+    def viewshed_enable(self, on: bool = True):
+        """Every later frame ORs the cells that won >= 1 pixel into per-tile masks (on), or stops doing so (the masks stay)."""
+        self._check(lib().topo_viewshed_enable(self._h, 1 if on else 0))
+
+    def viewshed_reset(self):
+        self._check(lib().topo_viewshed_reset(self._h))
+
+    def viewshed(self, lat_deg, lon_deg) -> np.ndarray:
+        """The tile's mask: (h-1, w-1) bool, cell (x, y) = the quad between texels (x, y) and (x+1, y+1), row 0 north."""
+        if self.tile_size is None:
+            raise TopoError(TOPO_ERR_NOT_FOUND, "no tile loaded")
+        w, h = self.tile_size
+        out = np.zeros((h - 1, w - 1), np.uint8)
+        n = C.c_uint64(0)
+        self._check(lib().topo_viewshed_read(self._h, lat_deg, lon_deg, _p(out), w - 1, C.byref(n)))
+        if int(out.sum()) != n.value:
+            raise TopoError(TOPO_ERR_INVALID, f"viewshed count {n.value} differs from the mask's {int(out.sum())} cells")
+        return out.astype(bool)
+
+    def debug_viewshed_stats(self) -> dict:
+        """What k_viewshed did since the masks were made or last reset (include/topo_hip_test.h)."""
+        out = np.zeros(3, np.uint64)
+        self._check(lib().topo_debug_viewshed_stats(self._h, _p(out)))
+        return {"terrain_keys": int(out[0]), "updates": int(out[1]), "atomics": int(out[2])}
 
     def probe_div(self, kind: int, x: np.ndarray, y: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

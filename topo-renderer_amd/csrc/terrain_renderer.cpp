@@ -77,8 +77,9 @@ TerrainRenderer::~TerrainRenderer() {
         if (c.stream) (void)hipStreamSynchronize(c.stream);
     for (auto& kv : tiles_) {
         (void)hipFree(kv.second.d_pool);
+        if (kv.second.d_mask) (void)hipFree(kv.second.d_mask);
     }
-    void* bufs[] = {d_tiles_, d_views_, d_out_rgba_, d_out_depth_, d_edge_jobs_, d_corner_jobs_, d_peaks_, d_proj_, d_overlay_geo_, d_overlay_keys_};
+    void* bufs[] = {d_tiles_, d_vs_table_, d_vs_stats_, d_views_, d_out_rgba_, d_out_depth_, d_edge_jobs_, d_corner_jobs_, d_peaks_, d_proj_, d_overlay_geo_, d_overlay_keys_};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (auto& c : ctx_) {
@@ -216,6 +217,11 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
         (void)hipFree(t.d_pool);
         return hip_fail(e, "tile upload");
     }
+    if (vs_ever_)      // (a replaced tile's mask goes with it: the new one starts empty)
+        if (int rc = alloc_mask(t)) {
+            (void)hipFree(t.d_pool);
+            return rc;
+        }
     // TerrainUniforms::new (render/data.rs:124-151)
     t.dev.heights = t.d_heights;
     t.dev.normals = t.d_normals;
@@ -263,6 +269,7 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
     if (had_old) {
         TOPO_HIP_TRY(hipStreamSynchronize(stream_));
         (void)hipFree(old.d_pool);
+        if (old.d_mask) (void)hipFree(old.d_mask);
     }
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
@@ -293,6 +300,7 @@ int TerrainRenderer::unload_terrain(int32_t lat, int32_t lon) {
     if (int rc = join()) return rc;
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
     (void)hipFree(t->d_pool);
+    if (t->d_mask) (void)hipFree(t->d_mask);
     tiles_.erase(geo_key(lat, lon));
     table_dirty_ = true;
     return TOPO_OK;
@@ -345,6 +353,12 @@ int TerrainRenderer::upload_tile_table() {
         if (int rc = ensure(&d_tiles_, &cap_tiles_, table.size() * sizeof(TileDev))) return rc;
         TOPO_HIP_TRY(hipStreamSynchronize(stream_));
         TOPO_HIP_TRY(hipMemcpy(d_tiles_, table.data(), table.size() * sizeof(TileDev), hipMemcpyHostToDevice));
+        if (vs_ever_) {      // the viewshed's rank -> mask table: ranks shift whenever tiles come and go
+            std::vector<uint32_t*> masks;
+            for (auto& kv : tiles_) masks.push_back(kv.second.d_mask);
+            if (int rc = ensure(&d_vs_table_, &cap_vs_table_, masks.size() * sizeof(uint32_t*))) return rc;
+            TOPO_HIP_TRY(hipMemcpy(d_vs_table_, masks.data(), masks.size() * sizeof(uint32_t*), hipMemcpyHostToDevice));
+        }
     }
     table_dirty_ = false;
     return TOPO_OK;
@@ -685,11 +699,91 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
                 if (int rc = (*after_slot)(i, stream)) return rc;
         }
     }
+    if (vs_on_)      // behind the frame's last k_resolve (and its last slot): the cells that won a pixel, into the tiles' masks
+        launch_viewshed(p, (uint32_t* const*)d_vs_table_, d_vs_stats_, stream);
     if ((ev_need & (1u << 8)) && !own_times) TOPO_HIP_TRY(hipEventRecord(ev[8], stream));
     if (!p.status_out) TOPO_HIP_TRY(hipMemcpyAsync(h_status_slot, p.counters, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     ++c.submitted;
     c.timed = true;
     TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// ---- viewshed ----------------------------------------------------------------------------------------------------------------
+
+int TerrainRenderer::alloc_mask(Tile& t) {
+    TOPO_HIP_TRY(hipMalloc(&t.d_mask, mask_bytes()));
+    const hipError_t e = hipMemsetAsync(t.d_mask, 0, mask_bytes(), stream_);      // (frames on other streams are ordered after stream_)
+    if (e != hipSuccess) {
+        (void)hipFree(t.d_mask);
+        t.d_mask = nullptr;
+        return hip_fail(e, "viewshed mask");
+    }
+    return TOPO_OK;
+}
+
+// The masks are allocated when accumulation is first turned on (for the tiles loaded then; later tiles get theirs in add_terrain) and
+// kept until the tile goes; turning accumulation off only stops the launches.
+int TerrainRenderer::viewshed_enable(bool on) {
+    if (int rc = bind_device()) return rc;
+    if (on && !vs_ever_) {
+        if (int rc = join()) return rc;
+        const size_t stats = (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long);
+        if (!d_vs_stats_) {
+            TOPO_HIP_TRY(hipMalloc((void**)&d_vs_stats_, stats));
+            TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_, 0, stats, stream_));
+        }
+        for (auto& kv : tiles_)
+            if (!kv.second.d_mask)
+                if (int rc = alloc_mask(kv.second)) return rc;
+        vs_ever_ = true;
+        table_dirty_ = true;      // the next submission uploads the rank -> mask table with the tile table
+    }
+    vs_on_ = on;
+    return TOPO_OK;
+}
+
+int TerrainRenderer::viewshed_reset() {
+    if (int rc = bind_device()) return rc;
+    if (!vs_ever_) return TOPO_OK;
+    if (int rc = join()) return rc;      // frames in flight on the contexts' own streams; later ones are ordered after stream_
+    for (auto& kv : tiles_) TOPO_HIP_TRY(hipMemsetAsync(kv.second.d_mask, 0, mask_bytes(), stream_));
+    TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_, 0, (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long), stream_));
+    return TOPO_OK;
+}
+
+int TerrainRenderer::viewshed_read(int32_t lat, int32_t lon, uint8_t* mask_out, size_t pitch, uint64_t* n_visible) {
+    if (!mask_out) return fail(TOPO_ERR_INVALID, "mask_out is null");
+    Tile* t = find(lat, lon);
+    if (!t) return fail(TOPO_ERR_NOT_FOUND, "no such tile");
+    if (!vs_ever_) return fail(TOPO_ERR_INVALID, "viewshed accumulation was never enabled");
+    const uint32_t wm1 = tile_w_ - 1, hm1 = tile_h_ - 1;
+    if (pitch < wm1) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
+    if (int rc = join()) return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    std::vector<uint32_t> words(mask_bytes() / 4);
+    TOPO_HIP_TRY(hipMemcpy(words.data(), t->d_mask, mask_bytes(), hipMemcpyDeviceToHost));
+    uint64_t count = 0;
+    for (uint32_t x = 0, bit = 0; x < wm1; ++x)      // bit = x (h-1) + y: the cell of the draw id's triangle (triangle_vertices)
+        for (uint32_t y = 0; y < hm1; ++y, ++bit) {
+            const uint8_t v = (uint8_t)((words[bit >> 5] >> (bit & 31u)) & 1u);
+            mask_out[(size_t)y * pitch + x] = v;
+            count += v;
+        }
+    if (n_visible) *n_visible = count;
+    return TOPO_OK;
+}
+
+int TerrainRenderer::viewshed_stats(uint64_t out[3]) {
+    if (!out) return fail(TOPO_ERR_INVALID, "null argument");
+    out[0] = out[1] = out[2] = 0;
+    if (!vs_ever_) return TOPO_OK;
+    if (int rc = join()) return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    std::vector<unsigned long long> s((size_t)kViewshedStatSlots * 4);
+    TOPO_HIP_TRY(hipMemcpy(s.data(), d_vs_stats_, s.size() * sizeof(s[0]), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < s.size(); i += 4)
+        for (int k = 0; k < 3; ++k) out[k] += s[i + k];
     return TOPO_OK;
 }
 

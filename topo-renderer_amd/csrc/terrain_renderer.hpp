@@ -41,6 +41,7 @@ struct Tile {          // RenderBuffer (render_buffer.rs:23-31) minus the wgpu p
     // submission prove on the host that none of its blocks can be an occlusion-test candidate.  radius < 0: unknown.
     double centres[4] = {0.0, 0.0, 0.0, -1.0};
     TileDev dev{};
+    uint32_t* d_mask = nullptr;     // viewshed: 1 bit per cell (bit x (h-1) + y), once accumulation has been enabled; freed with the tile
 };
 
 class TerrainRenderer {
@@ -96,6 +97,12 @@ class TerrainRenderer {
     int visible_peaks_device(const topo_uniforms* view, uint32_t w, uint32_t h, const float* depth_dev, size_t depth_pitch,
                              uint32_t n, const float* peaks_dev, uint8_t* visible_dev, uint32_t* xy_dev);
 
+    // viewshed: the DEM cells that won >= 1 pixel of the frames rendered while accumulation is on, per tile
+    int viewshed_enable(bool on);
+    int viewshed_reset();
+    int viewshed_read(int32_t lat, int32_t lon, uint8_t* mask_out, size_t pitch, uint64_t* n_visible);
+    int viewshed_stats(uint64_t out[3]);      // test hook: terrain keys, combined updates, atomics issued since the last reset
+
     const char* last_error() const { return err_.c_str(); }
 
    private:
@@ -113,6 +120,8 @@ class TerrainRenderer {
     std::map<GeoKey, uint32_t> ranks() const;
     Tile* find(int lat, int lon);
     int upload_tile_table();
+    int alloc_mask(Tile& t);
+    size_t mask_bytes() const { return (((size_t)(tile_w_ - 1) * (tile_h_ - 1) + 31) / 32) * 4; }
 
     int device_ = 0;
     uint32_t W_ = 0, H_ = 0;
@@ -216,6 +225,11 @@ class TerrainRenderer {
     uint32_t depth_w_ = 0, depth_h_ = 0;
     uint32_t last_blocks_tested_ = 0;
     bool last_far_phase_ = true;           // whether the last submission launched the far phase (test hook)
+    // viewshed: render_frame launches k_viewshed while vs_on_; the masks exist (every tile has one) once vs_ever_.  The masks are shared
+    // by every frame context: frames in flight only OR into them, so they need no order among themselves.
+    bool vs_on_ = false, vs_ever_ = false;
+    void* d_vs_table_ = nullptr; size_t cap_vs_table_ = 0;      // rank -> the tile's mask, rebuilt with the tile table
+    unsigned long long* d_vs_stats_ = nullptr;                   // kViewshedStatSlots x 4 counters of k_viewshed
 
     std::string err_;
 };

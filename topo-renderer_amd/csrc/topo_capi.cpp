@@ -332,6 +332,26 @@ int topo_overlay_glyphs_device(topo_ctx* ctx, const topo_glyph* glyphs, uint32_t
     TOPO_CALL(ctx->r->overlay_glyphs_device(glyphs, n_glyphs, depth, atlas_mask, atlas_w, atlas_h, rgba_dev, rgba_pitch));
 }
 
+int topo_viewshed_enable(topo_ctx* ctx, int32_t on) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->viewshed_enable(on != 0));
+}
+
+int topo_viewshed_reset(topo_ctx* ctx) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->viewshed_reset());
+}
+
+int topo_viewshed_read(topo_ctx* ctx, int32_t lat_deg, int32_t lon_deg, uint8_t* mask_out, size_t pitch, uint64_t* n_visible_out) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->viewshed_read(lat_deg, lon_deg, mask_out, pitch, n_visible_out));
+}
+
+int topo_debug_viewshed_stats(topo_ctx* ctx, uint64_t out[3]) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->viewshed_stats(out));
+}
+
 int topo_frame_status(topo_ctx* ctx, uint32_t out[4]) {
     TOPO_GUARD(ctx);
     if (!out) return TOPO_ERR_INVALID;

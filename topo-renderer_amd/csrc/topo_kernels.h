@@ -139,6 +139,11 @@ void launch_raster_rare(const FrameParams& p, hipStream_t s);
 void launch_raster_big(const FrameParams& p, hipStream_t s);
 void launch_resolve(const FrameParams& p, const OutputParams& o, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
+// viewshed (topo_viewshed_*), behind the frame's last k_resolve: the DEM cells that won a pixel, OR-ed into per-tile bit masks.
+// masks: device table, rank -> the tile's mask (bit = cell = x (h-1) + y); stats: kViewshedStatSlots x 4 counters (k_viewshed).
+constexpr uint32_t kViewshedStatSlots = 1024;
+void launch_viewshed(const FrameParams& p, uint32_t* const* masks, unsigned long long* stats, hipStream_t s);
+
 // overlay pass (line_shader.wgsl over the post pass's image): keys = W*H overlay keys, (re-)initialised when keys_fresh
 void launch_overlay(const OverlayVertex* verts, const uint32_t* idx, uint32_t n_tris, uint32_t n_verts, float width, int32_t W, int32_t H, uint64_t* keys,
                     bool keys_fresh, uint8_t* rgba, size_t pitch, uint32_t linear_target, uint32_t bgra, hipStream_t s);

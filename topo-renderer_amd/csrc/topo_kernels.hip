@@ -1882,6 +1882,89 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
 #undef TOPO_PROF
 }
 
+// Viewshed (topo_viewshed_*): after the frame's last k_resolve, every DEM cell that owns at least one pixel of the visibility
+// buffer gets its bit set in the mask of its tile.  A key's low word is draw << 1 | fan (the two halves of a near-clipped triangle),
+// draw = rank * tris_per_tile + triangle; bit = cell = triangle >> 1 = x (h-1) + y; masks[rank] is the mask of the tile at that
+// rank.  A frame whose rare-triangle queue overflowed is incomplete -- farther triangles won pixels they should not have -- and
+// marks nothing.  A wave takes 64 segments at a time (one coalesced read of their marks, as k_clear); unmarked
+// segments are sky.  Of each marked segment's 64 keys, a run of neighbouring lanes that hit the same mask word is combined into its
+// last lane (a segmented OR over as many doubling steps as the longest run needs), and only that lane updates the word: a load,
+// and the atomicOr only when it would set a bit (issued blind, the atomics cost 6x as much at c4: DESIGN.md §5,
+// tools/experiments/viewshed_blind_atomics_experiment.patch).  kBatch segments are taken at once so that their key loads -- and
+// then their mask loads -- are in flight together.
+// stats (per workgroup, 4 words): [0] terrain keys, [1] combined updates (run tails), [2] atomics issued.
+__global__ __launch_bounds__(256) void k_viewshed(FrameParams P, uint32_t* const* __restrict__ masks, unsigned long long* __restrict__ stats) {
+    if (P.counters[2] & kStatusRareOverflow) return;
+    constexpr int kBatch = 4;
+    constexpr uint32_t kSky = 0xFFFFFFFFu;
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t n = (size_t)P.n_views * P.W * P.H, nseg = (n + 63) >> 6;
+    const size_t wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwave = (size_t)gridDim.x * 4;
+    const uint32_t cells = P.tris_per_tile >> 1, words = (cells + 31) >> 5;
+    uint64_t n_keys = 0, n_tails = 0, n_atomics = 0;
+    for (size_t g = wave * 64; g < nseg; g += nwave * 64) {
+        uint64_t todo = __ballot(g + lane < nseg && P.dirty[g + lane] != 0);
+        while (todo) {
+            uint32_t t[kBatch], rank[kBatch], word[kBatch], bit[kBatch], cur[kBatch];
+            uint64_t heads[kBatch];
+            bool tail[kBatch];
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) {
+                t[b] = kSky;
+                if (todo) {
+                    const size_t at = (g + (size_t)__builtin_ctzll(todo)) * 64 + lane;
+                    todo &= todo - 1;
+                    if (at < n) t[b] = (uint32_t)P.vis[at];      // the key's low word: draw << 1 | fan
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) {
+                rank[b] = 0; word[b] = 0; bit[b] = 0;
+                if (t[b] != kSky) {
+                    const uint32_t draw = t[b] >> 1;
+                    rank[b] = fastdiv(draw, P.div_tris);
+                    const uint32_t cell = (draw - rank[b] * P.tris_per_tile) >> 1;
+                    word[b] = cell >> 5;
+                    bit[b] = 1u << (cell & 31u);
+                    t[b] = rank[b] * words + word[b];      // the run key: one mask word of one tile (< 2^26: ids are < 2^31)
+                }
+                n_keys += (uint64_t)__popcll(__ballot(t[b] != kSky));
+                const uint32_t prev = __shfl_up(t[b], 1);
+                heads[b] = __ballot(lane == 0 || prev != t[b]);
+                // The OR takes a lane d back whenever it holds the same word, with no segment flag: a run is contiguous, so a lane of
+                // ANOTHER run with the same word (A B A) only adds bits of that same word -- still right for the word the tail updates --
+                // and every lane of the tail's own run is reached, because a step's source lane outside the run has nothing of the run
+                // behind it either.
+                uint64_t need = ~heads[b];      // lanes whose run reaches back further than the bits gathered so far
+                for (uint32_t d = 1; need; d <<= 1) {
+                    const uint32_t tp = __shfl_up(t[b], d), bp = __shfl_up(bit[b], d);
+                    if (lane >= d && tp == t[b]) bit[b] |= bp;      // (a lane further back with the same word: its bits belong there too)
+                    need &= need << d;
+                }
+                tail[b] = t[b] != kSky && (lane == 63 || ((heads[b] >> (lane + 1)) & 1u));
+                n_tails += (uint64_t)__popcll(__ballot(tail[b]));
+                // (the table index is tested in the product build too: what it reads is a pointer)
+                if (tail[b] && !(TOPO_CHK(P.counters, rank[b] < P.n_tiles && word[b] < words, 16u, t[b]) && rank[b] < P.n_tiles && word[b] < words))
+                    tail[b] = false;
+            }
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) cur[b] = tail[b] ? masks[rank[b]][word[b]] : 0u;
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) {
+                const bool issue = tail[b] && (cur[b] & bit[b]) != bit[b];
+                n_atomics += (uint64_t)__popcll(__ballot(issue));
+                if (issue) atomicOr(&masks[rank[b]][word[b]], bit[b]);
+            }
+        }
+    }
+    if (lane == 0 && n_keys) {      // (n_keys == 0: nothing else is either)
+        unsigned long long* s = stats + (size_t)blockIdx.x * 4;
+        atomicAdd(&s[0], (unsigned long long)n_keys);
+        atomicAdd(&s[1], (unsigned long long)n_tails);
+        atomicAdd(&s[2], (unsigned long long)n_atomics);
+    }
+}
+
 // The post pass with the pixelise branch on (postprocessing_shader.wgsl:70-74; never in the reference, which pins pixelize_n to
 // 100): the colour is a sample of the render target AWAY from the pixel's own texel, so the frame takes two passes -- k_resolve
 // stores the render-target texels (post_off), this kernel samples them (sample_pixelized), takes the contour from the depth
@@ -2325,6 +2408,13 @@ void launch_resolve(const FrameParams& p, const OutputParams& o, hipStream_t s, 
     else if (!p.linear_target) launch(k_resolve<true, true>);
     else if (!bgra) launch(k_resolve<false, false>);
     else launch(k_resolve<false, true>);
+}
+
+void launch_viewshed(const FrameParams& p, uint32_t* const* masks, unsigned long long* stats, hipStream_t s) {
+    if (p.n_tiles == 0) return;
+    const size_t groups = (((size_t)p.n_views * p.W * p.H + 63) / 64 + 63) / 64;      // 64 segments of 64 keys per wave and step
+    const unsigned grid = (unsigned)((groups + 3) / 4 < kViewshedStatSlots ? (groups + 3) / 4 : kViewshedStatSlots);
+    hipLaunchKernelGGL(k_viewshed, dim3(grid), dim3(256), 0, s, p, masks, stats);
 }
 
 void launch_overlay(const OverlayVertex* verts, const uint32_t* idx, uint32_t n_tris, uint32_t n_verts, float width, int32_t W, int32_t H, uint64_t* keys,
