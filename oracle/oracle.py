@@ -155,6 +155,17 @@ class OracleRenderer:
         self._check(lib().oracle_render(self._h, _p(rgba), w * 4, _p(depth), w * 4, _p(pre) if pre is not None else None))
         return (rgba, depth, pre) if want_pre_post else (rgba, depth)
 
+    def render_window(self, x0, y0, w, h):
+        """The pixels [x0, x0+w) x [y0, y0+h) of render()'s frame, byte for byte, without rendering the rest of the target:
+        (rgba (h, w, 4), depth (h, w)).  Refused for the pixelise branch."""
+        L = lib()
+        L.oracle_render_window.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t]
+        rgba = np.empty((h, w, 4), np.uint8)
+        depth = np.empty((h, w), np.float32)
+        self._check(L.oracle_render_window(self._h, x0, y0, w, h, _p(rgba), w * 4, _p(depth), w * 4))
+        return rgba, depth
+
     def render_views_tiled(self, uniforms_list, threads, groups):
         """render_views with more threads than frames: each frame's tiles in `groups` runs of the draw order, merged per pixel."""
         w, h = self.size

@@ -410,7 +410,10 @@ void fs_main(const Uniforms& u, float frag_x, float frag_y, v3 wpos, v3 wnrm, fl
  * One frame (terrain_renderer.rs:365-452): clear, draws, post.
  * ------------------------------------------------------------------------------------------ */
 struct Frame {
-    uint32_t W, H;
+    uint32_t W, H;                /* the render target: viewport, clip-space reconstruction and the post taps' clamps */
+    /* the rectangle of the target the buffers below hold (bx, by, bw x bh): the whole target, or for oracle_render_window
+     * the window plus a 1 px ring clamped to the target.  Everything outside it is skipped, nothing else changes. */
+    uint32_t bx = 0, by = 0, bw = 0, bh = 0;
     std::vector<float> depth;     /* Depth32Float, clear 1.0 (terrain_renderer.rs:392) */
     std::vector<uint8_t> color;   /* render_texture, Rgba8UnormSrgb */
     std::vector<uint8_t> final_;  /* surface, Rgba8UnormSrgb */
@@ -474,10 +477,10 @@ void raster_triangle(Frame& f, const Uniforms& u, const VSOut& v0, const VSOut& 
     int64_t minX = std::min(s0.X, std::min(s1.X, s2.X)), maxX = std::max(s0.X, std::max(s1.X, s2.X));
     int64_t minY = std::min(s0.Y, std::min(s1.Y, s2.Y)), maxY = std::max(s0.Y, std::max(s1.Y, s2.Y));
     /* pixel centres at (px*256+128, py*256+128) */
-    int64_t x0 = std::max<int64_t>(0, floor_div(minX - 128 + 255, 256));
-    int64_t x1 = std::min<int64_t>((int64_t)f.W - 1, floor_div(maxX - 128, 256));
-    int64_t y0 = std::max<int64_t>(0, floor_div(minY - 128 + 255, 256));
-    int64_t y1 = std::min<int64_t>((int64_t)f.H - 1, floor_div(maxY - 128, 256));
+    int64_t x0 = std::max<int64_t>(f.bx, floor_div(minX - 128 + 255, 256));
+    int64_t x1 = std::min<int64_t>((int64_t)f.bx + f.bw - 1, floor_div(maxX - 128, 256));
+    int64_t y0 = std::max<int64_t>(f.by, floor_div(minY - 128 + 255, 256));
+    int64_t y1 = std::min<int64_t>((int64_t)f.by + f.bh - 1, floor_div(maxY - 128, 256));
     if (x0 > x1 || y0 > y1) return;
     /* F_ab(p) = (by-ay)(px-ax) - (bx-ax)(py-ay): >= 0 inside for this winding.
      * Top-left rule: edge a->b owns its boundary iff it is a left edge (dy > 0) or a top edge
@@ -502,7 +505,7 @@ void raster_triangle(Frame& f, const Uniforms& u, const VSOut& v0, const VSOut& 
             float z = fmaf(b1, dz1, fmaf(b2, dz2, s0.z));
             if (!(z < 1.0f)) continue; /* far plane (and NaN) */
             if (z < 0.0f) z = 0.0f;
-            const size_t p = (size_t)py * f.W + (size_t)px;
+            const size_t p = (size_t)(py - f.by) * f.bw + (size_t)(px - f.bx);
             if (!(z < f.depth[p])) continue; /* CompareFunction::Less */
             /* perspective-correct varyings: weights q_i, a = (a0 q0 + a1 q1 + a2 q2) / (q0 + q1 + q2) */
             const VSOut *a0 = &v0, *a1 = &v1, *a2 = &v2;
@@ -654,12 +657,15 @@ static void sample_pixelized(const Frame& f, const PostUniforms& pu, int px, int
  * centres (viewport == target size), so every tap is an exact texel fetch; depth taps clamp to the
  * edge (default sampler: texture.rs:113-117).  pixelize_n < 99.99999 (never in the reference, which always passes 100:
  * application_data.rs:31) moves the COLOUR sample to floor(uv n) / n: sample_pixelized() above. */
-void post_pass(Frame& f, const PostUniforms& pu) {
-    const int W = (int)f.W, H = (int)f.H;
+/* [x0, x1) x [y0, y1): the target pixels to produce, inside the frame's buffer rectangle with their 1 px ring (clamped to the
+ * target), which the depth taps read. */
+void post_pass(Frame& f, const PostUniforms& pu, int x0, int y0, int x1, int y1) {
+    const int W = (int)f.W, H = (int)f.H, bx = (int)f.bx, by = (int)f.by;
+    const size_t bw = f.bw;
     const bool pixelize = pu.pixelize_n < 99.99999f;
-    for (int py = 0; py < H; ++py)
-        for (int px = 0; px < W; ++px) {
-            const size_t p = (size_t)py * W + px;
+    for (int py = y0; py < y1; ++py)
+        for (int px = x0; px < x1; ++px) {
+            const size_t p = (size_t)(py - by) * bw + (px - bx);
             const uint8_t* c8 = &f.color[p * 4];
             const bool is_srgb = format_is_srgb(f.format);
             float rc[4] = {is_srgb ? srgb().decode[c8[0]] : from_unorm8(c8[0]), is_srgb ? srgb().decode[c8[1]] : from_unorm8(c8[1]),
@@ -671,7 +677,7 @@ void post_pass(Frame& f, const PostUniforms& pu) {
                 for (int j = -1; j <= 1; ++j) {
                     if (i == 0 && j == 0) continue;
                     int sx = std::min(std::max(px + i, 0), W - 1), sy = std::min(std::max(py + j, 0), H - 1);
-                    contour -= dist_from_depth(f.depth[(size_t)sy * W + sx]);
+                    contour -= dist_from_depth(f.depth[(size_t)(sy - by) * bw + (sx - bx)]);
                 }
             float a = smoothstep(0.05f, 0.15f, contour / center_linear);
             const float cc[4] = {0.0f, 0.0f, 0.0f, 1.0f};
@@ -699,9 +705,13 @@ struct Oracle {
     }
 };
 
-void render_frame(const Oracle& o, const Uniforms& u, Frame& f) {
+/* The frame, or (bw > 0) only the pixels [x0, x0 + w) x [y0, y0 + h) of it, byte for byte the same. */
+void render_frame(const Oracle& o, const Uniforms& u, Frame& f, uint32_t x0 = 0, uint32_t y0 = 0, uint32_t w = 0, uint32_t h = 0) {
     f.W = o.W; f.H = o.H; f.format = o.format;
-    const size_t P = (size_t)o.W * o.H;
+    if (w == 0) { x0 = 0; y0 = 0; w = o.W; h = o.H; }
+    f.bx = x0 > 0 ? x0 - 1 : 0; f.by = y0 > 0 ? y0 - 1 : 0;
+    f.bw = std::min(x0 + w + 1, o.W) - f.bx; f.bh = std::min(y0 + h + 1, o.H) - f.by;
+    const size_t P = (size_t)f.bw * f.bh;
     f.depth.assign(P, 1.0f);
     f.color.resize(P * 4);
     f.final_.resize(P * 4);
@@ -713,7 +723,7 @@ void render_frame(const Oracle& o, const Uniforms& u, Frame& f) {
         draw_tile(f, u, *kv.second, rank * 2u * (kv.second->w - 1) * (kv.second->h - 1));
         ++rank;
     }
-    post_pass(f, o.pu);
+    post_pass(f, o.pu, (int)x0, (int)y0, (int)(x0 + w), (int)(y0 + h));
 }
 
 void copy_out(const Frame& f, uint8_t* rgba, size_t rgba_pitch, float* depth, size_t depth_pitch,
@@ -803,6 +813,24 @@ int oracle_render(void* p, uint8_t* rgba, size_t rgba_pitch, float* depth, size_
     return 0;
 }
 
+/* The pixels [x0, x0 + w) x [y0, y0 + h) of the current W x H target, byte for byte those of oracle_render's frame: only the
+ * window and a 1 px ring (clamped to the target; the contour taps read it) are rasterised and post-processed, so a window of a
+ * 2^31 px target costs the vertex stage plus its own pixels.  The pixelise branch samples away from the pixel: refused. */
+int oracle_render_window(void* p, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint8_t* rgba, size_t rgba_pitch, float* depth,
+                         size_t depth_pitch) {
+    Oracle& o = *(Oracle*)p;
+    if (w == 0 || h == 0 || x0 >= o.W || y0 >= o.H || w > o.W - x0 || h > o.H - y0) { o.err = "window outside the target"; return -1; }
+    if (o.pu.pixelize_n < 99.99999f) { o.err = "render_window: the pixelise branch samples outside the window"; return -2; }
+    Frame f;
+    render_frame(o, o.u, f, x0, y0, w, h);
+    for (uint32_t y = 0; y < h; ++y) {
+        const size_t row = (size_t)(y0 + y - f.by) * f.bw + (x0 - f.bx);
+        if (rgba) memcpy(rgba + (size_t)y * rgba_pitch, &f.final_[row * 4], (size_t)w * 4);
+        if (depth) memcpy((uint8_t*)depth + (size_t)y * depth_pitch, &f.depth[row], (size_t)w * 4);
+    }
+    return 0;
+}
+
 /* n independent frames over the same tile set (one per panorama sector), OpenMP over frames.
  * Output v lands at base + v*view_stride; used for the timed CPU baseline. */
 int oracle_render_views(void* p, uint32_t n, const void* uniforms160xn, uint8_t* rgba, size_t rgba_view_stride,
@@ -860,6 +888,7 @@ int oracle_render_views_tiled(void* p, uint32_t n, const void* uniforms160xn, ui
         const int v = job / groups, g = job % groups;
         Frame& f = part[job];
         f.W = o.W; f.H = o.H; f.format = o.format;
+        f.bw = o.W; f.bh = o.H;
         f.depth.assign(P, 1.0f);
         f.color.resize(P * 4);
         store_color(f, 0, clear);
@@ -880,7 +909,7 @@ int oracle_render_views_tiled(void* p, uint32_t n, const void* uniforms160xn, ui
             std::vector<uint8_t>().swap(q.color);
         }
         f.final_.resize(P * 4);
-        post_pass(f, o.pu);
+        post_pass(f, o.pu, 0, 0, (int)o.W, (int)o.H);
         copy_out(f, rgba ? rgba + (size_t)v * rgba_view_stride : nullptr, rgba_pitch,
                  depth ? (float*)((uint8_t*)depth + (size_t)v * depth_view_stride) : nullptr, depth_pitch, nullptr);
     }
@@ -1032,7 +1061,7 @@ int oracle_read_normals(void* p, int32_t lat, int32_t lon, uint8_t* out) {
 int oracle_visible_peaks(void* p, uint32_t n, const float* peaks_xyz, uint8_t* visible, uint32_t* xy) {
     Oracle& o = *(Oracle*)p;
     const Frame& f = o.frame;
-    if (f.W != o.W || f.H != o.H || f.depth.empty()) { o.err = "render first"; return -1; }
+    if (f.W != o.W || f.H != o.H || f.bw != o.W || f.bh != o.H || f.depth.empty()) { o.err = "render first"; return -1; }
     /* the depth read buffer as the reference lays it out */
     const uint32_t pitch = ((o.W * 4 - 1) / 256 + 1) * 256;
     std::vector<uint8_t> buf((size_t)pitch * o.H, 0);
@@ -1125,6 +1154,7 @@ void oracle_coverage_probe(uint32_t W, uint32_t H, const float xy[6], uint32_t* 
     }
     Frame f;
     f.W = W; f.H = H;
+    f.bw = W; f.bh = H;
     f.depth.assign((size_t)W * H, 1.0f);
     f.color.assign((size_t)W * H * 4, 0);
     Uniforms u;

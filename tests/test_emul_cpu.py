@@ -306,6 +306,53 @@ def test_raster_rows_stays_in_bounds_and_matches_triangle_pixel():
     assert walked > 100
 
 
+# ---- the same lane bodies at the size limits the host accepts (tests/limits_emul.cpp) ---------------------------------
+def _limits_driver(kind):
+    """tests/limits_emul.cpp built as its own program: "opt" as host_emul.cpp is built, "ubsan" at -O0 with every undefined
+    behaviour the sanitizer knows fatal (at -O1 and above g++ folds some of the overflowing products away unchecked)."""
+    import os
+    import subprocess
+    here = os.path.dirname(os.path.abspath(__file__))
+    src = os.path.join(here, "limits_emul.cpp")
+    hdrs = [os.path.join(here, "..", "topo-renderer_amd", "csrc", f) for f in ("topo_math.h", "topo_pipeline.h")]
+    exe = os.path.join(here, "_build", "limits_emul_" + kind)
+    flags = ["-O2"] if kind == "opt" else ["-O0", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=all"]
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in [src] + hdrs):
+        subprocess.check_call(["g++", *flags, "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-o", exe, src])
+    return exe
+
+
+def _run_limits(kind, *args):
+    import subprocess
+    r = subprocess.run([_limits_driver(kind), *args], capture_output=True, text=True, timeout=300)
+    assert "runtime error" not in r.stderr, r.stderr[-2000:]
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    return {k: int(v) for k, v in (line.split() for line in r.stdout.split("\n") if line.strip())}
+
+
+@pytest.mark.parametrize("kind", ["opt", "ubsan"])
+def test_lanes_at_size_limits(kind):
+    """raster_rows, big_medium_lane and big_giant_lane on 65536 x 64, 64 x 65536, 65536 x 40000 and 46341 x 46341 targets
+    (one view of up to 2^32 - 1 px), triangles from sub-pixel to the +-2^20 px guard band at every corner and along the last
+    row and column: every fragment in the target and its window, once, with triangle_pixel's key -- and, under UBSan, no
+    signed overflow in the index arithmetic (the 32-bit `py * W` products once overflowed past 2^31 px)."""
+    st = _run_limits(kind, "1200")
+    assert st["violations"] == 0 and st["mismatches"] == 0
+    # both branches of big_giant_lane's int64 -> f32 conversion, the medium path, and k_raster's row walk all ran
+    assert st["items_narrow"] > 1000 and st["items_wide"] > 1000 and st["items_medium"] > 1000 and st["rows_tris"] > 300, st
+    # fragments at view-wide pixel indices past 2^31 and on every edge of the targets
+    assert st["frags_high"] > 10000, st
+    assert min(st["frags_last_row"], st["frags_last_col"], st["frags_first_row"], st["frags_first_col"]) > 1000, st
+
+
+@pytest.mark.parametrize("kind", ["opt", "ubsan"])
+def test_region_split_is_exact(kind):
+    """region_split_row (k_raster_rare's multiply-shift split of a triangle's regions into block rows) equals k / jw for
+    every jw <= 256 region columns and every region k < 2^17, on both sides of its n < 65536 switch."""
+    assert _run_limits(kind, "split")["split_mismatches"] == 0
+
+
 def test_split_resolve_equals_resolve_varyings(topo, orc):
     """resolve_setup + resolve_pixel (per-triangle record, then per pixel: the route k_resolve takes for waves whose pixels
     share few winners) gives the frame resolve_varyings gives, and both equal the oracle's -- uncut triangles of both

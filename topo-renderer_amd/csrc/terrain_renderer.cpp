@@ -426,10 +426,18 @@ int TerrainRenderer::set_pipeline_depth(int depth) {
     return TOPO_OK;
 }
 
+// The view count and target size every submission must keep to: the kernels store footprints and region coordinates in 16 bits
+// (FarItem, BigItem) and the view index of a work item in 16 (DESIGN.md "Size limits").  Both entry points into render_frame
+// (render_views_device, the slot path of render_panorama) check them before anything is queued.
+static const char* submission_error(uint32_t n, uint32_t w, uint32_t h) {
+    if (n > 0xFFFFu) return "too many views";
+    if (w == 0 || h == 0 || w > 65536 || h > 65536) return "bad target size";
+    return nullptr;
+}
+
 int TerrainRenderer::render_views_device(uint32_t n, const topo_uniforms* views, uint32_t w, uint32_t h, const OutputParams& out) {
     if (n == 0 || !views || !out.rgba) return fail(TOPO_ERR_INVALID, "null/empty argument");
-    if (n > 0xFFFFu) return fail(TOPO_ERR_INVALID, "too many views");
-    if (w == 0 || h == 0 || w > 65536 || h > 65536) return fail(TOPO_ERR_INVALID, "bad target size");
+    if (const char* e = submission_error(n, w, h)) return fail(TOPO_ERR_INVALID, e);
     if (int rc = bind_device()) return rc;
     if (table_dirty_)
         if (int rc = join()) return rc;
@@ -447,6 +455,8 @@ int TerrainRenderer::render_views_device(uint32_t n, const topo_uniforms* views,
 int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, const topo_uniforms* views, uint32_t w, uint32_t h,
                                   const OutputParams& out, const ResolveSlot* slots, uint32_t n_slots,
                                   const std::function<int(uint32_t, hipStream_t)>* after_slot) {
+    if (n == 0) return fail(TOPO_ERR_INVALID, "null/empty argument");
+    if (const char* e = submission_error(n, w, h)) return fail(TOPO_ERR_INVALID, e);
     const uint32_t n_tiles = (uint32_t)tiles_.size();
     const uint32_t bxc = n_tiles ? (tile_w_ - 1 + kBCX - 1) / kBCX : 0, byc = n_tiles ? (tile_h_ - 1 + kBCY - 1) / kBCY : 0;
     const size_t pixels = (size_t)n * w * h;

@@ -1268,9 +1268,9 @@ __global__ __launch_bounds__(256) void k_raster_rare(FrameParams P) {
                         for (uint32_t k = mine; k < n && base + k < P.big_cap; k += n_act) P.big[base + k] = it;
                         continue;
                     }
-                    const uint32_t magic = (1u << 24) / jw + 1u;      // k / jw = k * magic >> 24, exact while k * jw < 2^24 (jw <= 256, k < 2^16)
+                    const uint32_t magic = region_split_magic(jw);
                     for (uint32_t k = mine; k < n; k += n_act) {
-                        const uint32_t q = n < 65536u ? (uint32_t)(((uint64_t)k * magic) >> 24) : k / jw;
+                        const uint32_t q = region_split_row(k, jw, n, magic);
                         const int32_t ry = jy0 + (int32_t)q, rx = jx0 + (int32_t)(k - q * jw);
                         it.region = ((uint32_t)ry << 16) | (uint32_t)rx;
                         if (TOPO_CHK(P.counters, base + k < P.big_cap && rx >= 0 && ry >= 0 && rx * 64 < P.W && ry * 64 < P.H, 7u, base + k)) P.big[base + k] = it;

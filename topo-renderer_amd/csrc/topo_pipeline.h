@@ -244,6 +244,14 @@ TOPO_HD uint64_t vis_key(float z, uint32_t id) { return ((uint64_t)f_bits(z) << 
 #define TOPO_RCP_EST(x) (1.0f / (x))
 #endif
 
+// k_raster_rare's cooperative split of a triangle's block of n regions, jw (<= 256) region columns wide: region k lies in block
+// row k / jw.  region_split_magic(jw) turns that division into a multiply-shift, exact while k * jw < 2^24, i.e. for every k of
+// a block of fewer than 65536 regions; larger blocks divide (tests/test_emul_cpu.py::test_region_split_is_exact).
+TOPO_HD uint32_t region_split_magic(uint32_t jw) { return (1u << 24) / jw + 1u; }
+TOPO_HD uint32_t region_split_row(uint32_t k, uint32_t jw, uint32_t n, uint32_t magic) {
+    return n < 65536u ? (uint32_t)(((uint64_t)k * magic) >> 24) : k / jw;
+}
+
 // A triangle whose snapped vertices span < 2^14 sub-pixels (64 px) in x and y: every edge-function product fits int32.
 TOPO_HD bool spans_fit_int32(int32_t X0, int32_t Y0, int32_t X1, int32_t Y1, int32_t X2, int32_t Y2) {
     const int32_t mnx = X0 < X1 ? (X0 < X2 ? X0 : X2) : (X1 < X2 ? X1 : X2), mxx = X0 > X1 ? (X0 > X2 ? X0 : X2) : (X1 > X2 ? X1 : X2);
@@ -297,7 +305,7 @@ TOPO_HD void raster_rows(int32_t W, int32_t H, int32_t X0, int32_t Y0, int32_t X
                     float z = fmaf(w1, dz1, fmaf(w2, dz2, z0));
                     if (z < 1.0f) {
                         if (z < 0.0f) z = 0.0f;
-                        emit((uint32_t)(py * W + px0 + k), vis_key(z, id));
+                        emit((uint32_t)py * (uint32_t)W + (uint32_t)(px0 + k), vis_key(z, id));      // a view may hold 2^32 - 1 px
                     }
                 }
                 F0 += m0;
@@ -351,7 +359,7 @@ TOPO_HD void big_medium_lane(const int32_t X[3], const int32_t Y[3], const float
     int32_t F1 = R1 + TOPO_MUL24(A1, u) - TOPO_MUL24(B1, v0);
     int32_t F2 = R2 + TOPO_MUL24(A2, u) - TOPO_MUL24(B2, v0);
     const int32_t S0 = B0 * rows, S1 = B1 * rows, S2 = B2 * rows;
-    uint32_t pixel = (uint32_t)((py0 + v0) * W + px0 + u);
+    uint32_t pixel = (uint32_t)(py0 + v0) * (uint32_t)W + (uint32_t)(px0 + u);      // unsigned: a view may hold 2^32 - 1 px
     const uint32_t pstep = (uint32_t)(rows * W);
     const bool ucol = u < bw;
     int32_t yrow = py0 + v0;
