@@ -313,6 +313,39 @@ int topo_viewshed_reset(topo_ctx* ctx);
  * loaded, TOPO_ERR_INVALID if accumulation was never enabled. */
 int topo_viewshed_read(topo_ctx* ctx, int32_t lat_deg, int32_t lon_deg, uint8_t* mask_out, size_t pitch, uint64_t* n_visible_out);
 
+/* ---- horizon: where the terrain meets the sky in the latest submission, column by column -----------------------------------
+ * The latest submission is that of the last topo_render / topo_render_device / topo_render_views_device / topo_render_panorama (this
+ * rank's sectors) / topo_render_batch call; a batch of more than 8 viewpoints is several submissions, and only its last one stays
+ * queryable.  For every view v and column x of it the query reports the topmost terrain pixel: the smallest row whose pixel a
+ * triangle won.  Row 0 means the terrain reaches the top edge: the true horizon may lie above the view.  The tile and cell are those
+ * of the viewshed (cell (x, y) = the quad between texels (x, y) and (x+1, y+1), row 0 north); fan = the piece of a near-clipped
+ * triangle.  Errors: TOPO_ERR_INVALID when nothing was rendered yet, for views outside the submission, and once tiles were added,
+ * replaced or unloaded after it (its draw order is gone); TOPO_ERR_CAPACITY from the host read when the submission overflowed its
+ * rare-triangle queue (incomplete: see topo_join; the next topo_join does not report it again).  Multi-GPU: each rank answers for
+ * its own sectors. */
+typedef struct topo_horizon_point {      /* 32 bytes */
+    int32_t row;                         /* topmost terrain row; -1 all sky; -2 frame incomplete (device variant) */
+    float depth;                         /* depth output at (row, column); 1.0 for sky */
+    int32_t lat_deg, lon_deg;            /* tile of the winning triangle (0, 0 for sky) */
+    uint32_t cell_x, cell_y, fan;        /* the triangle: viewshed cell numbering, row 0 north */
+    uint32_t _reserved;
+} topo_horizon_point;
+#define TOPO_HORIZON_SKY (-1)
+#define TOPO_HORIZON_INCOMPLETE (-2)
+/* n_views / width / height of the latest submission (what the horizon calls read). */
+int topo_horizon_shape(topo_ctx* ctx, uint32_t* n_views, uint32_t* width, uint32_t* height);
+/* Host memory; waits for that submission.  Views [first_view, first_view + n_views), view i's `width` records at
+ * out + i * view_stride (records, >= width). */
+int topo_horizon_read(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, topo_horizon_point* out, size_t view_stride);
+/* Device memory (16-byte aligned); asynchronous: queued on the stream that submission ran on, behind it.  An incomplete frame
+ * writes row TOPO_HORIZON_INCOMPLETE into every record. */
+int topo_horizon_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, topo_horizon_point* out_dev, size_t view_stride);
+/* Host helper, f64: azimuth (degrees clockwise from true north at the eye, [0, 360)) and elevation (degrees above the plane normal
+ * to the eye's geocentric radius) of the pixel-space points (x, y) = xy[2i], xy[2i+1] of the view `view` of width x height, into
+ * az_el_out[2i], [2i+1].  The ray is obtained by inverting view->camera_proj; the eye is view->camera_pos.  With
+ * (x, y) = (column + 0.5, row + 0.5) a horizon record becomes the skyline's azimuth and elevation. */
+void topo_pixel_angles(const topo_uniforms* view, uint32_t width, uint32_t height, uint32_t n, const float* xy, double* az_el_out);
+
 /* ---- host-side helpers mirroring the reference's CPU code ---------------------------------------------- */
 
 /* Uniforms::new(&camera, bounds) with Camera{eye, yaw, pitch, fov_y, NEAR, FAR, view_mode, sun_angle{theta,phi}}:

@@ -160,6 +160,18 @@ impl TerrainRenderer {
         check(self.ctx, unsafe { sys::topo_viewshed_read(self.ctx, location.0, location.1, mask.as_mut_ptr(), cw, &mut n) })?;
         Ok((mask, n))
     }
+
+    /// Horizon (new): for every view and column of the latest submission, the topmost terrain pixel (`row` -1: all sky) with its
+    /// depth, tile and cell; waits for that submission.  Returns (n_views, width, records), view i's `width` records at
+    /// `records[i * width..]`; the buffer is sized from the submission's own shape.  Pixel-space angles:
+    /// `sys::topo_pixel_angles` with (column + 0.5, row + 0.5).
+    pub fn horizon(&mut self) -> Result<(u32, u32, Vec<sys::topo_horizon_point>), TopoError> {
+        let (mut n, mut w, mut h) = (0u32, 0u32, 0u32);
+        check(self.ctx, unsafe { sys::topo_horizon_shape(self.ctx, &mut n, &mut w, &mut h) })?;
+        let mut out = vec![sys::topo_horizon_point::default(); n as usize * w as usize];
+        check(self.ctx, unsafe { sys::topo_horizon_read(self.ctx, 0, n, out.as_mut_ptr(), w as usize) })?;
+        Ok((n, w, out))
+    }
 }
 
 impl Drop for TerrainRenderer {

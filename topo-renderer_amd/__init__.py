@@ -34,6 +34,10 @@ TIMING_NAMES = ("clear", "cull", "raster", "occlusion", "raster_big", "resolve",
 
 NEAR, FAR = 50.0, 500000.0           # data/camera.rs:6-7
 N_SECTORS = 8                        # fixed panorama sector count
+HORIZON_SKY, HORIZON_INCOMPLETE = -1, -2
+# topo_horizon_point (include/topo_hip.h), 32 bytes
+HORIZON_DTYPE = np.dtype([("row", "<i4"), ("depth", "<f4"), ("lat_deg", "<i4"), ("lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"),
+                          ("fan", "<u4"), ("_reserved", "<u4")])
 
 
 class TopoError(RuntimeError):
@@ -143,6 +147,10 @@ def lib():
             "topo_viewshed_reset": (C.c_int, [vp]),
             "topo_viewshed_read": (C.c_int, [vp, i32, i32, vp, sz, vp]),
             "topo_debug_viewshed_stats": (C.c_int, [vp, vp]),
+            "topo_horizon_shape": (C.c_int, [vp, vp, vp, vp]),
+            "topo_horizon_read": (C.c_int, [vp, u32, u32, vp, sz]),
+            "topo_horizon_device": (C.c_int, [vp, u32, u32, vp, sz]),
+            "topo_pixel_angles": (None, [vp, u32, u32, u32, vp, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -262,6 +270,18 @@ def geotiff_info(data: bytes):
     if rc != 0:
         raise TopoError(rc, "GeoTIFF container or geo tags not usable")
     return int(w.value), int(h.value), CoordinateTransform(rp, mp, sc)
+
+
+def pixel_angles(view_uniforms, width: int, height: int, xy) -> np.ndarray:
+    """topo_pixel_angles: (n, 2) f64 (azimuth degrees clockwise from true north, elevation degrees above the eye's horizontal plane)
+    of the pixel-space points xy (n, 2) of a view of width x height with these uniforms (160 bytes)."""
+    u = np.ascontiguousarray(view_uniforms).view(np.uint8)
+    if u.nbytes != 160:
+        raise ValueError("uniforms must be 160 bytes")
+    pts = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    out = np.zeros((len(pts), 2), np.float64)
+    lib().topo_pixel_angles(_p(u), width, height, len(pts), _p(pts), _p(out))
+    return out
 
 
 def post_uniforms(width, height, pixelize_n=100.0) -> np.ndarray:
@@ -614,6 +634,29 @@ class TerrainRenderer:
         out = np.zeros(3, np.uint64)
         self._check(lib().topo_debug_viewshed_stats(self._h, _p(out)))
         return {"terrain_keys": int(out[0]), "updates": int(out[1]), "atomics": int(out[2])}
+
+    # horizon: the topmost terrain pixel of every column of the latest submission (include/topo_hip.h)
+    def horizon_shape(self):
+        """(n_views, width, height) of the latest submission."""
+        n, w, h = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(lib().topo_horizon_shape(self._h, C.byref(n), C.byref(w), C.byref(h)))
+        return int(n.value), int(w.value), int(h.value)
+
+    def horizon(self, first_view: int = 0, n_views: int = None) -> np.ndarray:
+        """Views [first_view, first_view + n_views) of the latest submission as a structured array [n_views][width] of
+        HORIZON_DTYPE; waits for the submission.  Raises TopoError(CAPACITY) if it overflowed its rare-triangle queue."""
+        total, w, _ = self.horizon_shape()
+        n = total - first_view if n_views is None else n_views
+        out = np.zeros((max(n, 0), w), HORIZON_DTYPE)
+        self._check(lib().topo_horizon_read(self._h, first_view, n, _p(out) if out.size else None, w))
+        return out
+
+    def horizon_device(self, out_ptr: int, first_view: int = 0, n_views: int = None, view_stride: int = None):
+        """topo_horizon_device: records into device memory (view i at out_ptr + 32 * i * view_stride), queued behind the latest
+        submission on its stream."""
+        total, w, _ = self.horizon_shape()
+        n = total - first_view if n_views is None else n_views
+        self._check(lib().topo_horizon_device(self._h, first_view, n, C.c_void_p(out_ptr), w if view_stride is None else view_stride))
 
     def probe_div(self, kind: int, x: np.ndarray, y: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

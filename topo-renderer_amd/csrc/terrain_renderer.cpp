@@ -79,7 +79,7 @@ TerrainRenderer::~TerrainRenderer() {
         (void)hipFree(kv.second.d_pool);
         if (kv.second.d_mask) (void)hipFree(kv.second.d_mask);
     }
-    void* bufs[] = {d_tiles_, d_vs_table_, d_vs_stats_, d_views_, d_out_rgba_, d_out_depth_, d_edge_jobs_, d_corner_jobs_, d_peaks_, d_proj_, d_overlay_geo_, d_overlay_keys_};
+    void* bufs[] = {d_tiles_, d_vs_table_, d_vs_stats_, d_hz_ll_, d_hz_out_, d_hz_check_, d_views_, d_out_rgba_, d_out_depth_, d_edge_jobs_, d_corner_jobs_, d_peaks_, d_proj_, d_overlay_geo_, d_overlay_keys_};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     for (auto& c : ctx_) {
@@ -239,6 +239,7 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
     if (Tile* ex = find(lat, lon)) { old = *ex; had_old = true; tiles_.erase(geo_key(lat, lon)); }
     Tile& nt = tiles_[geo_key(lat, lon)] = t;
     table_dirty_ = true;
+    ++tile_gen_;
     if (int rc = upload_tile_table()) return rc;
     {
         const std::map<GeoKey, uint32_t> rk = ranks();
@@ -303,6 +304,7 @@ int TerrainRenderer::unload_terrain(int32_t lat, int32_t lon) {
     if (t->d_mask) (void)hipFree(t->d_mask);
     tiles_.erase(geo_key(lat, lon));
     table_dirty_ = true;
+    ++tile_gen_;
     return TOPO_OK;
 }
 
@@ -457,6 +459,7 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
                                   const std::function<int(uint32_t, hipStream_t)>* after_slot) {
     if (n == 0) return fail(TOPO_ERR_INVALID, "null/empty argument");
     if (const char* e = submission_error(n, w, h)) return fail(TOPO_ERR_INVALID, e);
+    latest_ctx_ = -1;      // (until this submission is queued whole: a failure half-way leaves nothing to query)
     const uint32_t n_tiles = (uint32_t)tiles_.size();
     const uint32_t bxc = n_tiles ? (tile_w_ - 1 + kBCX - 1) / kBCX : 0, byc = n_tiles ? (tile_h_ - 1 + kBCY - 1) / kBCY : 0;
     const size_t pixels = (size_t)n * w * h;
@@ -715,6 +718,17 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     if (!p.status_out) TOPO_HIP_TRY(hipMemcpyAsync(h_status_slot, p.counters, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     ++c.submitted;
     c.timed = true;
+    c.sub.n_views = n;
+    c.sub.W = w;
+    c.sub.H = h;
+    c.sub.n_tiles = n_tiles;
+    c.sub.tris_per_tile = p.tris_per_tile;
+    c.sub.hm1 = n_tiles ? tile_h_ - 1 : 2u;
+    c.sub.div_tris = p.div_tris;
+    c.sub.div_hm1 = p.div_hm1;
+    c.sub.counters = p.counters;
+    c.sub.tile_gen = tile_gen_;
+    latest_ctx_ = (int)(&c - ctx_);
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
 }
@@ -794,6 +808,128 @@ int TerrainRenderer::viewshed_stats(uint64_t out[3]) {
     TOPO_HIP_TRY(hipMemcpy(s.data(), d_vs_stats_, s.size() * sizeof(s[0]), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < s.size(); i += 4)
         for (int k = 0; k < 3; ++k) out[k] += s[i + k];
+    return TOPO_OK;
+}
+
+// ---- horizon ------------------------------------------------------------------------------------------------------------------
+
+static_assert(sizeof(HorizonPoint) == sizeof(topo_horizon_point) && sizeof(topo_horizon_point) == 32, "horizon record layout");
+
+int TerrainRenderer::horizon_shape(uint32_t* n_views, uint32_t* w, uint32_t* h) {
+    if (!n_views || !w || !h) return fail(TOPO_ERR_INVALID, "null argument");
+    if (latest_ctx_ < 0) return fail(TOPO_ERR_INVALID, "no submission to query");
+    const FrameCtx::Submission& s = ctx_[latest_ctx_].sub;
+    *n_views = s.n_views;
+    *w = s.W;
+    *h = s.H;
+    return TOPO_OK;
+}
+
+// The latest submission, if views [first, first + n) of it can be answered: its context and the stream it was queued on (the one a
+// query is queued on, behind it).  Tiles added, replaced or unloaded since have taken its draw order with them.
+int TerrainRenderer::horizon_prepare(uint32_t first, uint32_t n, size_t view_stride, FrameCtx** out_c, hipStream_t* out_s) {
+    if (latest_ctx_ < 0) return fail(TOPO_ERR_INVALID, "no submission to query");
+    FrameCtx& c = ctx_[latest_ctx_];
+    if (c.sub.tile_gen != tile_gen_) return fail(TOPO_ERR_INVALID, "tiles were added or unloaded since the latest submission: its draw order is gone");
+    if (n == 0 || first >= c.sub.n_views || n > c.sub.n_views - first) return fail(TOPO_ERR_INVALID, "views outside the latest submission");
+    if (view_stride < c.sub.W) return fail(TOPO_ERR_INVALID, "view stride smaller than a view's width");
+    if (int rc = bind_device()) return rc;
+    *out_c = &c;
+    *out_s = c.last_stream ? c.last_stream : stream_;      // (null: a wait covered it and the stream may be gone; the frame is done)
+    return TOPO_OK;
+}
+
+// k_horizon over views [first, first + n) of c's latest submission into `out` (device), on s.  The rank -> (lat, lon) table is the
+// current tile order, which horizon_prepare has checked to be the submission's; it is rebuilt after the tile set changed, once every
+// earlier query has finished (add_terrain / unload_terrain join the frames, and a query on a context's own stream marks it pending).
+int TerrainRenderer::horizon_launch(FrameCtx& c, uint32_t first, uint32_t n, HorizonPoint* out, size_t view_stride, hipStream_t s) {
+    if (hz_ll_gen_ != tile_gen_) {
+        if (int rc = join()) return rc;
+        TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+        hz_ll_.clear();
+        for (const auto& kv : tiles_) {      // draw order
+            hz_ll_.push_back(kv.second.lat);
+            hz_ll_.push_back(kv.second.lon);
+        }
+        if (int rc = ensure(&d_hz_ll_, &cap_hz_ll_, (hz_ll_.size() + 2) * sizeof(int32_t))) return rc;
+        if (!hz_ll_.empty()) TOPO_HIP_TRY(hipMemcpyAsync(d_hz_ll_, hz_ll_.data(), hz_ll_.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        hz_ll_gen_ = tile_gen_;
+    }
+#ifdef TOPO_BOUNDS_CHECK
+    if (!d_hz_check_) {
+        TOPO_HIP_TRY(hipMalloc((void**)&d_hz_check_, 16 * sizeof(uint32_t)));
+        TOPO_HIP_TRY(hipMemsetAsync(d_hz_check_, 0, 16 * sizeof(uint32_t), s));
+    }
+#endif
+    HorizonParams p{};
+    p.vis = (const uint64_t*)c.d_vis;
+    p.dirty = (const uint8_t*)c.d_dirty;
+    p.counters = c.sub.counters;
+    p.check = d_hz_check_;
+    p.tile_ll = (const int32_t*)d_hz_ll_;
+    p.out = out;
+    p.view_stride = view_stride;
+    p.n_keys = (size_t)c.sub.n_views * c.sub.W * c.sub.H;
+    p.first_view = first;
+    p.n_views = n;
+    p.W = c.sub.W;
+    p.H = c.sub.H;
+    p.n_tiles = c.sub.n_tiles;
+    p.tris_per_tile = c.sub.tris_per_tile;
+    p.hm1 = c.sub.hm1;
+    p.div_tris = c.sub.div_tris;
+    p.div_hm1 = c.sub.div_hm1;
+    launch_horizon(p, s);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// The bounds-checking build: what k_horizon recorded, into the status topo_frame_status reports (the queries have finished).
+int TerrainRenderer::horizon_fold_check() {
+#ifdef TOPO_BOUNDS_CHECK
+    if (!d_hz_check_) return TOPO_OK;
+    uint32_t w[16];
+    TOPO_HIP_TRY(hipMemcpy(w, d_hz_check_, sizeof w, hipMemcpyDeviceToHost));
+    if (w[2] & kStatusBounds) {
+        last_status_[0] |= kStatusBounds;
+        last_status_[1] = w[8]; last_status_[2] = w[9]; last_status_[3] = w[10];
+        TOPO_HIP_TRY(hipMemset(d_hz_check_, 0, sizeof w));
+    }
+#endif
+    return TOPO_OK;
+}
+
+// Host read: waits for the submission and the query.  The submission's status is folded as topo_render folds its own frame: the
+// frames of its context in front of it go to the next topo_join (their overflow stays pending there), and its own overflow is this
+// call's error -- the horizon of an incomplete frame -- and is not reported again by the next topo_join.
+int TerrainRenderer::horizon_read(uint32_t first, uint32_t n, topo_horizon_point* out, size_t view_stride) {
+    if (!out) return fail(TOPO_ERR_INVALID, "null argument");
+    FrameCtx* c = nullptr;
+    hipStream_t s = nullptr;
+    if (int rc = horizon_prepare(first, n, view_stride, &c, &s)) return rc;
+    const size_t row = (size_t)c->sub.W * sizeof(HorizonPoint);
+    if (int rc = ensure_on(s, &d_hz_out_, &cap_hz_out_, row * n)) return rc;
+    if (int rc = horizon_launch(*c, first, n, (HorizonPoint*)d_hz_out_, c->sub.W, s)) return rc;
+    TOPO_HIP_TRY(hipMemcpy2DAsync(out, view_stride * sizeof(topo_horizon_point), d_hz_out_, row, row, n, hipMemcpyDeviceToHost, s));
+    TOPO_HIP_TRY(hipStreamSynchronize(s));      // (the stream of the context's latest frame: all its frames are done)
+    c->pending = false;
+    overflow_pending_ |= fold_frames(*c, c->submitted - 1);
+    (void)fold_frames(*c);
+    if (int rc = horizon_fold_check()) return rc;
+    if (c->h_status[((c->submitted - 1) % kStatusRing) * 16 + 2] & kStatusRareOverflow)
+        return fail(TOPO_ERR_CAPACITY, "rare-triangle queue overflowed: the latest submission is incomplete, and so is its horizon");
+    return TOPO_OK;
+}
+
+// Device variant: queued behind the submission on its stream; an incomplete frame writes row TOPO_HORIZON_INCOMPLETE.
+int TerrainRenderer::horizon_device(uint32_t first, uint32_t n, topo_horizon_point* out_dev, size_t view_stride) {
+    if (!out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "out_dev must be 16-byte aligned");
+    FrameCtx* c = nullptr;
+    hipStream_t s = nullptr;
+    if (int rc = horizon_prepare(first, n, view_stride, &c, &s)) return rc;
+    if (int rc = horizon_launch(*c, first, n, (HorizonPoint*)out_dev, view_stride, s)) return rc;
+    if (s != stream_) c->pending = true;      // a context's own stream: the next join (and whatever rewrites the frame) waits for the query too
     return TOPO_OK;
 }
 
@@ -1083,6 +1219,7 @@ int TerrainRenderer::frame_status(uint32_t out[4]) {
     // of the next call that waits for frames)
     for (auto& fc : ctx_)
         if (!fc.pending && fc.h_status) overflow_pending_ |= fold_frames(fc);
+    if (int rc = horizon_fold_check()) return rc;
     for (int i = 0; i < 4; ++i) out[i] = last_status_[i];
     last_status_[0] = last_status_[1] = last_status_[2] = last_status_[3] = 0;
     return TOPO_OK;
@@ -1395,6 +1532,57 @@ void geometry_transform(float h, float lon_deg, float lat_deg, float out[3]) {
     out[0] = r * cosf(lat) * cosf(lon);
     out[1] = r * cosf(lat) * sinf(lon);
     out[2] = r * sinf(lat);
+}
+
+// topo_pixel_angles, in f64: the ray through pixel-space point (x, y) is the line between the points the inverse of camera_proj maps
+// it to on the near (NDC z 0) and the far (z 1) plane -- no f32 eye enters the direction -- seen in the local east / north / up
+// frame at the eye (up = the eye's geocentric radius; geometry_transform's axes: x to (0 N, 0 E), z to the north pole).
+void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n, const float* xy, double* az_el) {
+    const float* f = view->camera_proj;      // column-major: element (row r, column c) at f[4 c + r]
+    double m[4][4], inv[4][8];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) m[r][c] = f[4 * c + r];
+    for (int r = 0; r < 4; ++r)      // Gauss-Jordan with partial pivoting on [m | I]
+        for (int c = 0; c < 8; ++c) inv[r][c] = c < 4 ? m[r][c] : (c - 4 == r ? 1.0 : 0.0);
+    for (int c = 0; c < 4; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 4; ++r)
+            if (std::fabs(inv[r][c]) > std::fabs(inv[piv][c])) piv = r;
+        for (int k = 0; k < 8; ++k) std::swap(inv[c][k], inv[piv][k]);
+        const double d = inv[c][c];
+        for (int k = 0; k < 8; ++k) inv[c][k] /= d;
+        for (int r = 0; r < 4; ++r)
+            if (r != c) {
+                const double s = inv[r][c];
+                for (int k = 0; k < 8; ++k) inv[r][k] -= s * inv[c][k];
+            }
+    }
+    auto unproject = [&](double nx, double ny, double nz, double out[3]) {
+        double p[4];
+        for (int r = 0; r < 4; ++r) p[r] = inv[r][4] * nx + inv[r][5] * ny + inv[r][6] * nz + inv[r][7];
+        for (int k = 0; k < 3; ++k) out[k] = p[k] / p[3];
+    };
+    const double ex = view->camera_pos[0], ey = view->camera_pos[1], ez = view->camera_pos[2];
+    const double el = std::sqrt(ex * ex + ey * ey + ez * ez);
+    const double up[3] = {ex / el, ey / el, ez / el};
+    const double eh = std::hypot(up[0], up[1]);
+    const double east[3] = {eh > 0.0 ? -up[1] / eh : 0.0, eh > 0.0 ? up[0] / eh : 1.0, 0.0};      // z x up (at a pole: +y)
+    const double north[3] = {up[1] * east[2] - up[2] * east[1], up[2] * east[0] - up[0] * east[2], up[0] * east[1] - up[1] * east[0]};
+    const double kDeg = 180.0 / 3.14159265358979323846;
+    for (uint32_t i = 0; i < n; ++i) {
+        const double nx = 2.0 * xy[2 * i] / w - 1.0, ny = 1.0 - 2.0 * xy[2 * i + 1] / h;
+        double p0[3], p1[3];
+        unproject(nx, ny, 0.0, p0);
+        unproject(nx, ny, 1.0, p1);
+        const double d[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+        const double de = d[0] * east[0] + d[1] * east[1] + d[2] * east[2];
+        const double dn = d[0] * north[0] + d[1] * north[1] + d[2] * north[2];
+        const double du = d[0] * up[0] + d[1] * up[1] + d[2] * up[2];
+        double az = std::atan2(de, dn) * kDeg;
+        if (az < 0.0) az += 360.0;
+        az_el[2 * i] = az;
+        az_el[2 * i + 1] = std::atan2(du, std::hypot(de, dn)) * kDeg;
+    }
 }
 
 // Uniforms::new (render/data.rs:44-58) over Camera::{up,direction,get_view,build_view_proj_matrix}

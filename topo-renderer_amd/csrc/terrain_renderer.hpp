@@ -103,6 +103,11 @@ class TerrainRenderer {
     int viewshed_read(int32_t lat, int32_t lon, uint8_t* mask_out, size_t pitch, uint64_t* n_visible);
     int viewshed_stats(uint64_t out[3]);      // test hook: terrain keys, combined updates, atomics issued since the last reset
 
+    // horizon: the topmost terrain pixel of every column of the latest submission's views (topo_horizon_*)
+    int horizon_shape(uint32_t* n_views, uint32_t* w, uint32_t* h);
+    int horizon_read(uint32_t first_view, uint32_t n_views, topo_horizon_point* out, size_t view_stride);
+    int horizon_device(uint32_t first_view, uint32_t n_views, topo_horizon_point* out_dev, size_t view_stride);
+
     const char* last_error() const { return err_.c_str(); }
 
    private:
@@ -180,6 +185,13 @@ class TerrainRenderer {
         void* d_counters = nullptr; size_t cap_counters = 0;
         void* d_pre_rgba = nullptr; size_t cap_pre_rgba = 0;      // the pixelise branch: the render-target image k_post_pixelize samples,
         void* d_pre_depth = nullptr; size_t cap_pre_depth = 0;    // and a depth image when the caller wants none
+        // the context's latest submission as the horizon query reads it (its keys and marks are d_vis / d_dirty until the next one)
+        struct Submission {
+            uint32_t n_views = 0, W = 0, H = 0, n_tiles = 0, tris_per_tile = 0, hm1 = 0;
+            FastDiv div_tris{}, div_hm1{};
+            const uint32_t* counters = nullptr;     // its counter set (the sets alternate from frame to frame)
+            uint64_t tile_gen = 0;                  // tile_gen_ when it was rendered
+        } sub;
     };
     static constexpr int kMaxPipeline = 4;
     static constexpr uint64_t kStatusRing = 64;
@@ -230,6 +242,19 @@ class TerrainRenderer {
     bool vs_on_ = false, vs_ever_ = false;
     void* d_vs_table_ = nullptr; size_t cap_vs_table_ = 0;      // rank -> the tile's mask, rebuilt with the tile table
     unsigned long long* d_vs_stats_ = nullptr;                   // kViewshedStatSlots x 4 counters of k_viewshed
+    // horizon: the frame context of the latest submission (-1: none, or one that failed half-way), and the tile set's generation
+    // (add_terrain / unload_terrain bump it: a submission rendered with another tile order can no longer be decoded).  The rank ->
+    // (lat, lon) table and the host read's device buffer are made by the first query.
+    int latest_ctx_ = -1;
+    uint64_t tile_gen_ = 0;
+    std::vector<int32_t> hz_ll_;                                 // the table's host copy (the source of its upload)
+    uint64_t hz_ll_gen_ = ~0ull;
+    void* d_hz_ll_ = nullptr;    size_t cap_hz_ll_ = 0;
+    void* d_hz_out_ = nullptr;   size_t cap_hz_out_ = 0;
+    uint32_t* d_hz_check_ = nullptr;      // TOPO_BOUNDS_CHECK build: k_horizon's bounds record, folded into topo_frame_status
+    int horizon_prepare(uint32_t first_view, uint32_t n_views, size_t view_stride, FrameCtx** c, hipStream_t* s);
+    int horizon_launch(FrameCtx& c, uint32_t first_view, uint32_t n_views, HorizonPoint* out, size_t view_stride, hipStream_t s);
+    int horizon_fold_check();
 
     std::string err_;
 };
@@ -246,6 +271,7 @@ void comm_destroy(Comm* c);
 void panorama_sector_range(int rank, int world, uint32_t* first, uint32_t* count);
 uint32_t panorama_slots(int world, uint32_t sector_w, uint32_t sector_h, topo_panorama_slot* out, uint32_t cap);
 void geometry_transform(float h, float lon_deg, float lat_deg, float out[3]);
+void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n, const float* xy, double* az_el);
 void terrain_rotation(float model_lon_deg, float model_lat_deg, float rot3x3_colmajor[9]);
 uint32_t locations_range(float latitude, float longitude, float range_dist, int32_t* out_lat_lon, uint32_t cap);
 void change_location_plan(float latitude, float longitude, float range_dist, const int32_t* loaded, uint32_t n_loaded,

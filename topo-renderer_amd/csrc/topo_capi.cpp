@@ -352,6 +352,26 @@ int topo_debug_viewshed_stats(topo_ctx* ctx, uint64_t out[3]) {
     TOPO_CALL(ctx->r->viewshed_stats(out));
 }
 
+int topo_horizon_shape(topo_ctx* ctx, uint32_t* n_views, uint32_t* width, uint32_t* height) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->horizon_shape(n_views, width, height));
+}
+
+int topo_horizon_read(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, topo_horizon_point* out, size_t view_stride) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->horizon_read(first_view, n_views, out, view_stride));
+}
+
+int topo_horizon_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, topo_horizon_point* out_dev, size_t view_stride) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->horizon_device(first_view, n_views, out_dev, view_stride));
+}
+
+void topo_pixel_angles(const topo_uniforms* view, uint32_t width, uint32_t height, uint32_t n, const float* xy, double* az_el_out) {
+    if (!view || !az_el_out || (n && !xy) || width == 0 || height == 0) return;
+    topo::pixel_angles(view, width, height, n, xy, az_el_out);
+}
+
 int topo_frame_status(topo_ctx* ctx, uint32_t out[4]) {
     TOPO_GUARD(ctx);
     if (!out) return TOPO_ERR_INVALID;

@@ -144,6 +144,30 @@ void launch_resolve(const FrameParams& p, const OutputParams& o, hipStream_t s, 
 constexpr uint32_t kViewshedStatSlots = 1024;
 void launch_viewshed(const FrameParams& p, uint32_t* const* masks, unsigned long long* stats, hipStream_t s);
 
+// horizon (topo_horizon_*), behind a finished submission: per queried view and column, the topmost pixel whose key names a
+// triangle, decoded to its tile and cell.  Reads the submission's keys, marks and status word; writes only `out`.
+struct HorizonPoint {      // = topo_horizon_point (32 bytes)
+    int32_t row;
+    float depth;
+    int32_t lat, lon;
+    uint32_t cell_x, cell_y, fan, reserved;
+};
+struct HorizonParams {
+    const uint64_t* vis;          // the submission's keys: n_keys = n_views * W * H
+    const uint8_t* dirty;         // its segment marks, one per 64 keys
+    const uint32_t* counters;     // its counter set (status word [2])
+    uint32_t* check;              // TOPO_BOUNDS_CHECK build: 16-word status record of the query (bounds violations); else unused
+    const int32_t* tile_ll;       // rank -> (lat, lon) of the submission's tile order, n_tiles pairs
+    HorizonPoint* out;            // view v's records at out + v * view_stride
+    size_t view_stride;           // records
+    size_t n_keys;
+    uint32_t first_view, n_views; // the views queried
+    uint32_t W, H;
+    uint32_t n_tiles, tris_per_tile, hm1;
+    FastDiv div_tris, div_hm1;
+};
+void launch_horizon(const HorizonParams& p, hipStream_t s);
+
 // overlay pass (line_shader.wgsl over the post pass's image): keys = W*H overlay keys, (re-)initialised when keys_fresh
 void launch_overlay(const OverlayVertex* verts, const uint32_t* idx, uint32_t n_tris, uint32_t n_verts, float width, int32_t W, int32_t H, uint64_t* keys,
                     bool keys_fresh, uint8_t* rgba, size_t pitch, uint32_t linear_target, uint32_t bgra, hipStream_t s);

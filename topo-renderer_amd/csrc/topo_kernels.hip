@@ -1965,6 +1965,99 @@ __global__ __launch_bounds__(256) void k_viewshed(FrameParams P, uint32_t* const
     }
 }
 
+// One horizon record, as two 16-byte vector stores.
+__device__ __forceinline__ void horizon_store(HorizonPoint* dst, int32_t row, uint32_t depth_bits, int32_t lat, int32_t lon, uint32_t cx, uint32_t cy,
+                                              uint32_t fan) {
+    int4* d = reinterpret_cast<int4*>(dst);
+    d[0] = make_int4(row, (int32_t)depth_bits, lat, lon);
+    d[1] = make_int4((int32_t)cx, (int32_t)cy, (int32_t)fan, 0);
+}
+
+// Horizon (topo_horizon_*): for every column of every queried view of a finished submission, the topmost pixel whose key names a
+// triangle (the smallest row whose low word is not kNoTri), and what it shows: the key's depth, the tile (rank -> (lat, lon) in the
+// submission's tile order) and the cell (draw = rank * tris_per_tile + tri, cell = tri >> 1 = x (h-1) + y, as k_viewshed decodes it).
+// Launched by the query on the submission's stream, behind it; it reads the keys, the marks and the status word and writes only
+// `out` (the next k_clear trusts the marks).  A frame whose rare-triangle queue overflowed is incomplete: every record reads row -2.
+// One wave per (view, 64-column group), a lane per column; no column is walked row by row from the top.  A step takes the marks of
+// kWin x 64 rows at once (lane l: row y0 + 64 j + l, both segments the group's <= 64 keys of that row can touch) and ballots them into
+// row masks: an unmarked segment holds only kVisClear, so a row without a mark is sky for the whole group.  The marked rows then go
+// in ascending order, kBatch at a time with their key loads in flight together, until every lane has found terrain or the rows run
+// out.  Linear indices are 64-bit: a submission holds up to 2^32 - 1 keys.
+__global__ __launch_bounds__(256) void k_horizon(HorizonParams P) {
+    constexpr int kWin = 4, kBatch = 8;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t groups = (P.W + 63) >> 6;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave >= (uint64_t)groups * P.n_views) return;      // (whole waves)
+    const uint32_t v = (uint32_t)(wave / groups), x0 = (uint32_t)(wave - (uint64_t)v * groups) * 64;
+    const uint32_t ncols = P.W - x0 < 64u ? P.W - x0 : 64u;
+    const bool valid = lane < ncols;
+    HorizonPoint* const dst = P.out + (size_t)v * P.view_stride + x0 + lane;
+    if (P.counters[2] & kStatusRareOverflow) {
+        if (valid) horizon_store(dst, -2, 0u, 0, 0, 0u, 0u, 0u);
+        return;
+    }
+    const size_t vbase = (size_t)(P.first_view + v) * P.W * P.H + x0;      // the key of (row 0, column x0) of the view
+    [[maybe_unused]] const size_t nseg = (P.n_keys + 63) >> 6;      // (the check build's bound)
+    const uint64_t* const col = P.vis + vbase + lane;
+    uint64_t key = kVisClear;
+    int32_t row = -1;
+    bool searching = valid;
+    for (uint32_t y0 = 0; y0 < P.H && __ballot(searching); y0 += 64 * kWin) {
+        uint64_t rows[kWin];
+#pragma unroll
+        for (int j = 0; j < kWin; ++j) {
+            const uint32_t y = y0 + 64 * j + lane;
+            bool m = false;
+            if (y < P.H) {
+                const size_t a = vbase + (size_t)y * P.W, sa = a >> 6, sb = (a + ncols - 1) >> 6;
+                if (TOPO_CHK(P.check, sb < nseg, 17u, sb)) m = (P.dirty[sa] | P.dirty[sb]) != 0;
+            }
+            rows[j] = __ballot(m);
+        }
+#pragma unroll
+        for (int j = 0; j < kWin; ++j) {
+            uint64_t todo = rows[j];
+            while (todo && __ballot(searching)) {
+                uint32_t r[kBatch];
+                uint64_t k[kBatch];
+#pragma unroll
+                for (int b = 0; b < kBatch; ++b) {
+                    r[b] = todo ? y0 + 64 * j + (uint32_t)__builtin_ctzll(todo) : P.H;      // (P.H: no row left)
+                    todo &= todo - 1;
+                }
+#pragma unroll
+                for (int b = 0; b < kBatch; ++b) {
+                    const size_t at = (size_t)r[b] * P.W;
+                    k[b] = searching && r[b] < P.H && TOPO_CHK(P.check, vbase + lane + at < P.n_keys, 17u, vbase + lane + at) ? col[at] : kVisClear;
+                }
+#pragma unroll
+                for (int b = 0; b < kBatch; ++b)
+                    if (searching && (uint32_t)k[b] != kNoTri) {      // (rows ascend within the batch: the first hit is the topmost)
+                        key = k[b];
+                        row = (int32_t)r[b];
+                        searching = false;
+                    }
+            }
+        }
+    }
+    if (!valid) return;
+    if (row < 0) {
+        horizon_store(dst, -1, (uint32_t)(kVisClear >> 32), 0, 0, 0u, 0u, 0u);      // sky: depth 1.0
+        return;
+    }
+    const uint32_t id = (uint32_t)key, draw = id >> 1;
+    const uint32_t rank = fastdiv(draw, P.div_tris), cell = (draw - rank * P.tris_per_tile) >> 1;
+    const uint32_t cx = fastdiv(cell, P.div_hm1), cy = cell - cx * P.hm1;
+    int32_t lat = 0, lon = 0;
+    // (the rank is tested in the product build too: what it indexes is a table)
+    if (TOPO_CHK(P.check, rank < P.n_tiles, 17u, id) && rank < P.n_tiles) {
+        lat = P.tile_ll[2 * (size_t)rank];
+        lon = P.tile_ll[2 * (size_t)rank + 1];
+    }
+    horizon_store(dst, row, (uint32_t)(key >> 32), lat, lon, cx, cy, id & 1u);
+}
+
 // The post pass with the pixelise branch on (postprocessing_shader.wgsl:70-74; never in the reference, which pins pixelize_n to
 // 100): the colour is a sample of the render target AWAY from the pixel's own texel, so the frame takes two passes -- k_resolve
 // stores the render-target texels (post_off), this kernel samples them (sample_pixelized), takes the contour from the depth
@@ -2415,6 +2508,12 @@ void launch_viewshed(const FrameParams& p, uint32_t* const* masks, unsigned long
     const size_t groups = (((size_t)p.n_views * p.W * p.H + 63) / 64 + 63) / 64;      // 64 segments of 64 keys per wave and step
     const unsigned grid = (unsigned)((groups + 3) / 4 < kViewshedStatSlots ? (groups + 3) / 4 : kViewshedStatSlots);
     hipLaunchKernelGGL(k_viewshed, dim3(grid), dim3(256), 0, s, p, masks, stats);
+}
+
+void launch_horizon(const HorizonParams& p, hipStream_t s) {
+    const uint64_t waves = (uint64_t)((p.W + 63) / 64) * p.n_views;      // one per (view, 64-column group)
+    if (waves == 0) return;
+    hipLaunchKernelGGL(k_horizon, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p);
 }
 
 void launch_overlay(const OverlayVertex* verts, const uint32_t* idx, uint32_t n_tris, uint32_t n_verts, float width, int32_t W, int32_t H, uint64_t* keys,
