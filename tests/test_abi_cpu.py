@@ -266,3 +266,11 @@ def test_missing_rccl_is_an_error_not_a_crash(topo):
     assert len(lines) == 3 and lines[2] == "WORLD1 1", lines
     for l in lines[:2]:
         assert l.startswith(f"ERR {topo.TOPO_ERR_HIP} ") and "librccl.so not found" in l and len(l) > 40, l
+
+
+def test_host_math_builds_without_hip(topo):
+    """The reference's CPU math (camera, ranges, synthetic tiles) is one translation unit that needs no HIP header: g++ alone,
+    with include/ as its only include path, accepts it."""
+    root = os.path.dirname(os.path.dirname(topo.HEADER_PATH))
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I", "include", "topo-renderer_amd/csrc/host_math.cpp"], cwd=root, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr

@@ -1,0 +1,25 @@
+// host_math.hpp -- host-side restatements of the reference's CPU math (glam 0.31) and the other pure functions behind the
+// C ABI: no HIP, so host_math.cpp builds with any C++17 compiler.
+#pragma once
+
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+#include "../../include/topo_hip.h"
+
+namespace topo {
+
+void camera_uniforms(const float eye[3], float yaw, float pitch, float fov_y, float width, float height,
+                     float sun_theta_deg, float sun_phi_deg, int32_t view_mode, topo_uniforms* out);
+void panorama_uniforms(const float eye[3], float yaw0, float pitch, uint32_t sector_w, uint32_t sector_h, float sun_theta_deg, float sun_phi_deg,
+                       int32_t view_mode, uint32_t n_sectors, topo_uniforms* out);
+void geometry_transform(float h, float lon_deg, float lat_deg, float out[3]);
+void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n, const float* xy, double* az_el);
+void terrain_rotation(float model_lon_deg, float model_lat_deg, float rot3x3_colmajor[9]);
+uint32_t locations_range(float latitude, float longitude, float range_dist, int32_t* out_lat_lon, uint32_t cap);
+void change_location_plan(float latitude, float longitude, float range_dist, const int32_t* loaded, uint32_t n_loaded,
+                          std::vector<std::pair<int32_t, int32_t>>& unload, std::vector<std::pair<int32_t, int32_t>>& request);
+void synth_tile(int32_t lat, int32_t lon, uint32_t w, uint32_t h, uint32_t seed, float* out);
+
+}  // namespace topo

@@ -23,12 +23,6 @@
 
 namespace topo {
 
-#define TOPO_HIP_TRY(expr)                                   \
-    do {                                                     \
-        hipError_t e_ = (expr);                              \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr);    \
-    } while (0)
-
 namespace {
 
 struct RcclApi {
@@ -249,13 +243,8 @@ int TerrainRenderer::render_panorama(Comm* comm, const float eye[3], float yaw0,
     topo_uniforms views[kPanoramaSectors];
     panorama_uniforms(eye, yaw0, pitch, sector_w, sector_h, sun_theta_deg, sun_phi_deg, view_mode, kPanoramaSectors, views);
     const size_t sector_px = (size_t)sector_w * sector_h;
-    OutputParams o{};
-    o.rgba = strip_dev + (size_t)first * sector_px * 4;
-    o.rgba_view_stride = sector_px * 4;
-    o.rgba_pitch = (size_t)sector_w * 4;
-    o.depth = depth_dev ? depth_dev + (size_t)first * sector_px : nullptr;
-    o.depth_view_stride = sector_px * 4;
-    o.depth_pitch = (size_t)sector_w * 4;
+    const size_t row = (size_t)sector_w * 4;
+    const OutputParams o = image_output(strip_dev + (size_t)first * sector_px * 4, row, depth_dev ? depth_dev + (size_t)first * sector_px : nullptr, row, sector_h);
     // (TOPO_PANORAMA_FORCE_SLOTS: the slot-by-slot resolve without an exchange, so that a one-GPU box can test it)
     const bool force_slots = world == 1 && getenv("TOPO_PANORAMA_FORCE_SLOTS") != nullptr;
     if (world == 1 && !force_slots) return render_views_device(count, views + first, sector_w, sector_h, o);      // nothing to ship: the ordinary path, frames in flight and all
@@ -333,13 +322,8 @@ int TerrainRenderer::render_batch(uint32_t n_viewpoints, const float* eyes, cons
         for (uint32_t v = 0; v < nv; ++v)
             panorama_uniforms(eyes + 3 * (v0 + v), yaw0s[v0 + v], pitch, sector_w, sector_h, sun_theta_phi_deg[2 * (v0 + v)],
                               sun_theta_phi_deg[2 * (v0 + v) + 1], view_mode, kPanoramaSectors, views.data() + (size_t)v * kPanoramaSectors);
-        OutputParams o{};
-        o.rgba = rgba_dev + (size_t)v0 * kPanoramaSectors * sector_px * 4;
-        o.rgba_view_stride = sector_px * 4;
-        o.rgba_pitch = (size_t)sector_w * 4;
-        o.depth = depth_dev ? depth_dev + (size_t)v0 * kPanoramaSectors * sector_px : nullptr;
-        o.depth_view_stride = sector_px * 4;
-        o.depth_pitch = (size_t)sector_w * 4;
+        const size_t row = (size_t)sector_w * 4, at = (size_t)v0 * kPanoramaSectors * sector_px;
+        const OutputParams o = image_output(rgba_dev + at * 4, row, depth_dev ? depth_dev + at : nullptr, row, sector_h);
         if (int rc = render_views_device(nv * kPanoramaSectors, views.data(), sector_w, sector_h, o)) return rc;
     }
     return TOPO_OK;

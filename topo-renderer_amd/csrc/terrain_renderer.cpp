@@ -12,11 +12,25 @@
 
 namespace topo {
 
-#define TOPO_HIP_TRY(expr)                                   \
-    do {                                                     \
-        hipError_t e_ = (expr);                              \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr);    \
-    } while (0)
+namespace {
+
+// The experiment switches of the submission path (tools/README.md, in its table's order), read once per process.
+struct Switches {
+    static int env(const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; }
+    const bool views_by_copy = env("TOPO_VIEWS_BY_COPY", 0) != 0;
+    const bool views_in_cull = env("TOPO_VIEWS_IN_CULL", 1) != 0;
+    const bool status_by_copy = env("TOPO_STATUS_BY_COPY", 0) != 0;
+    const bool far_skip = env("TOPO_FAR_SKIP", 1) != 0;
+    const bool events_by_marker = env("TOPO_EVENTS_BY_MARKER", 0) != 0;
+    const bool fuse_clear_cull = env("TOPO_FUSE_CLEAR_CULL", 1) != 0;
+    const int near_strip = env("TOPO_NEAR_STRIP", 0);      // 1..15; anything else: the default
+};
+const Switches& switches() { static const Switches s; return s; }
+
+bool is_linear(uint32_t format) { return format == TOPO_FORMAT_RGBA8_UNORM || format == TOPO_FORMAT_BGRA8_UNORM; }
+bool is_bgra(uint32_t format) { return format == TOPO_FORMAT_BGRA8_UNORM_SRGB || format == TOPO_FORMAT_BGRA8_UNORM; }
+
+}  // namespace
 
 int TerrainRenderer::fail(int code, const std::string& msg) {
     err_ = msg;
@@ -75,17 +89,8 @@ TerrainRenderer::~TerrainRenderer() {
     if (stream_) (void)hipStreamSynchronize(stream_);
     for (auto& c : ctx_)
         if (c.stream) (void)hipStreamSynchronize(c.stream);
-    for (auto& kv : tiles_) {
-        (void)hipFree(kv.second.d_pool);
-        if (kv.second.d_mask) (void)hipFree(kv.second.d_mask);
-    }
-    void* bufs[] = {d_tiles_, d_vs_table_, d_vs_stats_, d_hz_ll_, d_hz_out_, d_hz_check_, d_views_, d_out_rgba_, d_out_depth_, d_edge_jobs_, d_corner_jobs_, d_peaks_, d_proj_, d_overlay_geo_, d_overlay_keys_};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
+    for (auto& kv : tiles_) free_tile(kv.second);
     for (auto& c : ctx_) {
-        void* cb[] = {c.d_vis, c.d_dirty, c.d_work, c.d_work2, c.d_far, c.d_big, c.d_rare, c.d_counters, c.d_pre_rgba, c.d_pre_depth};
-        for (void* p : cb)
-            if (p) (void)hipFree(p);
         for (auto& set : c.evr)
             for (auto& e : set)
                 if (e) (void)hipEventDestroy(e);
@@ -103,21 +108,32 @@ TerrainRenderer::~TerrainRenderer() {
         if (e) (void)hipEventDestroy(e);
     for (const auto& pin : pinned_) (void)hipHostUnregister(pin.first);
     if (own_stream_) (void)hipStreamDestroy(own_stream_);
+    // (the DeviceBuffer members go now: the device is bound and every stream has been waited for)
 }
 
-int TerrainRenderer::ensure(void** p, size_t* cap, size_t need) { return ensure_on(stream_, p, cap, need); }
-
-int TerrainRenderer::ensure_on(hipStream_t s, void** p, size_t* cap, size_t need) {
-    if (need <= *cap) return TOPO_OK;
-    if (*p) {
+int TerrainRenderer::ensure(hipStream_t s, DeviceBuffer& b, size_t need) {
+    if (need <= b.cap) return TOPO_OK;
+    if (b.p) {
         TOPO_HIP_TRY(hipStreamSynchronize(s));
-        TOPO_HIP_TRY(hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
+        TOPO_HIP_TRY(hipFree(b.p));
+        b.p = nullptr;
+        b.cap = 0;
     }
-    TOPO_HIP_TRY(hipMalloc(p, need));
-    *cap = need;
+    TOPO_HIP_TRY(hipMalloc(&b.p, need));
+    b.cap = need;
     return TOPO_OK;
+}
+
+int TerrainRenderer::wait_all() {
+    if (int rc = join()) return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    return TOPO_OK;
+}
+
+void TerrainRenderer::free_tile(Tile& t) {
+    (void)hipFree(t.d_pool);
+    if (t.d_mask) (void)hipFree(t.d_mask);
+    t.d_pool = t.d_mask = nullptr;
 }
 
 Tile* TerrainRenderer::find(int lat, int lon) {
@@ -156,18 +172,18 @@ void TerrainRenderer::collect_jobs(const Tile& nt, const std::map<GeoKey, uint32
 // launch per kind covers any number of jobs).
 int TerrainRenderer::upload_seam_jobs(const std::vector<EdgeJob>& edges, const std::vector<CornerJob>& corners) {
     if (!edges.empty()) {
-        if (int rc = ensure(&d_edge_jobs_, &cap_edge_jobs_, edges.size() * sizeof(EdgeJob))) return rc;
-        TOPO_HIP_TRY(hipMemcpyAsync(d_edge_jobs_, edges.data(), edges.size() * sizeof(EdgeJob), hipMemcpyHostToDevice, stream_));
+        if (int rc = ensure(stream_, d_edge_jobs_, edges.size() * sizeof(EdgeJob))) return rc;
+        TOPO_HIP_TRY(hipMemcpyAsync(d_edge_jobs_.p, edges.data(), edges.size() * sizeof(EdgeJob), hipMemcpyHostToDevice, stream_));
     }
     if (!corners.empty()) {
-        if (int rc = ensure(&d_corner_jobs_, &cap_corner_jobs_, corners.size() * sizeof(CornerJob))) return rc;
-        TOPO_HIP_TRY(hipMemcpyAsync(d_corner_jobs_, corners.data(), corners.size() * sizeof(CornerJob), hipMemcpyHostToDevice, stream_));
+        if (int rc = ensure(stream_, d_corner_jobs_, corners.size() * sizeof(CornerJob))) return rc;
+        TOPO_HIP_TRY(hipMemcpyAsync(d_corner_jobs_.p, corners.data(), corners.size() * sizeof(CornerJob), hipMemcpyHostToDevice, stream_));
     }
     // the job vectors are pageable host memory: hipMemcpyAsync has staged them before returning
     return TOPO_OK;
 }
 void TerrainRenderer::launch_seam_jobs(size_t n_edges, size_t n_corners) {
-    launch_normals_border((const TileDev*)d_tiles_, (const EdgeJob*)d_edge_jobs_, (uint32_t)n_edges, (const CornerJob*)d_corner_jobs_, (uint32_t)n_corners,
+    launch_normals_border(d_tiles_.as<const TileDev>(), d_edge_jobs_.as<const EdgeJob>(), (uint32_t)n_edges, d_corner_jobs_.as<const CornerJob>(), (uint32_t)n_corners,
                           tile_w_, tile_h_, stream_);
 }
 int TerrainRenderer::run_seam_jobs(const std::vector<EdgeJob>& edges, const std::vector<CornerJob>& corners) {
@@ -214,12 +230,12 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
     const hipError_t e = hipMemcpyAsync(t.d_heights, heights, texels * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_);
     // (the zero-initialised normal texture: k_normals_interior writes the untouched border ring as zero)
     if (e != hipSuccess) {
-        (void)hipFree(t.d_pool);
+        free_tile(t);
         return hip_fail(e, "tile upload");
     }
     if (vs_ever_)      // (a replaced tile's mask goes with it: the new one starts empty)
         if (int rc = alloc_mask(t)) {
-            (void)hipFree(t.d_pool);
+            free_tile(t);
             return rc;
         }
     // TerrainUniforms::new (render/data.rs:124-151)
@@ -269,8 +285,7 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
     }
     if (had_old) {
         TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-        (void)hipFree(old.d_pool);
-        if (old.d_mask) (void)hipFree(old.d_mask);
+        free_tile(old);
     }
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
@@ -281,7 +296,7 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
 // followed by the normals kernel (any size, any LDS tile size).  `mid`: recorded between the part that precedes the normals and
 // the rest (the load phase's timing bracket).
 void TerrainRenderer::launch_load_kernels(uint32_t first, uint32_t count, hipEvent_t mid) {
-    const TileDev* tiles = (const TileDev*)d_tiles_;
+    const TileDev* tiles = d_tiles_.as<const TileDev>();
     if (normals_tables_fused(tile_w_, tile_h_, lds_rows_)) {
         launch_trig_tables(tiles, first, count, tile_w_, tile_h_, stream_);
         if (mid) (void)hipEventRecord(mid, stream_);
@@ -298,10 +313,8 @@ void TerrainRenderer::launch_load_kernels(uint32_t first, uint32_t count, hipEve
 int TerrainRenderer::unload_terrain(int32_t lat, int32_t lon) {
     Tile* t = find(lat, lon);
     if (!t) return TOPO_OK;   // BTreeMap::remove of a missing key is a no-op
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-    (void)hipFree(t->d_pool);
-    if (t->d_mask) (void)hipFree(t->d_mask);
+    if (int rc = wait_all()) return rc;
+    free_tile(*t);
     tiles_.erase(geo_key(lat, lon));
     table_dirty_ = true;
     ++tile_gen_;
@@ -318,8 +331,8 @@ int TerrainRenderer::recompute_normals() {
     std::vector<EdgeJob> edges;
     std::vector<CornerJob> corners;
     for (Tile* t : order) collect_jobs(*t, rk, edges, corners);
-    if (int rc = ensure(&d_edge_jobs_, &cap_edge_jobs_, (edges.size() + 1) * sizeof(EdgeJob))) return rc;
-    if (int rc = ensure(&d_corner_jobs_, &cap_corner_jobs_, (corners.size() + 1) * sizeof(CornerJob))) return rc;
+    if (int rc = ensure(stream_, d_edge_jobs_, (edges.size() + 1) * sizeof(EdgeJob))) return rc;
+    if (int rc = ensure(stream_, d_corner_jobs_, (corners.size() + 1) * sizeof(CornerJob))) return rc;
     if (int rc = upload_seam_jobs(edges, corners)) return rc;      // (the job lists: host -> device, ahead of the kernels that are timed)
     // the whole load phase of the resident tiles, every load-time kernel inside the bracket: the tables of the frame phase
     // (ev 0 -> 2), then the normals K1-K3 (ev 2 -> 1)
@@ -352,14 +365,14 @@ int TerrainRenderer::upload_tile_table() {
     std::vector<TileDev> table;
     for (auto& kv : tiles_) table.push_back(kv.second.dev);   // std::map iterates in BTreeMap order
     if (!table.empty()) {
-        if (int rc = ensure(&d_tiles_, &cap_tiles_, table.size() * sizeof(TileDev))) return rc;
+        if (int rc = ensure(stream_, d_tiles_, table.size() * sizeof(TileDev))) return rc;
         TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-        TOPO_HIP_TRY(hipMemcpy(d_tiles_, table.data(), table.size() * sizeof(TileDev), hipMemcpyHostToDevice));
+        TOPO_HIP_TRY(hipMemcpy(d_tiles_.p, table.data(), table.size() * sizeof(TileDev), hipMemcpyHostToDevice));
         if (vs_ever_) {      // the viewshed's rank -> mask table: ranks shift whenever tiles come and go
             std::vector<uint32_t*> masks;
             for (auto& kv : tiles_) masks.push_back(kv.second.d_mask);
-            if (int rc = ensure(&d_vs_table_, &cap_vs_table_, masks.size() * sizeof(uint32_t*))) return rc;
-            TOPO_HIP_TRY(hipMemcpy(d_vs_table_, masks.data(), masks.size() * sizeof(uint32_t*), hipMemcpyHostToDevice));
+            if (int rc = ensure(stream_, d_vs_table_, masks.size() * sizeof(uint32_t*))) return rc;
+            TOPO_HIP_TRY(hipMemcpy(d_vs_table_.p, masks.data(), masks.size() * sizeof(uint32_t*), hipMemcpyHostToDevice));
         }
     }
     table_dirty_ = false;
@@ -398,29 +411,51 @@ int TerrainRenderer::join() {
 bool TerrainRenderer::fold_frames(FrameCtx& c, uint64_t end) {
     bool overflow = false;
     for (; c.checked < end; ++c.checked) {
-        const uint32_t* w = c.h_status + (c.checked % kStatusRing) * 16;
+        const uint32_t* w = c.status_words(c.checked);
         // status bits accumulate over the frames folded since the last topo_frame_status (which clears them): a burst of frames
         // cannot hide an earlier frame's overflow or bounds violation behind a clean last frame
-        last_status_[0] |= w[2];
-        if (w[2] & kStatusBounds) { last_status_[1] = w[8]; last_status_[2] = w[9]; last_status_[3] = w[10]; }
-        overflow |= (w[2] & kStatusRareOverflow) != 0;
+        last_status_[0] |= w[kCtrStatus];
+        if (w[kCtrStatus] & kStatusBounds) record_bounds(w);
+        overflow |= (w[kCtrStatus] & kStatusRareOverflow) != 0;
     }
     return overflow;
 }
 
-int TerrainRenderer::check_frames() {
-    bool overflow = overflow_pending_;
-    overflow_pending_ = false;
+// A bounds record (of a frame's counter set, or a horizon query's) into the status topo_frame_status reports.
+void TerrainRenderer::record_bounds(const uint32_t* w) {
+    last_status_[0] |= kStatusBounds;
+    last_status_[1] = w[kCtrBoundsTag]; last_status_[2] = w[kCtrBoundsLo]; last_status_[3] = w[kCtrBoundsHi];
+}
+
+bool TerrainRenderer::fold_idle() {
+    bool overflow = false;
     for (auto& c : ctx_)
         if (!c.pending && c.h_status) overflow |= fold_frames(c);
+    return overflow;
+}
+
+// For the calls that answer for the latest frame of c themselves (topo_render, topo_horizon_read), after waiting for it.  The frames
+// of c in front of it go to the next topo_join: their overflow stays pending.  Its own status bits reach topo_frame_status, and
+// whether it overflowed is returned -- the caller's error, not pending, not reported again by the next topo_join.  `retry`: the
+// caller throws an overflowed frame away and renders it again, so its status describes no frame anyone gets and is skipped.
+bool TerrainRenderer::fold_latest(FrameCtx& c, bool retry) {
+    overflow_pending_ |= fold_frames(c, c.submitted - 1);
+    const bool overflow = (c.latest_status()[kCtrStatus] & kStatusRareOverflow) != 0;
+    if (overflow && retry) ++c.checked;
+    else (void)fold_frames(c);
+    return overflow;
+}
+
+int TerrainRenderer::check_frames() {
+    const bool overflow = fold_idle() | overflow_pending_;
+    overflow_pending_ = false;
     if (overflow) return fail(TOPO_ERR_CAPACITY, "rare-triangle queue overflowed: a frame is incomplete (raise the queue capacity or render fewer views per submission)");
     return TOPO_OK;
 }
 
 int TerrainRenderer::set_pipeline_depth(int depth) {
     if (depth < 1 || depth > kMaxPipeline) return fail(TOPO_ERR_INVALID, "pipeline depth must be 1..4");
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (int rc = wait_all()) return rc;
     for (int i = 0; i < depth; ++i)
         if (int rc = init_ctx(ctx_[i], depth > 1)) return rc;
     pipeline_depth_ = depth;
@@ -454,64 +489,120 @@ int TerrainRenderer::render_views_device(uint32_t n, const topo_uniforms* views,
     return render_frame(c, c.stream, n, views, w, h, out);
 }
 
+// Is the far phase worth its four launches (each ~4 us of GPU and ~9 us of host time)?  k_cull makes an occlusion-test
+// candidate of a block whose nearest possible view depth, w(centre) - radius |w row|, exceeds the split;
+// w(centre) <= w(C) + R |w row| for the sphere (C, R) around the tile's block centres (Tile::centres).  The split is a
+// performance knob with a flat optimum (60..120 km at c4; results do not depend on it): when that bound stays below 4/3 of
+// it for every view and tile -- a lone tile around the viewpoint -- the frame's split (*split_m) is raised above the bound, no
+// block becomes a candidate and the far phase need not be launched (true).  A function of its arguments alone: no HIP, no state.
+static bool far_phase_empty(const topo_uniforms* views, uint32_t n, const std::map<GeoKey, Tile>& tiles, float* split_m) {
+    double bound = 0.0;
+    for (uint32_t i = 0; i < n && bound >= 0.0; ++i) {
+        const float* m = views[i].camera_proj;
+        const double wn = std::sqrt((double)m[3] * m[3] + (double)m[7] * m[7] + (double)m[11] * m[11]);
+        for (const auto& kv : tiles) {
+            const double* s = kv.second.centres;
+            const double w_far = (double)m[3] * s[0] + (double)m[7] * s[1] + (double)m[11] * s[2] + (double)m[15] + s[3] * wn;
+            if (!(s[3] >= 0.0) || !(w_far < 1e30)) { bound = -1.0; break; }      // unknown sphere, NaN or huge: keep the far phase
+            bound = std::max(bound, w_far);
+        }
+    }
+    if (!(bound >= 0.0 && bound + 2.0 < (double)*split_m * (4.0 / 3.0))) return false;
+    *split_m = std::max(*split_m, (float)(bound + 2.0));      // (>= bound + 1 after the rounding to f32: no candidates)
+    return true;
+}
+
+// clear and cull in one launch: unless switched off, whenever there are tiles to cull
+static bool fused_clear_cull(const FrameParams& p) { return switches().fuse_clear_cull && p.n_tiles != 0; }
+
 int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, const topo_uniforms* views, uint32_t w, uint32_t h,
                                   const OutputParams& out, const ResolveSlot* slots, uint32_t n_slots,
                                   const std::function<int(uint32_t, hipStream_t)>* after_slot) {
     if (n == 0) return fail(TOPO_ERR_INVALID, "null/empty argument");
     if (const char* e = submission_error(n, w, h)) return fail(TOPO_ERR_INVALID, e);
     latest_ctx_ = -1;      // (until this submission is queued whole: a failure half-way leaves nothing to query)
-    const uint32_t n_tiles = (uint32_t)tiles_.size();
-    const uint32_t bxc = n_tiles ? (tile_w_ - 1 + kBCX - 1) / kBCX : 0, byc = n_tiles ? (tile_h_ - 1 + kBCY - 1) / kBCY : 0;
+    FrameParams p{};
+    if (int rc = grow_frame_buffers(c, stream, n, w, h, p)) return rc;
+    ViewPack pack{};
+    bool pack_in_cull = false;
+    if (int rc = stage_views(c, stream, views, p, pack, &pack_in_cull)) return rc;
+    fill_params(c, p);
+    last_blocks_tested_ = p.work_cap;
+    last_far_phase_ = p.split_m > 0.0f && !(switches().far_skip && far_phase_empty(views, n, tiles_, &p.split_m));
+    if (int rc = queue_frame(c, stream, p, pack_in_cull ? &pack : nullptr, last_far_phase_, out, slots, n_slots, after_slot)) return rc;
+    record_submission(c, p);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Sizes the frame's queues and lists (into p) and grows the context's buffers to them; the status ring of the context.
+int TerrainRenderer::grow_frame_buffers(FrameCtx& c, hipStream_t stream, uint32_t n, uint32_t w, uint32_t h, FrameParams& p) {
+    p.n_views = n;
+    p.n_tiles = (uint32_t)tiles_.size();
+    p.W = (int32_t)w;
+    p.H = (int32_t)h;
+    p.bx_count = p.n_tiles ? (tile_w_ - 1 + kBCX - 1) / kBCX : 0;
+    p.by_count = p.n_tiles ? (tile_h_ - 1 + kBCY - 1) / kBCY : 0;
     const size_t pixels = (size_t)n * w * h;
-    const size_t work_cap = (size_t)n * n_tiles * bxc * byc;
-    const size_t big_cap = big_cap_cfg_ ? big_cap_cfg_ : (1u << 22);
-    const size_t rare_cap = rare_cap_cfg_ ? rare_cap_cfg_ : (rare_cap_auto_ ? (size_t)rare_cap_auto_ : (1u << 22));
+    const size_t work_cap = (size_t)n * p.n_tiles * p.bx_count * p.by_count;
+    p.big_cap = big_cap_cfg_ ? big_cap_cfg_ : (1u << 22);
+    p.rare_cap = rare_cap_cfg_ ? rare_cap_cfg_ : (rare_cap_auto_ ? (uint32_t)rare_cap_auto_ : (1u << 22));
     if (work_cap >= (1ull << 30)) return fail(TOPO_ERR_CAPACITY, "too many raster blocks in one submission");
     if (pixels >= (1ull << 32)) return fail(TOPO_ERR_CAPACITY, "more than 2^32 pixels in one submission");
     const size_t vis_keys = (pixels + 63) & ~(size_t)63;   // whole 64-key segments: k_clear rewrites segments, not keys
-    if (vis_keys * 8 > c.cap_vis) {
+    if (vis_keys * 8 > c.d_vis.cap) {
         // a fresh buffer holds garbage: mark every segment so that the first k_clear initialises all of it
-        if (int rc = ensure_on(stream, &c.d_vis, &c.cap_vis, vis_keys * 8)) return rc;
-        if (int rc = ensure_on(stream, &c.d_dirty, &c.cap_dirty, vis_keys / 64 + 64)) return rc;
-        TOPO_HIP_TRY(hipMemsetAsync(c.d_dirty, 1, c.cap_dirty, stream));
+        if (int rc = ensure(stream, c.d_vis, vis_keys * 8)) return rc;
+        if (int rc = ensure(stream, c.d_dirty, vis_keys / 64 + 64)) return rc;
+        TOPO_HIP_TRY(hipMemsetAsync(c.d_dirty.p, 1, c.d_dirty.cap, stream));
     }
-    if (int rc = ensure(&d_views_, &cap_views_, sizeof(ViewDev) * kMaxViewsPerSlot * kViewSlots)) return rc;
+    if (int rc = ensure(stream_, d_views_, sizeof(ViewDev) * kMaxViewsPerSlot * kViewSlots)) return rc;
     // A near block (and a far survivor) is cut into strips of near_strip cell rows, one wave each: the raster phase is as long
     // as its longest strip, and a strip's vertex rows cost less than the pixels of its triangles.  Measured (tools/exp_strip.sh,
     // ms per frame at 1 / 2 / 4 rows): c1 0.146 / 0.148 / 0.157, c2 0.186 / 0.184 / 0.194, c3 0.382 / 0.372 / 0.390,
     // c4 0.964 / 0.933 / 0.942.  TOPO_NEAR_STRIP overrides (experiments).
-    static const int strip_env = getenv("TOPO_NEAR_STRIP") ? atoi(getenv("TOPO_NEAR_STRIP")) : 0;
-    const uint32_t near_strip = strip_env >= 1 && strip_env <= 15 ? (uint32_t)strip_env : (work_cap <= 64 * 1024 ? 1u : 2u);
-    const size_t near_cap = (size_t)((kBCY + near_strip - 1) / near_strip) * work_cap;
-    if (int rc = ensure_on(stream, &c.d_work, &c.cap_work, (near_cap ? near_cap : 1) * sizeof(WorkItem))) return rc;
-    if (int rc = ensure_on(stream, &c.d_work2, &c.cap_work2, (near_cap ? near_cap : 1) * sizeof(WorkItem))) return rc;   // far survivors, in strips too
+    const int strip_env = switches().near_strip;
+    p.near_strip = strip_env >= 1 && strip_env <= 15 ? (uint32_t)strip_env : (work_cap <= 64 * 1024 ? 1u : 2u);
+    const size_t near_cap = (size_t)((kBCY + p.near_strip - 1) / p.near_strip) * work_cap;
+    if (int rc = ensure(stream, c.d_work, (near_cap ? near_cap : 1) * sizeof(WorkItem))) return rc;
+    if (int rc = ensure(stream, c.d_work2, (near_cap ? near_cap : 1) * sizeof(WorkItem))) return rc;   // far survivors, in strips too
     // the far-candidate list: kFarLists sub-lists, cull workgroup b (256 blocks) appending to sub-list b % kFarLists
     const size_t far_sub_cap = ((work_cap + 255) / 256 + kFarLists - 1) / kFarLists * 256;
-    if (int rc = ensure_on(stream, &c.d_far, &c.cap_far, (far_sub_cap ? far_sub_cap * kFarLists : 1) * sizeof(FarItem))) return rc;
-    if (int rc = ensure_on(stream, &c.d_big, &c.cap_big, big_cap * sizeof(BigItem))) return rc;
-    if (int rc = ensure_on(stream, &c.d_rare, &c.cap_rare, rare_cap * sizeof(RareItem))) return rc;
-    if (!c.d_counters) {
-        if (int rc = ensure_on(stream, &c.d_counters, &c.cap_counters, 2 * kCounterWords * sizeof(uint32_t))) return rc;      // two sets, alternating
-        TOPO_HIP_TRY(hipMemsetAsync(c.d_counters, 0, 2 * kCounterWords * sizeof(uint32_t), stream));
+    if (int rc = ensure(stream, c.d_far, (far_sub_cap ? far_sub_cap * kFarLists : 1) * sizeof(FarItem))) return rc;
+    if (int rc = ensure(stream, c.d_big, p.big_cap * sizeof(BigItem))) return rc;
+    if (int rc = ensure(stream, c.d_rare, p.rare_cap * sizeof(RareItem))) return rc;
+    if (!c.d_counters.p) {
+        if (int rc = ensure(stream, c.d_counters, 2 * kCounterWords * sizeof(uint32_t))) return rc;      // two sets, alternating
+        TOPO_HIP_TRY(hipMemsetAsync(c.d_counters.p, 0, 2 * kCounterWords * sizeof(uint32_t), stream));
     }
-    if (!c.h_status) TOPO_HIP_TRY(hipHostMalloc((void**)&c.h_status, kStatusRing * 16 * sizeof(uint32_t)));
+    if (!c.h_status) TOPO_HIP_TRY(hipHostMalloc((void**)&c.h_status, kStatusRing * kStatusWords * sizeof(uint32_t)));
     if (c.submitted - c.checked == kStatusRing) {      // nobody has waited for this context's frames for a whole ring: fold them now
         if (c.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(c.last_stream));      // (where the latest of them was queued)
         overflow_pending_ |= fold_frames(c);
     }
     c.last_stream = stream;
     c.pending = pipeline_depth_ > 1;
-    // View constants.  Up to kPackViews views (a panorama's eight sectors) travel as the argument of a one-workgroup kernel
-    // (k_put_views: the launch copies them; a copy-engine operation and the event guarding its pinned source cost the GPU 13 us
-    // per frame and the host two more calls).  Larger submissions go through a small ring of pinned staging slots, each guarded
-    // by an event, so a submission never has to wait for the stream (pageable sources would force a synchronous staging copy).
-    // Either way each slot has its own device copy, so a later submission cannot overwrite constants a running frame reads.
+    p.work_cap = (uint32_t)work_cap;
+    p.far_sub_cap = (uint32_t)far_sub_cap;
+    p.near_cap = (uint32_t)near_cap;
+    return TOPO_OK;
+}
+
+// View constants.  Up to kPackViews views (a panorama's eight sectors) travel as the argument of a one-workgroup kernel
+// (k_put_views: the launch copies them; a copy-engine operation and the event guarding its pinned source cost the GPU 13 us
+// per frame and the host two more calls).  Larger submissions go through a small ring of pinned staging slots, each guarded
+// by an event, so a submission never has to wait for the stream (pageable sources would force a synchronous staging copy).
+// Either way each slot has its own device copy, so a later submission cannot overwrite constants a running frame reads.
+// (With the frame's first kernel being k_clear_cull -- there are tiles to cull -- the pack rides in THAT launch's argument
+// segment, *pack_in_cull: no upload kernel either; TOPO_VIEWS_IN_CULL=0: always k_put_views.)
+int TerrainRenderer::stage_views(FrameCtx& c, hipStream_t stream, const topo_uniforms* views, FrameParams& p, ViewPack& pack, bool* pack_in_cull) {
+    const uint32_t n = p.n_views;
     if (n > kMaxViewsPerSlot) return fail(TOPO_ERR_INVALID, "too many views in one submission");
-    static const bool pack_off = getenv("TOPO_VIEWS_BY_COPY") && atoi(getenv("TOPO_VIEWS_BY_COPY")) != 0;
     static_assert(kViewSlots % kMaxPipeline == 0, "every frame context has its own share of the slots");
     // a slot belongs to one frame context, so whatever used it before is ahead of this submission in the same stream
     const int slot = (int)(&c - ctx_) * (kViewSlots / kMaxPipeline) + (int)(c.frames % (kViewSlots / kMaxPipeline));
-    ViewDev* d_slot = (ViewDev*)d_views_ + (size_t)slot * kMaxViewsPerSlot;
+    ViewDev* d_slot = d_views_.as<ViewDev>() + (size_t)slot * kMaxViewsPerSlot;
+    p.views = d_slot;
     auto fill_views = [&](ViewDev* vd) {
         for (uint32_t i = 0; i < n; ++i) {
             memcpy(vd[i].proj, views[i].camera_proj, sizeof vd[i].proj);
@@ -521,114 +612,73 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
             vd[i].view_mode = views[i].view_mode;
         }
     };
-    // (with the frame's first kernel being k_clear_cull -- there are tiles to cull -- the pack rides in THAT launch's argument
-    // segment: no upload kernel either; TOPO_VIEWS_IN_CULL=0: always k_put_views)
-    static const bool fuse_off = getenv("TOPO_FUSE_CLEAR_CULL") && atoi(getenv("TOPO_FUSE_CLEAR_CULL")) == 0;
-    static const bool in_cull_off = getenv("TOPO_VIEWS_IN_CULL") && atoi(getenv("TOPO_VIEWS_IN_CULL")) == 0;
-    const bool fuse = !fuse_off && n_tiles != 0;
-    ViewPack pack{};
-    const bool packed = n <= kPackViews && !pack_off, pack_in_cull = packed && fuse && !in_cull_off;
+    const bool packed = n <= kPackViews && !switches().views_by_copy;
+    *pack_in_cull = packed && fused_clear_cull(p) && switches().views_in_cull;
     if (packed) {
         fill_views(pack.v);
-        if (!pack_in_cull) launch_put_views(pack, n, d_slot, stream);
-    } else {
-        if (!h_views_) {
-            TOPO_HIP_TRY(hipHostMalloc((void**)&h_views_, sizeof(ViewDev) * kMaxViewsPerSlot * kViewSlots));
-            for (int i = 0; i < kViewSlots; ++i) TOPO_HIP_TRY(hipEventCreateWithFlags(&view_ev_[i], hipEventDisableTiming));
-        }
-        if (view_used_[slot]) TOPO_HIP_TRY(hipEventSynchronize(view_ev_[slot]));
-        ViewDev* vd = h_views_ + (size_t)slot * kMaxViewsPerSlot;
-        fill_views(vd);
-        TOPO_HIP_TRY(hipMemcpyAsync(d_slot, vd, n * sizeof(ViewDev), hipMemcpyHostToDevice, stream));
-        TOPO_HIP_TRY(hipEventRecord(view_ev_[slot], stream));
-        view_used_[slot] = true;
+        if (!*pack_in_cull) launch_put_views(pack, n, d_slot, stream);
+        return TOPO_OK;
     }
+    if (!h_views_) {
+        TOPO_HIP_TRY(hipHostMalloc((void**)&h_views_, sizeof(ViewDev) * kMaxViewsPerSlot * kViewSlots));
+        for (int i = 0; i < kViewSlots; ++i) TOPO_HIP_TRY(hipEventCreateWithFlags(&view_ev_[i], hipEventDisableTiming));
+    }
+    if (view_used_[slot]) TOPO_HIP_TRY(hipEventSynchronize(view_ev_[slot]));
+    ViewDev* vd = h_views_ + (size_t)slot * kMaxViewsPerSlot;
+    fill_views(vd);
+    TOPO_HIP_TRY(hipMemcpyAsync(d_slot, vd, n * sizeof(ViewDev), hipMemcpyHostToDevice, stream));
+    TOPO_HIP_TRY(hipEventRecord(view_ev_[slot], stream));
+    view_used_[slot] = true;
+    return TOPO_OK;
+}
 
-    FrameParams p{};
-    p.tiles = (const TileDev*)d_tiles_;
-    p.views = d_slot;
-    p.vis = (uint64_t*)c.d_vis;
-    p.dirty = (uint8_t*)c.d_dirty;
-    p.work = (WorkItem*)c.d_work;
+// Everything of FrameParams that grow_frame_buffers and stage_views have not set (post_off and the resolve range: queue_frame).
+void TerrainRenderer::fill_params(FrameCtx& c, FrameParams& p) {
+    p.tiles = d_tiles_.as<const TileDev>();
+    p.vis = c.d_vis.as<uint64_t>();
+    p.dirty = c.d_dirty.as<uint8_t>();
+    p.work = c.d_work.as<WorkItem>();
     // this frame's counter set; the other one is zeroed by this frame's clear for the next frame of the context
-    p.counters = (uint32_t*)c.d_counters + (c.frames & 1u) * kCounterWords;
+    p.counters = c.d_counters.as<uint32_t>() + (c.frames & 1u) * kCounterWords;
     // this frame's counters (queue fills, status bits), for whoever waits for the frame (check_frames, get_counters): stored by
     // k_resolve into the pinned ring.  The bounds-checking build, whose k_resolve may still set a status bit, copies them
     // behind the frame instead.
-    uint32_t* const h_status_slot = c.h_status + (c.submitted % kStatusRing) * 16;
 #if defined(TOPO_BOUNDS_CHECK) || defined(TOPO_RESOLVE_PROF)
     p.status_out = nullptr;
 #else
-    static const bool status_copy = getenv("TOPO_STATUS_BY_COPY") && atoi(getenv("TOPO_STATUS_BY_COPY")) != 0;
-    p.status_out = status_copy ? nullptr : h_status_slot;
+    p.status_out = switches().status_by_copy ? nullptr : c.status_words(c.submitted);
 #endif
-    uint32_t* const counters_next = (uint32_t*)c.d_counters + ((c.frames & 1u) ^ 1u) * kCounterWords;
-    p.big = (BigItem*)c.d_big;
-    p.rare = (RareItem*)c.d_rare;
-    p.far = (FarItem*)c.d_far;
-    p.work2 = (WorkItem*)c.d_work2;
+    p.big = c.d_big.as<BigItem>();
+    p.rare = c.d_rare.as<RareItem>();
+    p.far = c.d_far.as<FarItem>();
+    p.work2 = c.d_work2.as<WorkItem>();
     p.split_m = occlusion_split_m_;
-    p.rare_cap = (uint32_t)rare_cap;
-    p.work_cap = (uint32_t)work_cap;
-    p.far_sub_cap = (uint32_t)far_sub_cap;
-    p.near_cap = (uint32_t)near_cap;
-    p.near_strip = near_strip;
-    p.big_cap = (uint32_t)big_cap;
-    p.n_views = n;
-    p.n_tiles = n_tiles;
-    p.W = (int32_t)w;
-    p.H = (int32_t)h;
     p.tile_w = tile_w_;
     p.tile_h = tile_h_;
-    p.bx_count = bxc;
-    p.by_count = byc;
-    p.tris_per_tile = n_tiles ? 2u * (tile_w_ - 1) * (tile_h_ - 1) : 8u;
+    p.tris_per_tile = p.n_tiles ? 2u * (tile_w_ - 1) * (tile_h_ - 1) : 8u;
     p.div_tris = fastdiv_make(p.tris_per_tile);
-    p.div_hm1 = fastdiv_make(n_tiles ? tile_h_ - 1 : 2u);
-    p.rblocks_x = (w + kResolveBlockW - 1) / kResolveBlockW;
-    p.rblocks_view = p.rblocks_x * ((h + kResolveBlockH - 1) / kResolveBlockH);
+    p.div_hm1 = fastdiv_make(p.n_tiles ? tile_h_ - 1 : 2u);
+    p.rblocks_x = ((uint32_t)p.W + kResolveBlockW - 1) / kResolveBlockW;
+    p.rblocks_view = p.rblocks_x * (((uint32_t)p.H + kResolveBlockH - 1) / kResolveBlockH);
     p.div_rblocks_x = fastdiv_make(p.rblocks_x > 1 ? p.rblocks_x : 2u);
     p.div_rblocks_view = fastdiv_make(p.rblocks_view > 1 ? p.rblocks_view : 2u);
-    {   // the cleared render target texel: Color{0, 0.71, 0.885, 1} (terrain_renderer.rs:379-384) stored as Rgba8UnormSrgb
-        float thresh[256];
-        for (int i = 0; i < 256; ++i) thresh[i] = bits_f(TOPO_SRGB_THRESH_BITS[i]);
-        p.linear_target = (format_ == TOPO_FORMAT_RGBA8_UNORM || format_ == TOPO_FORMAT_BGRA8_UNORM) ? 1u : 0u;
-        p.bgra = (format_ == TOPO_FORMAT_BGRA8_UNORM_SRGB || format_ == TOPO_FORMAT_BGRA8_UNORM) ? 1u : 0u;
-        p.sky_c8 = (p.linear_target ? to_unorm8(0.0f) | (to_unorm8(0.71f) << 8) | (to_unorm8(0.885f) << 16)
-                                    : srgb_encode(thresh, 0.0f) | (srgb_encode(thresh, 0.71f) << 8) | (srgb_encode(thresh, 0.885f) << 16)) |
-                   (to_unorm8(1.0f) << 24);
-    }
-    last_blocks_tested_ = (uint32_t)work_cap;
-    // Is the far phase worth its four launches (each ~4 us of GPU and ~9 us of host time)?  k_cull makes an occlusion-test
-    // candidate of a block whose nearest possible view depth, w(centre) - radius |w row|, exceeds the split;
-    // w(centre) <= w(C) + R |w row| for the sphere (C, R) around the tile's block centres (Tile::centres).  The split is a
-    // performance knob with a flat optimum (60..120 km at c4; results do not depend on it): when that bound stays below 4/3 of
-    // it for every view and tile -- a lone tile around the viewpoint -- the frame's split is raised above the bound, no block
-    // becomes a candidate and the far phase is not launched.
-    bool far_phase = p.split_m > 0.0f;
-    static const bool far_skip_off = getenv("TOPO_FAR_SKIP") && atoi(getenv("TOPO_FAR_SKIP")) == 0;
-    if (far_phase && !far_skip_off) {
-        double bound = 0.0;
-        for (uint32_t i = 0; i < n && bound >= 0.0; ++i) {
-            const float* m = views[i].camera_proj;
-            const double wn = std::sqrt((double)m[3] * m[3] + (double)m[7] * m[7] + (double)m[11] * m[11]);
-            for (const auto& kv : tiles_) {
-                const double* s = kv.second.centres;
-                const double w_far = (double)m[3] * s[0] + (double)m[7] * s[1] + (double)m[11] * s[2] + (double)m[15] + s[3] * wn;
-                if (!(s[3] >= 0.0) || !(w_far < 1e30)) { bound = -1.0; break; }      // unknown sphere, NaN or huge: keep the far phase
-                bound = std::max(bound, w_far);
-            }
-        }
-        if (bound >= 0.0 && bound + 2.0 < (double)p.split_m * (4.0 / 3.0)) {
-            p.split_m = std::max(p.split_m, (float)(bound + 2.0));      // (>= bound + 1 after the rounding to f32: no candidates)
-            far_phase = false;
-        }
-    }
-    last_far_phase_ = far_phase;
+    // the cleared render target texel: Color{0, 0.71, 0.885, 1} (terrain_renderer.rs:379-384) stored as Rgba8UnormSrgb
+    float thresh[256];
+    for (int i = 0; i < 256; ++i) thresh[i] = bits_f(TOPO_SRGB_THRESH_BITS[i]);
+    p.linear_target = is_linear(format_) ? 1u : 0u;
+    p.bgra = is_bgra(format_) ? 1u : 0u;
+    p.sky_c8 = (p.linear_target ? to_unorm8(0.0f) | (to_unorm8(0.71f) << 8) | (to_unorm8(0.885f) << 16)
+                                : srgb_encode(thresh, 0.0f) | (srgb_encode(thresh, 0.71f) << 8) | (srgb_encode(thresh, 0.885f) << 16)) |
+               (to_unorm8(1.0f) << 24);
+}
 
-    // clear -> cull -> [near blocks: raster, rare, big] -> occlusion test of the far blocks -> [survivors: raster,
-    // rare, big] -> resolve.  Event slots: 0 clear, 1 cull, 2 raster(near), 3 rare+big(near), 4 occlusion,
-    // 5 raster(far), 6 rare+big(far), 7 resolve.
+// clear -> cull -> [near blocks: raster, rare, big] -> occlusion test of the far blocks -> [survivors: raster,
+// rare, big] -> resolve.  Event slots: 0 clear, 1 cull, 2 raster(near), 3 rare+big(near), 4 occlusion,
+// 5 raster(far), 6 rare+big(far), 7 resolve.
+int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p, const ViewPack* pack_in_cull, bool far_phase, const OutputParams& out,
+                                 const ResolveSlot* slots, uint32_t n_slots, const std::function<int(uint32_t, hipStream_t)>* after_slot) {
+    const uint32_t n = p.n_views, w = (uint32_t)p.W, h = (uint32_t)p.H;
+    uint32_t* const counters_next = c.d_counters.as<uint32_t>() + ((c.frames & 1u) ^ 1u) * kCounterWords;
     // A timing event between two kernels costs ~6 us of idle GPU (the next kernel waits for the marker), so only the
     // events the selected timing slots need are recorded (topo_set_timing_slots); slot -> stages: 0:{0} 1:{1} 2:{2,5} 3:{4}
     // 4:{3,6} 5:{7}, stage i = ev[i]..ev[i+1]; the total (ev[0], ev[8]) is always kept.
@@ -644,8 +694,7 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     // the kernels but the kernels' own start and end times (hipExtLaunchKernel: ev[0] = start of the frame's first kernel, ev[7] /
     // ev[8] = start / end of k_resolve): a pair of markers costs a frame 8-10 us, these next to nothing.
     const bool pixelize = post_.pixelize_n < 99.99999f;
-    static const bool markers_only = getenv("TOPO_EVENTS_BY_MARKER") && atoi(getenv("TOPO_EVENTS_BY_MARKER")) != 0;
-    const bool own_times = !markers_only && !pixelize && (timing_slots_ & ~(1u << 5)) == 0;
+    const bool own_times = !switches().events_by_marker && !pixelize && (timing_slots_ & ~(1u << 5)) == 0;
     const int ring = (int)(c.frames % kEvRing);
     hipEvent_t* const ev = c.evr[ring];
     c.evr_recorded[ring] = ev_need;
@@ -656,7 +705,8 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     const hipEvent_t ev_first = (ev_need & (1u << 0)) && own_times ? ev[0] : nullptr;
     // clear and cull side by side in one launch (timing slot "clear" then holds both, "cull" nothing); TOPO_FUSE_CLEAR_CULL=0 or
     // an empty tile set: one after the other
-    if (fuse) launch_clear_cull(p, counters_next, stream, ev_first, pack_in_cull ? &pack : nullptr, n);
+    const bool fuse = fused_clear_cull(p);
+    if (fuse) launch_clear_cull(p, counters_next, stream, ev_first, pack_in_cull, n);
     else launch_clear(p, counters_next, stream, ev_first);
     if (ev_need & (1u << 1)) TOPO_HIP_TRY(hipEventRecord(ev[1], stream));
     if (!fuse) launch_cull(p, stream);
@@ -666,9 +716,7 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     launch_raster_rare(p, stream);
     launch_raster_big(p, stream);
     if (ev_need & (1u << 4)) TOPO_HIP_TRY(hipEventRecord(ev[4], stream));
-    if (far_phase) {
-        launch_occlusion(p, stream);
-    }
+    if (far_phase) launch_occlusion(p, stream);
     if (ev_need & (1u << 5)) TOPO_HIP_TRY(hipEventRecord(ev[5], stream));
     if (far_phase) launch_raster(p, 1, stream);
     if (ev_need & (1u << 6)) TOPO_HIP_TRY(hipEventRecord(ev[6], stream));
@@ -686,13 +734,13 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     if (pixelize) {
         if (n_slots) return fail(TOPO_ERR_UNSUPPORTED, "the pixelise branch is not available on the slot-by-slot (multi-GPU) path");
         const size_t img = (size_t)w * h * 4;
-        if (int rc = ensure_on(stream, &c.d_pre_rgba, &c.cap_pre_rgba, img * n)) return rc;
+        if (int rc = ensure(stream, c.d_pre_rgba, img * n)) return rc;
         if (!out.depth)
-            if (int rc = ensure_on(stream, &c.d_pre_depth, &c.cap_pre_depth, img * n)) return rc;
-        kout.rgba = (uint8_t*)c.d_pre_rgba;
+            if (int rc = ensure(stream, c.d_pre_depth, img * n)) return rc;
+        kout.rgba = c.d_pre_rgba.as<uint8_t>();
         kout.rgba_view_stride = img;
         kout.rgba_pitch = (size_t)w * 4;
-        if (!out.depth) { kout.depth = (float*)c.d_pre_depth; kout.depth_view_stride = img; kout.depth_pitch = (size_t)w * 4; }
+        if (!out.depth) { kout.depth = c.d_pre_depth.as<float>(); kout.depth_view_stride = img; kout.depth_pitch = (size_t)w * 4; }
         p.post_off = 1;
     }
     if (n_slots == 0) {
@@ -701,7 +749,7 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
         launch_resolve(p, kout, stream, ev_rstart, ev_rstop);
         if (pixelize)
             launch_post_pixelize(n, (int32_t)w, (int32_t)h, post_.viewport[0] >= 1.0f ? post_.viewport[0] : (float)w, post_.viewport[1] >= 1.0f ? post_.viewport[1] : (float)h,
-                                 post_.pixelize_n, (const uint8_t*)c.d_pre_rgba, out, kout.depth, kout.depth_view_stride, kout.depth_pitch, p.linear_target, p.bgra, stream);
+                                 post_.pixelize_n, c.d_pre_rgba.as<const uint8_t>(), out, kout.depth, kout.depth_view_stride, kout.depth_pitch, p.linear_target, p.bgra, stream);
     } else {
         for (uint32_t i = 0; i < n_slots; ++i) {
             if ((uint64_t)slots[i].block_first + slots[i].block_count > (uint64_t)p.rblocks_view * n) return fail(TOPO_ERR_INVALID, "resolve slot outside the frame");
@@ -713,24 +761,31 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
         }
     }
     if (vs_on_)      // behind the frame's last k_resolve (and its last slot): the cells that won a pixel, into the tiles' masks
-        launch_viewshed(p, (uint32_t* const*)d_vs_table_, d_vs_stats_, stream);
+        launch_viewshed(p, d_vs_table_.as<uint32_t* const>(), d_vs_stats_.as<unsigned long long>(), stream);
     if ((ev_need & (1u << 8)) && !own_times) TOPO_HIP_TRY(hipEventRecord(ev[8], stream));
-    if (!p.status_out) TOPO_HIP_TRY(hipMemcpyAsync(h_status_slot, p.counters, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (!p.status_out) TOPO_HIP_TRY(hipMemcpyAsync(c.status_words(c.submitted), p.counters, kStatusWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    return TOPO_OK;
+}
+
+// The submission as the status ring, the timings and the horizon query see it.
+void TerrainRenderer::record_submission(FrameCtx& c, const FrameParams& p) {
     ++c.submitted;
     c.timed = true;
-    c.sub.n_views = n;
-    c.sub.W = w;
-    c.sub.H = h;
-    c.sub.n_tiles = n_tiles;
-    c.sub.tris_per_tile = p.tris_per_tile;
-    c.sub.hm1 = n_tiles ? tile_h_ - 1 : 2u;
-    c.sub.div_tris = p.div_tris;
-    c.sub.div_hm1 = p.div_hm1;
-    c.sub.counters = p.counters;
+    c.sub.n_views = p.n_views;
     c.sub.tile_gen = tile_gen_;
+    HorizonParams& q = c.sub.query;
+    q.vis = p.vis;
+    q.dirty = p.dirty;
+    q.counters = p.counters;
+    q.W = (uint32_t)p.W;
+    q.H = (uint32_t)p.H;
+    q.n_keys = (size_t)p.n_views * q.W * q.H;
+    q.n_tiles = p.n_tiles;
+    q.tris_per_tile = p.tris_per_tile;
+    q.hm1 = p.n_tiles ? tile_h_ - 1 : 2u;
+    q.div_tris = p.div_tris;
+    q.div_hm1 = p.div_hm1;
     latest_ctx_ = (int)(&c - ctx_);
-    TOPO_HIP_TRY(hipGetLastError());
-    return TOPO_OK;
 }
 
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
@@ -753,9 +808,9 @@ int TerrainRenderer::viewshed_enable(bool on) {
     if (on && !vs_ever_) {
         if (int rc = join()) return rc;
         const size_t stats = (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long);
-        if (!d_vs_stats_) {
-            TOPO_HIP_TRY(hipMalloc((void**)&d_vs_stats_, stats));
-            TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_, 0, stats, stream_));
+        if (!d_vs_stats_.p) {
+            if (int rc = ensure(stream_, d_vs_stats_, stats)) return rc;
+            TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_.p, 0, stats, stream_));
         }
         for (auto& kv : tiles_)
             if (!kv.second.d_mask)
@@ -772,7 +827,7 @@ int TerrainRenderer::viewshed_reset() {
     if (!vs_ever_) return TOPO_OK;
     if (int rc = join()) return rc;      // frames in flight on the contexts' own streams; later ones are ordered after stream_
     for (auto& kv : tiles_) TOPO_HIP_TRY(hipMemsetAsync(kv.second.d_mask, 0, mask_bytes(), stream_));
-    TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_, 0, (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long), stream_));
+    TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_.p, 0, (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long), stream_));
     return TOPO_OK;
 }
 
@@ -783,8 +838,7 @@ int TerrainRenderer::viewshed_read(int32_t lat, int32_t lon, uint8_t* mask_out, 
     if (!vs_ever_) return fail(TOPO_ERR_INVALID, "viewshed accumulation was never enabled");
     const uint32_t wm1 = tile_w_ - 1, hm1 = tile_h_ - 1;
     if (pitch < wm1) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (int rc = wait_all()) return rc;
     std::vector<uint32_t> words(mask_bytes() / 4);
     TOPO_HIP_TRY(hipMemcpy(words.data(), t->d_mask, mask_bytes(), hipMemcpyDeviceToHost));
     uint64_t count = 0;
@@ -802,10 +856,9 @@ int TerrainRenderer::viewshed_stats(uint64_t out[3]) {
     if (!out) return fail(TOPO_ERR_INVALID, "null argument");
     out[0] = out[1] = out[2] = 0;
     if (!vs_ever_) return TOPO_OK;
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (int rc = wait_all()) return rc;
     std::vector<unsigned long long> s((size_t)kViewshedStatSlots * 4);
-    TOPO_HIP_TRY(hipMemcpy(s.data(), d_vs_stats_, s.size() * sizeof(s[0]), hipMemcpyDeviceToHost));
+    TOPO_HIP_TRY(hipMemcpy(s.data(), d_vs_stats_.p, s.size() * sizeof(s[0]), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < s.size(); i += 4)
         for (int k = 0; k < 3; ++k) out[k] += s[i + k];
     return TOPO_OK;
@@ -820,8 +873,8 @@ int TerrainRenderer::horizon_shape(uint32_t* n_views, uint32_t* w, uint32_t* h) 
     if (latest_ctx_ < 0) return fail(TOPO_ERR_INVALID, "no submission to query");
     const FrameCtx::Submission& s = ctx_[latest_ctx_].sub;
     *n_views = s.n_views;
-    *w = s.W;
-    *h = s.H;
+    *w = s.query.W;
+    *h = s.query.H;
     return TOPO_OK;
 }
 
@@ -832,7 +885,7 @@ int TerrainRenderer::horizon_prepare(uint32_t first, uint32_t n, size_t view_str
     FrameCtx& c = ctx_[latest_ctx_];
     if (c.sub.tile_gen != tile_gen_) return fail(TOPO_ERR_INVALID, "tiles were added or unloaded since the latest submission: its draw order is gone");
     if (n == 0 || first >= c.sub.n_views || n > c.sub.n_views - first) return fail(TOPO_ERR_INVALID, "views outside the latest submission");
-    if (view_stride < c.sub.W) return fail(TOPO_ERR_INVALID, "view stride smaller than a view's width");
+    if (view_stride < c.sub.query.W) return fail(TOPO_ERR_INVALID, "view stride smaller than a view's width");
     if (int rc = bind_device()) return rc;
     *out_c = &c;
     *out_s = c.last_stream ? c.last_stream : stream_;      // (null: a wait covered it and the stream may be gone; the frame is done)
@@ -844,41 +897,29 @@ int TerrainRenderer::horizon_prepare(uint32_t first, uint32_t n, size_t view_str
 // earlier query has finished (add_terrain / unload_terrain join the frames, and a query on a context's own stream marks it pending).
 int TerrainRenderer::horizon_launch(FrameCtx& c, uint32_t first, uint32_t n, HorizonPoint* out, size_t view_stride, hipStream_t s) {
     if (hz_ll_gen_ != tile_gen_) {
-        if (int rc = join()) return rc;
-        TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+        if (int rc = wait_all()) return rc;
         hz_ll_.clear();
         for (const auto& kv : tiles_) {      // draw order
             hz_ll_.push_back(kv.second.lat);
             hz_ll_.push_back(kv.second.lon);
         }
-        if (int rc = ensure(&d_hz_ll_, &cap_hz_ll_, (hz_ll_.size() + 2) * sizeof(int32_t))) return rc;
-        if (!hz_ll_.empty()) TOPO_HIP_TRY(hipMemcpyAsync(d_hz_ll_, hz_ll_.data(), hz_ll_.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (int rc = ensure(stream_, d_hz_ll_, (hz_ll_.size() + 2) * sizeof(int32_t))) return rc;
+        if (!hz_ll_.empty()) TOPO_HIP_TRY(hipMemcpyAsync(d_hz_ll_.p, hz_ll_.data(), hz_ll_.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         hz_ll_gen_ = tile_gen_;
     }
 #ifdef TOPO_BOUNDS_CHECK
-    if (!d_hz_check_) {
-        TOPO_HIP_TRY(hipMalloc((void**)&d_hz_check_, 16 * sizeof(uint32_t)));
-        TOPO_HIP_TRY(hipMemsetAsync(d_hz_check_, 0, 16 * sizeof(uint32_t), s));
+    if (!d_hz_check_.p) {
+        if (int rc = ensure(s, d_hz_check_, kStatusWords * sizeof(uint32_t))) return rc;
+        TOPO_HIP_TRY(hipMemsetAsync(d_hz_check_.p, 0, kStatusWords * sizeof(uint32_t), s));
     }
 #endif
-    HorizonParams p{};
-    p.vis = (const uint64_t*)c.d_vis;
-    p.dirty = (const uint8_t*)c.d_dirty;
-    p.counters = c.sub.counters;
-    p.check = d_hz_check_;
-    p.tile_ll = (const int32_t*)d_hz_ll_;
+    HorizonParams p = c.sub.query;
+    p.check = d_hz_check_.as<uint32_t>();
+    p.tile_ll = d_hz_ll_.as<const int32_t>();
     p.out = out;
     p.view_stride = view_stride;
-    p.n_keys = (size_t)c.sub.n_views * c.sub.W * c.sub.H;
     p.first_view = first;
     p.n_views = n;
-    p.W = c.sub.W;
-    p.H = c.sub.H;
-    p.n_tiles = c.sub.n_tiles;
-    p.tris_per_tile = c.sub.tris_per_tile;
-    p.hm1 = c.sub.hm1;
-    p.div_tris = c.sub.div_tris;
-    p.div_hm1 = c.sub.div_hm1;
     launch_horizon(p, s);
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
@@ -887,13 +928,12 @@ int TerrainRenderer::horizon_launch(FrameCtx& c, uint32_t first, uint32_t n, Hor
 // The bounds-checking build: what k_horizon recorded, into the status topo_frame_status reports (the queries have finished).
 int TerrainRenderer::horizon_fold_check() {
 #ifdef TOPO_BOUNDS_CHECK
-    if (!d_hz_check_) return TOPO_OK;
-    uint32_t w[16];
-    TOPO_HIP_TRY(hipMemcpy(w, d_hz_check_, sizeof w, hipMemcpyDeviceToHost));
-    if (w[2] & kStatusBounds) {
-        last_status_[0] |= kStatusBounds;
-        last_status_[1] = w[8]; last_status_[2] = w[9]; last_status_[3] = w[10];
-        TOPO_HIP_TRY(hipMemset(d_hz_check_, 0, sizeof w));
+    if (!d_hz_check_.p) return TOPO_OK;
+    uint32_t w[kStatusWords];
+    TOPO_HIP_TRY(hipMemcpy(w, d_hz_check_.p, sizeof w, hipMemcpyDeviceToHost));
+    if (w[kCtrStatus] & kStatusBounds) {
+        record_bounds(w);
+        TOPO_HIP_TRY(hipMemset(d_hz_check_.p, 0, sizeof w));
     }
 #endif
     return TOPO_OK;
@@ -907,16 +947,15 @@ int TerrainRenderer::horizon_read(uint32_t first, uint32_t n, topo_horizon_point
     FrameCtx* c = nullptr;
     hipStream_t s = nullptr;
     if (int rc = horizon_prepare(first, n, view_stride, &c, &s)) return rc;
-    const size_t row = (size_t)c->sub.W * sizeof(HorizonPoint);
-    if (int rc = ensure_on(s, &d_hz_out_, &cap_hz_out_, row * n)) return rc;
-    if (int rc = horizon_launch(*c, first, n, (HorizonPoint*)d_hz_out_, c->sub.W, s)) return rc;
-    TOPO_HIP_TRY(hipMemcpy2DAsync(out, view_stride * sizeof(topo_horizon_point), d_hz_out_, row, row, n, hipMemcpyDeviceToHost, s));
+    const size_t row = (size_t)c->sub.query.W * sizeof(HorizonPoint);
+    if (int rc = ensure(s, d_hz_out_, row * n)) return rc;
+    if (int rc = horizon_launch(*c, first, n, d_hz_out_.as<HorizonPoint>(), c->sub.query.W, s)) return rc;
+    TOPO_HIP_TRY(hipMemcpy2DAsync(out, view_stride * sizeof(topo_horizon_point), d_hz_out_.p, row, row, n, hipMemcpyDeviceToHost, s));
     TOPO_HIP_TRY(hipStreamSynchronize(s));      // (the stream of the context's latest frame: all its frames are done)
     c->pending = false;
-    overflow_pending_ |= fold_frames(*c, c->submitted - 1);
-    (void)fold_frames(*c);
+    const bool overflow = fold_latest(*c, false);
     if (int rc = horizon_fold_check()) return rc;
-    if (c->h_status[((c->submitted - 1) % kStatusRing) * 16 + 2] & kStatusRareOverflow)
+    if (overflow)
         return fail(TOPO_ERR_CAPACITY, "rare-triangle queue overflowed: the latest submission is incomplete, and so is its horizon");
     return TOPO_OK;
 }
@@ -937,14 +976,7 @@ int TerrainRenderer::render_device(uint8_t* rgba_dev, size_t rgba_pitch, float* 
     if (!rgba_dev) return fail(TOPO_ERR_INVALID, "rgba_dev is null");
     if (!have_uniforms_) return fail(TOPO_ERR_INVALID, "topo_update has not been called");
     if (rgba_pitch < (size_t)W_ * 4 || (depth_dev && depth_pitch < (size_t)W_ * 4)) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
-    OutputParams o{};
-    o.rgba = rgba_dev;
-    o.rgba_view_stride = rgba_pitch * H_;
-    o.rgba_pitch = rgba_pitch;
-    o.depth = depth_dev;
-    o.depth_view_stride = depth_pitch * H_;
-    o.depth_pitch = depth_pitch;
-    return render_views_device(1, &uniforms_, W_, H_, o);
+    return render_views_device(1, &uniforms_, W_, H_, image_output(rgba_dev, rgba_pitch, depth_dev, depth_pitch, H_));
 }
 
 // render (terrain_renderer.rs:365-452) + depth copy (render_engine.rs:219-249), host outputs.
@@ -954,47 +986,32 @@ int TerrainRenderer::render(uint8_t* rgba, size_t rgba_pitch, float* depth, size
     if (rgba_pitch < (size_t)W_ * 4 || (depth && depth_pitch < (size_t)W_ * 4)) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
     if (int rc = bind_device()) return rc;
     const size_t row = (size_t)W_ * 4;
-    if (int rc = ensure(&d_out_rgba_, &cap_out_rgba_, row * H_)) return rc;
+    if (int rc = ensure(stream_, d_out_rgba_, row * H_)) return rc;
     if (depth)
-        if (int rc = ensure(&d_out_depth_, &cap_out_depth_, row * H_)) return rc;
-    OutputParams o{};
-    o.rgba = (uint8_t*)d_out_rgba_;
-    o.rgba_view_stride = row * H_;
-    o.rgba_pitch = row;
-    o.depth = depth ? (float*)d_out_depth_ : nullptr;
-    o.depth_view_stride = row * H_;
-    o.depth_pitch = row;
+        if (int rc = ensure(stream_, d_out_depth_, row * H_)) return rc;
+    const OutputParams o = image_output(d_out_rgba_.as<uint8_t>(), row, depth ? d_out_depth_.as<float>() : nullptr, row, H_);
     // A frame whose rare-triangle queue overflowed is incomplete.  The synchronous entry point does not hand such a frame
     // out: it grows the queue to what the frame asked for and renders it again (an explicit topo_debug_set_queue_caps
     // setting is a test hook and is left alone: then the call fails with TOPO_ERR_CAPACITY).
     // Frames queued earlier through the asynchronous entry points are waited for, but an overflow of one of THEM is not this
     // call's error (the caller could not tell which frame failed, and this frame would go unrendered): it stays pending and
     // is reported, once, by the next topo_join / topo_synchronize -- the calls that wait for those frames.
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-    for (auto& fc : ctx_)
-        if (!fc.pending && fc.h_status) overflow_pending_ |= fold_frames(fc);
+    if (int rc = wait_all()) return rc;
+    overflow_pending_ |= fold_idle();
     for (int attempt = 0;; ++attempt) {
         if (int rc = render_views_device(1, &uniforms_, W_, H_, o)) return rc;
-        if (int rc = join()) return rc;       // (pipelined contexts run on their own streams)
-        TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+        if (int rc = wait_all()) return rc;       // (pipelined contexts run on their own streams)
         FrameCtx& fc = ctx_[last_ctx_];
-        overflow_pending_ |= fold_frames(fc, fc.submitted - 1);      // (nothing: the frames in front of this one were folded above)
-        const uint32_t* words = fc.h_status + ((fc.submitted - 1) % kStatusRing) * 16;
-        const uint32_t status = words[2], wanted = words[3];
-        if (!(status & kStatusRareOverflow) || rare_cap_cfg_ != 0 || attempt >= 3) {
-            // the frame this call answers for: its bits reach topo_frame_status, its overflow is this call's error and not pending
-            (void)fold_frames(fc);
-            if (status & kStatusRareOverflow) return fail(TOPO_ERR_CAPACITY, "rare-triangle queue overflowed: frame incomplete");
-            break;
-        }
-        ++fc.checked;      // an attempt thrown away and rendered again: its status describes no frame anyone gets
+        const bool retry = rare_cap_cfg_ == 0 && attempt < 3;
+        if (!fold_latest(fc, retry)) break;      // (the frames in front of this one were folded above)
+        if (!retry) return fail(TOPO_ERR_CAPACITY, "rare-triangle queue overflowed: frame incomplete");
+        const uint32_t wanted = fc.latest_status()[kCtrRare];
         rare_cap_auto_ = (uint64_t)wanted + wanted / 4u + 1024u;      // the overflowed frame counted what it needs
         if (rare_cap_auto_ > (1ull << 28)) return fail(TOPO_ERR_CAPACITY, "rare-triangle queue would exceed 2^28 entries");
     }
-    if (int rc = download(rgba, rgba_pitch, (const uint8_t*)d_out_rgba_, row)) return rc;
+    if (int rc = download(rgba, rgba_pitch, d_out_rgba_.as<const uint8_t>(), row)) return rc;
     if (depth)
-        if (int rc = download((uint8_t*)depth, depth_pitch, (const uint8_t*)d_out_depth_, row)) return rc;
+        if (int rc = download((uint8_t*)depth, depth_pitch, d_out_depth_.as<const uint8_t>(), row)) return rc;
     have_depth_ = depth != nullptr;
     depth_w_ = W_;
     depth_h_ = H_;
@@ -1015,12 +1032,12 @@ int TerrainRenderer::download(uint8_t* dst, size_t dst_pitch, const uint8_t* src
             return TOPO_OK;
         }
     const size_t total = row * H_;
-    if (total > cap_stage_) {
+    if (total > stage_bytes_) {
         if (h_stage_) (void)hipHostFree(h_stage_);
         h_stage_ = nullptr;
-        cap_stage_ = 0;
+        stage_bytes_ = 0;
         TOPO_HIP_TRY(hipHostMalloc((void**)&h_stage_, total));
-        cap_stage_ = total;
+        stage_bytes_ = total;
     }
     constexpr int kSlices = 8;
     if (!stage_ev_[0])
@@ -1077,6 +1094,37 @@ int TerrainRenderer::unpin_host_buffer(void* p) {
     return fail(TOPO_ERR_NOT_FOUND, "buffer was not pinned by topo_pin_host_buffer");
 }
 
+// What both overlay passes start with: the call's geometry on the device -- part a, then part b 16-byte aligned behind it
+// (*b_dev) -- and the W x H overlay keys, *keys_fresh when the pass has to initialise them.
+int TerrainRenderer::overlay_upload(const void* a, size_t a_bytes, const void* b, size_t b_bytes, uint8_t** b_dev, bool* keys_fresh) {
+    if (int rc = bind_device()) return rc;
+    const size_t b_off = (a_bytes + 15) & ~(size_t)15, keys_b = (size_t)W_ * H_ * 8;
+    if (int rc = ensure(stream_, d_overlay_geo_, b_off + b_bytes + 16)) return rc;
+    *keys_fresh = keys_b > d_overlay_keys_.cap || overlay_w_ != W_ || overlay_h_ != H_;
+    if (int rc = ensure(stream_, d_overlay_keys_, keys_b)) return rc;
+    overlay_w_ = W_; overlay_h_ = H_;
+    *b_dev = d_overlay_geo_.as<uint8_t>() + b_off;
+    if (a_bytes) TOPO_HIP_TRY(hipMemcpyAsync(d_overlay_geo_.p, a, a_bytes, hipMemcpyHostToDevice, stream_));
+    if (b_bytes) TOPO_HIP_TRY(hipMemcpyAsync(*b_dev, b, b_bytes, hipMemcpyHostToDevice, stream_));
+    return TOPO_OK;
+}
+
+// Host image in, host image out (the frame topo_render returned, or any W x H image in the context's format): `draw` is one of
+// the device forms below, over the image's device copy.
+template <class Draw>
+int TerrainRenderer::overlay_host_image(uint8_t* rgba, size_t rgba_pitch, Draw draw) {
+    if (!rgba) return fail(TOPO_ERR_INVALID, "null argument");
+    if (rgba_pitch < (size_t)W_ * 4) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
+    if (int rc = bind_device()) return rc;
+    const size_t row = (size_t)W_ * 4;
+    if (int rc = ensure(stream_, d_out_rgba_, row * H_)) return rc;
+    TOPO_HIP_TRY(hipMemcpy2DAsync(d_out_rgba_.p, row, rgba, rgba_pitch, row, H_, hipMemcpyHostToDevice, stream_));
+    if (int rc = draw(d_out_rgba_.as<uint8_t>(), row)) return rc;
+    TOPO_HIP_TRY(hipMemcpy2DAsync(rgba, rgba_pitch, d_out_rgba_.p, row, row, H_, hipMemcpyDeviceToHost, stream_));
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    return TOPO_OK;
+}
+
 // LineRenderer::render (line_renderer.rs:200-212) over an image this context produced: the overlay triangles are drawn
 // on top of the post pass's output with the reference's layering (depth Greater against the post quad's 1/4096).
 int TerrainRenderer::overlay_lines_device(const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices, float line_width,
@@ -1084,38 +1132,21 @@ int TerrainRenderer::overlay_lines_device(const void* vertices, uint32_t n_verti
     if ((n_vertices && !vertices) || (n_indices && !indices) || !rgba_dev) return fail(TOPO_ERR_INVALID, "null argument");
     if (n_indices % 3 != 0) return fail(TOPO_ERR_INVALID, "the overlay is a triangle list: index count must be a multiple of 3");
     if (rgba_pitch < (size_t)W_ * 4) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
-    if (int rc = bind_device()) return rc;
-    const size_t vb = (size_t)n_vertices * sizeof(OverlayVertex), ib = (size_t)n_indices * 4, keys_b = (size_t)W_ * H_ * 8;
-    if (int rc = ensure(&d_overlay_geo_, &cap_overlay_geo_, ((vb + 15) & ~(size_t)15) + ib + 16)) return rc;
-    const bool fresh = keys_b > cap_overlay_keys_ || overlay_w_ != W_ || overlay_h_ != H_;
-    if (int rc = ensure(&d_overlay_keys_, &cap_overlay_keys_, keys_b)) return rc;
-    overlay_w_ = W_; overlay_h_ = H_;
-    uint8_t* geo = (uint8_t*)d_overlay_geo_;
-    uint32_t* d_idx = (uint32_t*)(geo + ((vb + 15) & ~(size_t)15));
-    if (vb) TOPO_HIP_TRY(hipMemcpyAsync(geo, vertices, vb, hipMemcpyHostToDevice, stream_));
-    if (ib) TOPO_HIP_TRY(hipMemcpyAsync(d_idx, indices, ib, hipMemcpyHostToDevice, stream_));
-    const uint32_t linear = (format_ == TOPO_FORMAT_RGBA8_UNORM || format_ == TOPO_FORMAT_BGRA8_UNORM) ? 1u : 0u;
-    const uint32_t bgra = (format_ == TOPO_FORMAT_BGRA8_UNORM_SRGB || format_ == TOPO_FORMAT_BGRA8_UNORM) ? 1u : 0u;
-    launch_overlay((const OverlayVertex*)geo, d_idx, n_indices / 3, n_vertices, line_width, (int32_t)W_, (int32_t)H_, (uint64_t*)d_overlay_keys_, fresh,
-                   rgba_dev, rgba_pitch, linear, bgra, stream_);
+    uint8_t* d_idx = nullptr;
+    bool fresh = false;
+    if (int rc = overlay_upload(vertices, (size_t)n_vertices * sizeof(OverlayVertex), indices, (size_t)n_indices * 4, &d_idx, &fresh)) return rc;
+    launch_overlay(d_overlay_geo_.as<const OverlayVertex>(), (const uint32_t*)d_idx, n_indices / 3, n_vertices, line_width, (int32_t)W_, (int32_t)H_,
+                   d_overlay_keys_.as<uint64_t>(), fresh, rgba_dev, rgba_pitch, is_linear(format_), is_bgra(format_), stream_);
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));      // the geometry is only borrowed for the call
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
 }
 
-// Host image in, host image out (the frame topo_render returned, or any W x H image in the context's format).
 int TerrainRenderer::overlay_lines(const void* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices, float line_width,
                                    uint8_t* rgba, size_t rgba_pitch) {
-    if (!rgba) return fail(TOPO_ERR_INVALID, "null argument");
-    if (rgba_pitch < (size_t)W_ * 4) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
-    if (int rc = bind_device()) return rc;
-    const size_t row = (size_t)W_ * 4;
-    if (int rc = ensure(&d_out_rgba_, &cap_out_rgba_, row * H_)) return rc;
-    TOPO_HIP_TRY(hipMemcpy2DAsync(d_out_rgba_, row, rgba, rgba_pitch, row, H_, hipMemcpyHostToDevice, stream_));
-    if (int rc = overlay_lines_device(vertices, n_vertices, indices, n_indices, line_width, (uint8_t*)d_out_rgba_, row)) return rc;
-    TOPO_HIP_TRY(hipMemcpy2DAsync(rgba, rgba_pitch, d_out_rgba_, row, row, H_, hipMemcpyDeviceToHost, stream_));
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-    return TOPO_OK;
+    return overlay_host_image(rgba, rgba_pitch, [&](uint8_t* img, size_t pitch) {
+        return overlay_lines_device(vertices, n_vertices, indices, n_indices, line_width, img, pitch);
+    });
 }
 
 // TextRenderer::render (text_renderer.rs:198-204) over an image this context produced: glyphon's glyph quads, alpha-blended,
@@ -1128,20 +1159,11 @@ int TerrainRenderer::overlay_glyphs_device(const void* glyphs, uint32_t n_glyphs
     const GlyphInstance* gs = (const GlyphInstance*)glyphs;
     for (uint32_t i = 0; i < n_glyphs; ++i)
         if (gs[i].content_type_with_srgb[0] != 1) return fail(TOPO_ERR_UNSUPPORTED, "only mask glyphs (glyphon content type 1) are drawn; colour glyphs are not");
-    if (int rc = bind_device()) return rc;
-    const size_t gb = (size_t)n_glyphs * sizeof(GlyphInstance), ab = (size_t)atlas_w * atlas_h, keys_b = (size_t)W_ * H_ * 8;
-    if (int rc = ensure(&d_overlay_geo_, &cap_overlay_geo_, ((gb + 15) & ~(size_t)15) + ab + 16)) return rc;
-    const bool fresh = keys_b > cap_overlay_keys_ || overlay_w_ != W_ || overlay_h_ != H_;
-    if (int rc = ensure(&d_overlay_keys_, &cap_overlay_keys_, keys_b)) return rc;
-    overlay_w_ = W_; overlay_h_ = H_;
-    uint8_t* geo = (uint8_t*)d_overlay_geo_;
-    uint8_t* d_atlas = geo + ((gb + 15) & ~(size_t)15);
-    if (gb) TOPO_HIP_TRY(hipMemcpyAsync(geo, glyphs, gb, hipMemcpyHostToDevice, stream_));
-    if (ab) TOPO_HIP_TRY(hipMemcpyAsync(d_atlas, atlas, ab, hipMemcpyHostToDevice, stream_));
-    const uint32_t linear = (format_ == TOPO_FORMAT_RGBA8_UNORM || format_ == TOPO_FORMAT_BGRA8_UNORM) ? 1u : 0u;
-    const uint32_t bgra = (format_ == TOPO_FORMAT_BGRA8_UNORM_SRGB || format_ == TOPO_FORMAT_BGRA8_UNORM) ? 1u : 0u;
-    launch_overlay_glyphs((const GlyphInstance*)geo, n_glyphs, depth, d_atlas, atlas_w, atlas_h, (int32_t)W_, (int32_t)H_, (uint64_t*)d_overlay_keys_, fresh, rgba_dev,
-                          rgba_pitch, linear, bgra, stream_);
+    uint8_t* d_atlas = nullptr;
+    bool fresh = false;
+    if (int rc = overlay_upload(glyphs, (size_t)n_glyphs * sizeof(GlyphInstance), atlas, (size_t)atlas_w * atlas_h, &d_atlas, &fresh)) return rc;
+    launch_overlay_glyphs(d_overlay_geo_.as<const GlyphInstance>(), n_glyphs, depth, d_atlas, atlas_w, atlas_h, (int32_t)W_, (int32_t)H_,
+                          d_overlay_keys_.as<uint64_t>(), fresh, rgba_dev, rgba_pitch, is_linear(format_), is_bgra(format_), stream_);
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));      // glyphs and atlas are only borrowed for the call
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
@@ -1149,16 +1171,9 @@ int TerrainRenderer::overlay_glyphs_device(const void* glyphs, uint32_t n_glyphs
 
 int TerrainRenderer::overlay_glyphs(const void* glyphs, uint32_t n_glyphs, float depth, const uint8_t* atlas, uint32_t atlas_w, uint32_t atlas_h, uint8_t* rgba,
                                     size_t rgba_pitch) {
-    if (!rgba) return fail(TOPO_ERR_INVALID, "null argument");
-    if (rgba_pitch < (size_t)W_ * 4) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
-    if (int rc = bind_device()) return rc;
-    const size_t row = (size_t)W_ * 4;
-    if (int rc = ensure(&d_out_rgba_, &cap_out_rgba_, row * H_)) return rc;
-    TOPO_HIP_TRY(hipMemcpy2DAsync(d_out_rgba_, row, rgba, rgba_pitch, row, H_, hipMemcpyHostToDevice, stream_));
-    if (int rc = overlay_glyphs_device(glyphs, n_glyphs, depth, atlas, atlas_w, atlas_h, (uint8_t*)d_out_rgba_, row)) return rc;
-    TOPO_HIP_TRY(hipMemcpy2DAsync(rgba, rgba_pitch, d_out_rgba_, row, row, H_, hipMemcpyDeviceToHost, stream_));
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-    return TOPO_OK;
+    return overlay_host_image(rgba, rgba_pitch, [&](uint8_t* img, size_t pitch) {
+        return overlay_glyphs_device(glyphs, n_glyphs, depth, atlas, atlas_w, atlas_h, img, pitch);
+    });
 }
 
 // RenderEngine::get_visible_labels over the depth the context already holds on the device.
@@ -1166,9 +1181,9 @@ int TerrainRenderer::visible_peaks_device(const topo_uniforms* view, uint32_t w,
                                           uint32_t n, const float* peaks_dev, uint8_t* visible_dev, uint32_t* xy_dev) {
     if (!view || !depth_dev || (n && (!peaks_dev || !visible_dev || !xy_dev))) return fail(TOPO_ERR_INVALID, "null argument");
     if (int rc = bind_device()) return rc;
-    if (int rc = ensure(&d_proj_, &cap_proj_, 16 * sizeof(float))) return rc;
-    TOPO_HIP_TRY(hipMemcpyAsync(d_proj_, view->camera_proj, 16 * sizeof(float), hipMemcpyHostToDevice, stream_));
-    launch_visible_peaks((const float*)d_proj_, w, h, depth_dev, depth_pitch, n, peaks_dev, visible_dev, xy_dev, stream_);
+    if (int rc = ensure(stream_, d_proj_, 16 * sizeof(float))) return rc;
+    TOPO_HIP_TRY(hipMemcpyAsync(d_proj_.p, view->camera_proj, 16 * sizeof(float), hipMemcpyHostToDevice, stream_));
+    launch_visible_peaks(d_proj_.as<const float>(), w, h, depth_dev, depth_pitch, n, peaks_dev, visible_dev, xy_dev, stream_);
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
 }
@@ -1180,10 +1195,10 @@ int TerrainRenderer::visible_peaks(uint32_t n, const float* peaks, uint8_t* visi
     if (n == 0) return TOPO_OK;
     if (int rc = bind_device()) return rc;
     const size_t in_b = (size_t)n * 12, xy_b = (size_t)n * 8, vis_b = ((size_t)n + 15) & ~(size_t)15;
-    if (int rc = ensure(&d_peaks_, &cap_peaks_, in_b + xy_b + vis_b)) return rc;
-    uint8_t* base = (uint8_t*)d_peaks_;
+    if (int rc = ensure(stream_, d_peaks_, in_b + xy_b + vis_b)) return rc;
+    uint8_t* base = d_peaks_.as<uint8_t>();
     TOPO_HIP_TRY(hipMemcpyAsync(base, peaks, in_b, hipMemcpyHostToDevice, stream_));
-    if (int rc = visible_peaks_device(&uniforms_, W_, H_, (const float*)d_out_depth_, (size_t)W_ * 4, n, (const float*)base,
+    if (int rc = visible_peaks_device(&uniforms_, W_, H_, d_out_depth_.as<const float>(), (size_t)W_ * 4, n, (const float*)base,
                                       base + in_b + xy_b, (uint32_t*)(base + in_b)))
         return rc;
     TOPO_HIP_TRY(hipMemcpyAsync(xy, base + in_b, xy_b, hipMemcpyDeviceToHost, stream_));
@@ -1193,16 +1208,14 @@ int TerrainRenderer::visible_peaks(uint32_t n, const float* peaks, uint8_t* visi
 }
 
 int TerrainRenderer::set_stream(hipStream_t s) {
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (int rc = wait_all()) return rc;
     for (auto& c : ctx_) c.last_stream = nullptr;      // (every frame has finished; the old stream may go away)
     stream_ = s ? s : own_stream_;
     return TOPO_OK;
 }
 
 int TerrainRenderer::synchronize() {
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (int rc = wait_all()) return rc;
     return check_frames();
 }
 
@@ -1213,12 +1226,10 @@ int TerrainRenderer::join_frames() {
 }
 
 int TerrainRenderer::frame_status(uint32_t out[4]) {
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (int rc = wait_all()) return rc;
     // (folds the finished frames into last_status_; an overflow is reported through out[0] here, and stays pending as the error
     // of the next call that waits for frames)
-    for (auto& fc : ctx_)
-        if (!fc.pending && fc.h_status) overflow_pending_ |= fold_frames(fc);
+    overflow_pending_ |= fold_idle();
     if (int rc = horizon_fold_check()) return rc;
     for (int i = 0; i < 4; ++i) out[i] = last_status_[i];
     last_status_[0] = last_status_[1] = last_status_[2] = last_status_[3] = 0;
@@ -1297,8 +1308,7 @@ int TerrainRenderer::get_timings(float out[TOPO_TIMING_SLOTS]) {
 int TerrainRenderer::get_timing_history(uint32_t n_frames, float* out_ms, uint32_t* n_out) {
     *n_out = 0;
     if (!out_ms && n_frames) return fail(TOPO_ERR_INVALID, "null argument");
-    if (int rc = join()) return rc;
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (int rc = wait_all()) return rc;
     struct Ref { uint64_t frame; int ctx, ring; };
     std::vector<Ref> refs;
     for (int ci = 0; ci < kMaxPipeline; ++ci) {
@@ -1325,14 +1335,15 @@ int TerrainRenderer::get_counters(uint32_t out[6]) {
     if (!fc.h_status) return TOPO_OK;
     if (int rc = bind_device()) return rc;
     if (fc.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(fc.last_stream));      // the stream the frame was queued on
-    uint32_t c[16] = {};
-    if (fc.submitted) memcpy(c, fc.h_status + ((fc.submitted - 1) % kStatusRing) * 16, sizeof c);
+    uint32_t c[kStatusWords] = {};
+    if (fc.submitted) memcpy(c, fc.latest_status(), sizeof c);
     if (getenv("TOPO_DEBUG_COUNTERS")) {   // raw queue counters, for kernel experiments
         fprintf(stderr, "[topo] counters:");
-        for (int i = 0; i < 16; ++i) fprintf(stderr, " %u", c[i]);
+        for (uint32_t i = 0; i < kStatusWords; ++i) fprintf(stderr, " %u", c[i]);
         fprintf(stderr, "\n");
     }
-    out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3]; out[4] = c[4]; out[5] = c[5];
+    static_assert(kCtrWork == 0 && kCtrFarSurvived == 5, "topo_get_counters hands out words kCtrWork .. kCtrFarSurvived");
+    for (uint32_t i = kCtrWork; i <= kCtrFarSurvived; ++i) out[i] = c[i];
     return TOPO_OK;
 }
 
@@ -1371,10 +1382,9 @@ int geotiff_transform(const TiffInfo& ti, float rp[2], float mp[2], float ps[2])
     return TOPO_OK;
 }
 
-// Decodes the first image of the file into a fresh device raster (caller frees *d_heights with hipFree).
-int TerrainRenderer::geotiff_to_device(const uint8_t* bytes, size_t n, float** d_heights, uint32_t* w, uint32_t* h, float rp[2],
+// Decodes the first image of the file into a device raster, `heights` (an empty buffer of the caller's).
+int TerrainRenderer::geotiff_to_device(const uint8_t* bytes, size_t n, DeviceBuffer& heights, uint32_t* w, uint32_t* h, float rp[2],
                                        float mp[2], float ps[2]) {
-    *d_heights = nullptr;
     TiffInfo ti;
     std::string e;
     if (int rc = tiff_parse(bytes, n, ti, e)) return fail(rc, "GeoTIFF: " + e);
@@ -1412,27 +1422,17 @@ int TerrainRenderer::geotiff_to_device(const uint8_t* bytes, size_t n, float** d
         for (size_t t = 0; t < n_thr; ++t)
             if (rcs[t]) return fail(rcs[t], "GeoTIFF: " + errs[t]);
     }
-    uint8_t* d_bytes = nullptr;
-    TiffSegDev* d_segs = nullptr;
-    uint32_t* d_rows = nullptr;
-    float* d_out = nullptr;
-    hipError_t he = hipMalloc((void**)&d_bytes, total ? total : 4);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_segs, segs.size() * sizeof(TiffSegDev));
-    if (he == hipSuccess) he = hipMalloc((void**)&d_rows, row_seg.size() * sizeof(uint32_t));
-    if (he == hipSuccess) he = hipMalloc((void**)&d_out, (size_t)ti.width * ti.height * sizeof(float));
-    if (he == hipSuccess) he = hipMemcpyAsync(d_bytes, staged.data(), total, hipMemcpyHostToDevice, stream_);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(TiffSegDev), hipMemcpyHostToDevice, stream_);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_rows, row_seg.data(), row_seg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_);
-    if (he == hipSuccess) {
-        launch_tiff_rows(d_bytes, d_segs, d_rows, (uint32_t)row_seg.size(), d_out, ti.width, ti.height, ti.predictor, ti.big_endian, stream_);
-        he = hipStreamSynchronize(stream_);          // the staging vectors are only borrowed for the call
-    }
-    (void)hipFree(d_bytes); (void)hipFree(d_segs); (void)hipFree(d_rows);
-    if (he != hipSuccess) {
-        (void)hipFree(d_out);
-        return hip_fail(he, "GeoTIFF decode");
-    }
-    *d_heights = d_out;
+    DeviceBuffer d_bytes, d_segs, d_rows;
+    if (int rc = ensure(stream_, d_bytes, total ? total : 4)) return rc;
+    if (int rc = ensure(stream_, d_segs, segs.size() * sizeof(TiffSegDev))) return rc;
+    if (int rc = ensure(stream_, d_rows, row_seg.size() * sizeof(uint32_t))) return rc;
+    if (int rc = ensure(stream_, heights, (size_t)ti.width * ti.height * sizeof(float))) return rc;
+    TOPO_HIP_TRY(hipMemcpyAsync(d_bytes.p, staged.data(), total, hipMemcpyHostToDevice, stream_));
+    TOPO_HIP_TRY(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(TiffSegDev), hipMemcpyHostToDevice, stream_));
+    TOPO_HIP_TRY(hipMemcpyAsync(d_rows.p, row_seg.data(), row_seg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    launch_tiff_rows(d_bytes.as<uint8_t>(), d_segs.as<const TiffSegDev>(), d_rows.as<const uint32_t>(), (uint32_t)row_seg.size(), heights.as<float>(), ti.width,
+                     ti.height, ti.predictor, ti.big_endian, stream_);
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));          // the staging vectors are only borrowed for the call
     *w = ti.width;
     *h = ti.height;
     return TOPO_OK;
@@ -1440,284 +1440,49 @@ int TerrainRenderer::geotiff_to_device(const uint8_t* bytes, size_t n, float** d
 
 int TerrainRenderer::geotiff_decode(const uint8_t* bytes, size_t n, float* heights_out, size_t capacity) {
     if (!bytes || !heights_out) return fail(TOPO_ERR_INVALID, "null argument");
-    float* d = nullptr;
+    DeviceBuffer d;
     uint32_t w = 0, h = 0;
     float rp[2], mp[2], ps[2];
-    if (int rc = geotiff_to_device(bytes, n, &d, &w, &h, rp, mp, ps)) return rc;
-    int rc = TOPO_OK;
-    if ((size_t)w * h > capacity) rc = fail(TOPO_ERR_CAPACITY, "heights_out is smaller than the image");
-    else if (hipMemcpy(heights_out, d, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(TOPO_ERR_HIP, "copy of the decoded raster failed");
-    (void)hipFree(d);
-    return rc;
+    if (int rc = geotiff_to_device(bytes, n, d, &w, &h, rp, mp, ps)) return rc;
+    if ((size_t)w * h > capacity) return fail(TOPO_ERR_CAPACITY, "heights_out is smaller than the image");
+    if (hipMemcpy(heights_out, d.p, (size_t)w * h * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return fail(TOPO_ERR_HIP, "copy of the decoded raster failed");
+    return TOPO_OK;
 }
 
 int TerrainRenderer::add_terrain_geotiff(int32_t lat, int32_t lon, const uint8_t* bytes, size_t n) {
     if (!bytes) return fail(TOPO_ERR_INVALID, "null argument");
-    float* d = nullptr;
+    DeviceBuffer d;
     uint32_t w = 0, h = 0;
     float rp[2], mp[2], ps[2];
-    if (int rc = geotiff_to_device(bytes, n, &d, &w, &h, rp, mp, ps)) return rc;
-    const int rc = add_terrain(lat, lon, d, true, w, h, rp, mp, ps);      // copies device-to-device
-    (void)hipFree(d);
-    return rc;
+    if (int rc = geotiff_to_device(bytes, n, d, &w, &h, rp, mp, ps)) return rc;
+    return add_terrain(lat, lon, d.as<const float>(), true, w, h, rp, mp, ps);      // copies device-to-device
 }
 
 int TerrainRenderer::probe_sincos(const float* x, float* s, float* c, size_t n) {
     if (int rc = bind_device()) return rc;
-    float *dx = nullptr, *ds = nullptr, *dc = nullptr;
-    TOPO_HIP_TRY(hipMalloc((void**)&dx, n * 4));
-    TOPO_HIP_TRY(hipMalloc((void**)&ds, n * 4));
-    TOPO_HIP_TRY(hipMalloc((void**)&dc, n * 4));
-    TOPO_HIP_TRY(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-    launch_probe_sincos(dx, ds, dc, n, stream_);
+    DeviceBuffer dx, ds, dc;
+    for (DeviceBuffer* b : {&dx, &ds, &dc})
+        if (int rc = ensure(stream_, *b, n * 4)) return rc;
+    TOPO_HIP_TRY(hipMemcpy(dx.p, x, n * 4, hipMemcpyHostToDevice));
+    launch_probe_sincos(dx.as<const float>(), ds.as<float>(), dc.as<float>(), n, stream_);
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-    TOPO_HIP_TRY(hipMemcpy(s, ds, n * 4, hipMemcpyDeviceToHost));
-    TOPO_HIP_TRY(hipMemcpy(c, dc, n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(dx); (void)hipFree(ds); (void)hipFree(dc);
+    TOPO_HIP_TRY(hipMemcpy(s, ds.p, n * 4, hipMemcpyDeviceToHost));
+    TOPO_HIP_TRY(hipMemcpy(c, dc.p, n * 4, hipMemcpyDeviceToHost));
     return TOPO_OK;
 }
 
 int TerrainRenderer::probe_div(int32_t kind, const float* x, const float* y, float* out, size_t n) {
     if (kind < 0 || kind > 8 || !x || !y || !out) return fail(TOPO_ERR_INVALID, "probe_div: bad argument");
     if (int rc = bind_device()) return rc;
-    float *dx = nullptr, *dy = nullptr, *dq = nullptr;
-    TOPO_HIP_TRY(hipMalloc((void**)&dx, n * 4));
-    TOPO_HIP_TRY(hipMalloc((void**)&dy, n * 4));
-    TOPO_HIP_TRY(hipMalloc((void**)&dq, n * 4));
-    TOPO_HIP_TRY(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-    TOPO_HIP_TRY(hipMemcpy(dy, y, n * 4, hipMemcpyHostToDevice));
-    launch_probe_div(kind, dx, dy, dq, n, stream_);
+    DeviceBuffer dx, dy, dq;
+    for (DeviceBuffer* b : {&dx, &dy, &dq})
+        if (int rc = ensure(stream_, *b, n * 4)) return rc;
+    TOPO_HIP_TRY(hipMemcpy(dx.p, x, n * 4, hipMemcpyHostToDevice));
+    TOPO_HIP_TRY(hipMemcpy(dy.p, y, n * 4, hipMemcpyHostToDevice));
+    launch_probe_div(kind, dx.as<const float>(), dy.as<const float>(), dq.as<float>(), n, stream_);
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-    TOPO_HIP_TRY(hipMemcpy(out, dq, n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dq);
+    TOPO_HIP_TRY(hipMemcpy(out, dq.p, n * 4, hipMemcpyDeviceToHost));
     return TOPO_OK;
-}
-
-// =========================================================================================================
-// Host-side CPU math of the reference (glam 0.31.0, Cargo.lock:1272-1273), restated in f32.
-// =========================================================================================================
-namespace {
-
-inline float rs_to_radians(float d) { return d * 0.017453292519943295f; }   // f32::to_radians
-
-struct V3 { float x, y, z; };
-inline float vdot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-inline V3 vcross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-inline V3 vnormalize(V3 v) {   // Vec3::normalize: self * length_recip()
-    const float r = 1.0f / sqrtf(vdot(v, v));
-    return {v.x * r, v.y * r, v.z * r};
-}
-
-// Mat3::from_euler(EulerRot::XYZEx, 0, b, c) = Rz(c) * Ry(b); with a = 0 every entry is one product.
-void euler_xyz_ex_a0(float b, float c, float m[9] /*column-major*/) {
-    const float si = sinf(0.0f), ci = cosf(0.0f);
-    const float sj = sinf(b), cj = cosf(b), sh = sinf(c), ch = cosf(c);
-    const float cc = ci * ch, cs = ci * sh, sc = si * ch, ss = si * sh;
-    m[0] = cj * ch;       m[1] = cj * sh;       m[2] = -sj;
-    m[3] = sj * sc - cs;  m[4] = sj * ss + cc;  m[5] = cj * si;
-    m[6] = sj * cc + ss;  m[7] = sj * cs - sc;  m[8] = cj * ci;
-}
-
-}  // namespace
-
-// TerrainUniforms::new's normal_to_world_rot (render/data.rs:125-133)
-void terrain_rotation(float model_lon_deg, float model_lat_deg, float rot[9]) {
-    euler_xyz_ex_a0(rs_to_radians(90.0f - model_lat_deg), rs_to_radians(model_lon_deg), rot);
-}
-
-// geometry::transform (render/geometry.rs:12-20)
-void geometry_transform(float h, float lon_deg, float lat_deg, float out[3]) {
-    const float r = kR0 + h;
-    const float lon = rs_to_radians(lon_deg), lat = rs_to_radians(lat_deg);
-    out[0] = r * cosf(lat) * cosf(lon);
-    out[1] = r * cosf(lat) * sinf(lon);
-    out[2] = r * sinf(lat);
-}
-
-// topo_pixel_angles, in f64: the ray through pixel-space point (x, y) is the line between the points the inverse of camera_proj maps
-// it to on the near (NDC z 0) and the far (z 1) plane -- no f32 eye enters the direction -- seen in the local east / north / up
-// frame at the eye (up = the eye's geocentric radius; geometry_transform's axes: x to (0 N, 0 E), z to the north pole).
-void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n, const float* xy, double* az_el) {
-    const float* f = view->camera_proj;      // column-major: element (row r, column c) at f[4 c + r]
-    double m[4][4], inv[4][8];
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) m[r][c] = f[4 * c + r];
-    for (int r = 0; r < 4; ++r)      // Gauss-Jordan with partial pivoting on [m | I]
-        for (int c = 0; c < 8; ++c) inv[r][c] = c < 4 ? m[r][c] : (c - 4 == r ? 1.0 : 0.0);
-    for (int c = 0; c < 4; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 4; ++r)
-            if (std::fabs(inv[r][c]) > std::fabs(inv[piv][c])) piv = r;
-        for (int k = 0; k < 8; ++k) std::swap(inv[c][k], inv[piv][k]);
-        const double d = inv[c][c];
-        for (int k = 0; k < 8; ++k) inv[c][k] /= d;
-        for (int r = 0; r < 4; ++r)
-            if (r != c) {
-                const double s = inv[r][c];
-                for (int k = 0; k < 8; ++k) inv[r][k] -= s * inv[c][k];
-            }
-    }
-    auto unproject = [&](double nx, double ny, double nz, double out[3]) {
-        double p[4];
-        for (int r = 0; r < 4; ++r) p[r] = inv[r][4] * nx + inv[r][5] * ny + inv[r][6] * nz + inv[r][7];
-        for (int k = 0; k < 3; ++k) out[k] = p[k] / p[3];
-    };
-    const double ex = view->camera_pos[0], ey = view->camera_pos[1], ez = view->camera_pos[2];
-    const double el = std::sqrt(ex * ex + ey * ey + ez * ez);
-    const double up[3] = {ex / el, ey / el, ez / el};
-    const double eh = std::hypot(up[0], up[1]);
-    const double east[3] = {eh > 0.0 ? -up[1] / eh : 0.0, eh > 0.0 ? up[0] / eh : 1.0, 0.0};      // z x up (at a pole: +y)
-    const double north[3] = {up[1] * east[2] - up[2] * east[1], up[2] * east[0] - up[0] * east[2], up[0] * east[1] - up[1] * east[0]};
-    const double kDeg = 180.0 / 3.14159265358979323846;
-    for (uint32_t i = 0; i < n; ++i) {
-        const double nx = 2.0 * xy[2 * i] / w - 1.0, ny = 1.0 - 2.0 * xy[2 * i + 1] / h;
-        double p0[3], p1[3];
-        unproject(nx, ny, 0.0, p0);
-        unproject(nx, ny, 1.0, p1);
-        const double d[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
-        const double de = d[0] * east[0] + d[1] * east[1] + d[2] * east[2];
-        const double dn = d[0] * north[0] + d[1] * north[1] + d[2] * north[2];
-        const double du = d[0] * up[0] + d[1] * up[1] + d[2] * up[2];
-        double az = std::atan2(de, dn) * kDeg;
-        if (az < 0.0) az += 360.0;
-        az_el[2 * i] = az;
-        az_el[2 * i + 1] = std::atan2(du, std::hypot(de, dn)) * kDeg;
-    }
-}
-
-// Uniforms::new (render/data.rs:44-58) over Camera::{up,direction,get_view,build_view_proj_matrix}
-// (data/camera.rs:97-128) and LightAngle::to_vec3 (:44-53).
-void camera_uniforms(const float eye_in[3], float yaw, float pitch, float fov_y, float width, float height,
-                     float sun_theta_deg, float sun_phi_deg, int32_t view_mode, topo_uniforms* out) {
-    memset(out, 0, sizeof *out);
-    const V3 eye = {eye_in[0], eye_in[1], eye_in[2]};
-    const V3 up = vnormalize(eye);
-    // Quat::from_rotation_arc(-Y, up)
-    const V3 from = {0.0f, -1.0f, 0.0f};
-    float qx, qy, qz, qw;
-    const float d = vdot(from, up);
-    const float one_minus_eps = 1.0f - 2.0f * 1.1920929e-7f;
-    if (d > one_minus_eps) {
-        qx = qy = qz = 0.0f; qw = 1.0f;
-    } else if (d < -one_minus_eps) {   // any_orthonormal_vector(from), half-turn
-        const float sign = copysignf(1.0f, from.z);
-        const float a = -1.0f / (sign + from.z);
-        const float b = from.x * from.y * a;
-        const V3 axis = {b, sign + from.y * from.y * a, -from.y};
-        const float s = sinf(3.14159265358979323846f * 0.5f), c = cosf(3.14159265358979323846f * 0.5f);
-        qx = axis.x * s; qy = axis.y * s; qz = axis.z * s; qw = c;
-    } else {
-        const V3 c = vcross(from, up);
-        const float w = 1.0f + d;
-        const float l2 = (c.x * c.x + c.z * c.z) + (c.y * c.y + w * w);   // SSE2 dot4 order
-        const float r = 1.0f / sqrtf(l2);
-        qx = c.x * r; qy = c.y * r; qz = c.z * r; qw = w * r;
-    }
-    // direction = rot * (cos yaw cos pitch, sin pitch, sin yaw cos pitch)   (Quat * Vec3)
-    const V3 v = {cosf(yaw) * cosf(pitch), sinf(pitch), sinf(yaw) * cosf(pitch)};
-    const V3 b = {qx, qy, qz};
-    const float b2 = vdot(b, b);
-    const float k0 = qw * qw - b2, k1 = vdot(v, b) * 2.0f, k2 = qw * 2.0f;
-    const V3 bxv = vcross(b, v);
-    const V3 f = {(v.x * k0 + b.x * k1) + bxv.x * k2, (v.y * k0 + b.y * k1) + bxv.y * k2, (v.z * k0 + b.z * k1) + bxv.z * k2};
-    // Mat4::look_to_rh(eye, f, up)
-    const V3 s = vnormalize(vcross(f, up));
-    const V3 u = vcross(s, f);
-    const float view[16] = {s.x, u.x, -f.x, 0.0f, s.y, u.y, -f.y, 0.0f, s.z, u.z, -f.z, 0.0f,
-                            -vdot(eye, s), -vdot(eye, u), vdot(eye, f), 1.0f};
-    // Mat4::perspective_rh(fov_y, aspect, NEAR, FAR)
-    const float aspect = width / height;
-    const float sf = sinf(0.5f * fov_y), cf = cosf(0.5f * fov_y);
-    const float hh = cf / sf, ww = hh / aspect, r = kFar / (kNear - kFar);
-    const float proj[16] = {ww, 0, 0, 0, 0, hh, 0, 0, 0, 0, r, -1.0f, 0, 0, r * kNear, 0};
-    for (int c = 0; c < 4; ++c)        // proj * view, column by column: ((c0*x + c1*y) + c2*z) + c3*w
-        for (int rr = 0; rr < 4; ++rr) {
-            float t = proj[rr] * view[c * 4 + 0];
-            t = t + proj[4 + rr] * view[c * 4 + 1];
-            t = t + proj[8 + rr] * view[c * 4 + 2];
-            t = t + proj[12 + rr] * view[c * 4 + 3];
-            out->camera_proj[c * 4 + rr] = t;
-        }
-    // normal_proj = view.inverse().transpose(): no shader reads it (render_shader.wgsl:5); filled with the
-    // rotation block of the view, which is what it equals for a rigid transform up to rounding.
-    for (int c = 0; c < 3; ++c)
-        for (int rr = 0; rr < 3; ++rr) out->normal_proj[c * 4 + rr] = view[c * 4 + rr];
-    out->normal_proj[15] = 1.0f;
-    out->camera_pos[0] = eye.x; out->camera_pos[1] = eye.y; out->camera_pos[2] = eye.z; out->camera_pos[3] = 0.0f;
-    float m3[9];
-    euler_xyz_ex_a0(rs_to_radians(90.0f - sun_phi_deg), rs_to_radians(sun_theta_deg), m3);
-    out->sun_direction[0] = m3[6]; out->sun_direction[1] = m3[7]; out->sun_direction[2] = m3[8];   // * Vec3::Z
-    out->view_mode = view_mode;
-}
-
-// The cameras of a 360-degree strip of n_sectors perspective sectors: sector k looks at yaw0 - k * 360/n
-// degrees with the vertical field of view that makes every sector 360/n degrees wide.
-void panorama_uniforms(const float eye[3], float yaw0, float pitch, uint32_t sector_w, uint32_t sector_h, float sun_theta_deg, float sun_phi_deg,
-                       int32_t view_mode, uint32_t n_sectors, topo_uniforms* out) {
-    const double kPi = 3.14159265358979323846;
-    const double fov = 2.0 * atan(tan(kPi / (double)n_sectors) * (double)sector_h / (double)sector_w);
-    for (uint32_t k = 0; k < n_sectors; ++k)
-        camera_uniforms(eye, (float)((double)yaw0 - (double)k * (2.0 * kPi / (double)n_sectors)), pitch, (float)fov, (float)sector_w,
-                        (float)sector_h, sun_theta_deg, sun_phi_deg, view_mode, out + k);
-}
-
-// UiController::get_locations_range (control/ui_controller.rs:61-83), f32 as in the reference.
-uint32_t locations_range(float latitude, float longitude, float range_dist, int32_t* out, uint32_t cap) {
-    auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-    (void)clampi;
-    // center.0 = (floor(lat) as i32).min(-90).max(89): always 89, as written
-    int c_lat = (int)floorf(latitude);
-    c_lat = c_lat < -90 ? c_lat : -90;
-    c_lat = c_lat > 89 ? c_lat : 89;
-    const int c_lon = ((int)(floorf(longitude) + 540.0f)) % 360 - 180;
-    const float lat_cos = cosf(rs_to_radians(latitude));
-    const float arc_factor = 0.5f * range_dist / kR0;
-    const float arc_factor_sin = sinf(arc_factor);
-    const float afs_sq = arc_factor_sin * arc_factor_sin;
-    const float R2D = 57.29577951308232f;                       // f32::to_degrees: self * (180 / PI)
-    const float dlon = acosf(1.0f - afs_sq / lat_cos / lat_cos) * R2D;
-    const float dlat = acosf(1.0f - afs_sq) * R2D;
-    int lat_start = (int)floorf(latitude - dlat);
-    lat_start = lat_start > -90 ? lat_start : -90;
-    int lat_end = (int)floorf(latitude + dlat);
-    lat_end = lat_end < 89 ? lat_end : 89;
-    const int lon_start = (int)floorf(longitude - dlon), lon_end = (int)floorf(longitude + dlon);
-    struct Item { int lat, lon, k0, k1; };
-    std::vector<Item> v;
-    for (int la = lat_start; la <= lat_end; ++la)
-        for (int lo = lon_start; lo <= lon_end; ++lo) v.push_back({la, lo, std::abs(la - c_lat), std::abs(lo - c_lon)});
-    std::stable_sort(v.begin(), v.end(), [](const Item& a, const Item& b) { return a.k0 != b.k0 ? a.k0 < b.k0 : a.k1 < b.k1; });
-    uint32_t n = 0;
-    for (const Item& it : v) {
-        if (n < cap && out) { out[2 * n] = it.lat; out[2 * n + 1] = (it.lon + 540) % 360 - 180; }
-        ++n;
-    }
-    return n;
-}
-
-// UiController::change_location (control/ui_controller.rs:23-59) as a plan: the tiles of get_locations_range(location,
-// range) that are not loaded yet are to be requested, the loaded ones outside it are to be unloaded.  The reference walks
-// HashSets (order unspecified); here both lists come out in a defined order: `request` in get_locations_range's sorted
-// order, `unload` in the order of `loaded`.
-void change_location_plan(float latitude, float longitude, float range_dist, const int32_t* loaded, uint32_t n_loaded,
-                          std::vector<std::pair<int32_t, int32_t>>& unload, std::vector<std::pair<int32_t, int32_t>>& request) {
-    const uint32_t n = locations_range(latitude, longitude, range_dist, nullptr, 0);
-    std::vector<int32_t> want(2 * (size_t)n);
-    locations_range(latitude, longitude, range_dist, want.data(), n);
-    std::vector<bool> have(n, false);
-    unload.clear();
-    request.clear();
-    for (uint32_t i = 0; i < n_loaded; ++i) {
-        bool in_new = false;
-        for (uint32_t k = 0; k < n; ++k)
-            if (want[2 * k] == loaded[2 * i] && want[2 * k + 1] == loaded[2 * i + 1]) { in_new = true; have[k] = true; }
-        if (!in_new) unload.emplace_back(loaded[2 * i], loaded[2 * i + 1]);
-    }
-    for (uint32_t k = 0; k < n; ++k) {
-        bool dup = false;       // (the range wraps at 180 degrees: a location can appear twice; a HashSet holds it once)
-        for (uint32_t j = 0; j < k && !dup; ++j) dup = want[2 * j] == want[2 * k] && want[2 * j + 1] == want[2 * k + 1];
-        if (!have[k] && !dup) request.emplace_back(want[2 * k], want[2 * k + 1]);
-    }
 }
 
 int TerrainRenderer::change_location(float latitude, float longitude, float range_dist, std::vector<std::pair<int32_t, int32_t>>& request,
@@ -1730,41 +1495,6 @@ int TerrainRenderer::change_location(float latitude, float longitude, float rang
         if (int rc = unload_terrain(u.first, u.second)) return rc;
     if (n_unloaded) *n_unloaded = (uint32_t)unload.size();
     return TOPO_OK;
-}
-
-// Synthetic COP90-shaped heights: 5-octave value-noise fBm over global texel coordinates with an integer
-// hash (same definition as topo-renderer_amd/synth.py; f32 ops in the same order).
-namespace {
-inline float synth_hash(int64_t ix, int64_t iy, uint32_t seed) {
-    uint32_t h = ((uint32_t)ix * 0x9E3779B1u) ^ ((uint32_t)iy * 0x85EBCA77u) ^ (seed * 0xC2B2AE3Du);
-    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
-    return (float)(h >> 8) * (1.0f / 16777216.0f);
-}
-}  // namespace
-
-void synth_tile(int32_t lat, int32_t lon, uint32_t w, uint32_t h, uint32_t seed, float* out) {
-    static const int wl[5] = {512, 256, 128, 64, 32};
-    static const float amp[5] = {1.0f, 0.5f, 0.25f, 0.125f, 0.0625f};
-    const float norm = (float)(3000.0 / 1.9375);
-    for (uint32_t y = 0; y < h; ++y) {
-        const int64_t gy = (int64_t)(89 - lat) * h + y;
-        for (uint32_t x = 0; x < w; ++x) {
-            const int64_t gx = ((int64_t)lon + 180) * w + x;
-            float acc = 0.0f;
-            for (int o = 0; o < 5; ++o) {
-                const int64_t cx = gx / wl[o], cy = gy / wl[o];
-                const float fx = (float)(gx % wl[o]) / (float)wl[o], fy = (float)(gy % wl[o]) / (float)wl[o];
-                const float ux = fx * fx * (3.0f - 2.0f * fx), uy = fy * fy * (3.0f - 2.0f * fy);
-                const uint32_t s = seed + (uint32_t)o;
-                const float v00 = synth_hash(cx, cy, s), v10 = synth_hash(cx + 1, cy, s);
-                const float v01 = synth_hash(cx, cy + 1, s), v11 = synth_hash(cx + 1, cy + 1, s);
-                const float a = v00 + ux * (v10 - v00), b = v01 + ux * (v11 - v01);
-                const float v = a + uy * (b - a);
-                acc = acc + amp[o] * v;
-            }
-            out[(size_t)y * w + x] = acc * norm;
-        }
-    }
 }
 
 }  // namespace topo

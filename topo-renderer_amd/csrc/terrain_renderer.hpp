@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/topo_hip.h"
+#include "host_math.hpp"
 #include "topo_kernels.h"
 
 namespace topo {
@@ -28,6 +29,29 @@ struct Comm;                                  // panorama.cpp: an RCCL communica
 using GeoKey = std::tuple<int, int, int, int>;
 inline GeoKey geo_key(int lat, int lon) {
     return GeoKey(lat < 0 ? -lat : lat, lat > 0 ? 1 : 0, lon < 0 ? -lon : lon, lon > 0 ? 1 : 0);
+}
+
+#define TOPO_HIP_TRY(expr)                                   \
+    do {                                                     \
+        hipError_t e_ = (expr);                              \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr);    \
+    } while (0)
+
+// A block of device memory that only grows (TerrainRenderer::ensure) and goes with its owner.  Owners bind the device and wait
+// for their streams in their destructor's body; the blocks are freed behind it, as members.
+struct DeviceBuffer {
+    void* p = nullptr;
+    size_t cap = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// Images of `rows` rows at the given pitches (bytes), one behind the other.
+inline OutputParams image_output(uint8_t* rgba, size_t rgba_pitch, float* depth, size_t depth_pitch, uint32_t rows) {
+    return OutputParams{rgba, rgba_pitch * rows, rgba_pitch, depth, depth_pitch * rows, depth_pitch};
 }
 
 struct Tile {          // RenderBuffer (render_buffer.rs:23-31) minus the wgpu plumbing
@@ -88,7 +112,7 @@ class TerrainRenderer {
     int set_timing_slots(uint32_t mask);
     int read_normals(int32_t lat, int32_t lon, uint8_t* out);
     int read_tile_tables(int32_t lat, int32_t lon, float* minmax_out, float* trig_out, double* bounds_out, uint32_t* n_blocks_out);      // test hook
-    int geotiff_to_device(const uint8_t* bytes, size_t n, float** d_heights, uint32_t* w, uint32_t* h, float rp[2], float mp[2], float ps[2]);
+    int geotiff_to_device(const uint8_t* bytes, size_t n, DeviceBuffer& heights, uint32_t* w, uint32_t* h, float rp[2], float mp[2], float ps[2]);
     int geotiff_decode(const uint8_t* bytes, size_t n, float* heights_out, size_t capacity);
     int add_terrain_geotiff(int32_t lat, int32_t lon, const uint8_t* bytes, size_t n);
     int probe_sincos(const float* x, float* s, float* c, size_t n);
@@ -115,7 +139,9 @@ class TerrainRenderer {
     int fail(int code, const std::string& msg);
     int hip_fail(hipError_t e, const char* what);
     int bind_device();
-    int ensure(void** p, size_t* cap, size_t need);
+    int ensure(hipStream_t s, DeviceBuffer& b, size_t need);      // grows b to `need` bytes; s: the stream to wait for before the old block goes
+    int wait_all();                                               // join + stream_
+    void free_tile(Tile& t);
     void collect_jobs(const Tile& nt, const std::map<GeoKey, uint32_t>& rank, std::vector<EdgeJob>& edges,
                       std::vector<CornerJob>& corners);   // the seam/corner orchestration of add_terrain
     int run_seam_jobs(const std::vector<EdgeJob>& edges, const std::vector<CornerJob>& corners);
@@ -125,6 +151,8 @@ class TerrainRenderer {
     std::map<GeoKey, uint32_t> ranks() const;
     Tile* find(int lat, int lon);
     int upload_tile_table();
+    int overlay_upload(const void* a, size_t a_bytes, const void* b, size_t b_bytes, uint8_t** b_dev, bool* keys_fresh);
+    template <class Draw> int overlay_host_image(uint8_t* rgba, size_t rgba_pitch, Draw draw);
     int alloc_mask(Tile& t);
     size_t mask_bytes() const { return (((size_t)(tile_w_ - 1) * (tile_h_ - 1) + 31) / 32) * 4; }
 
@@ -149,6 +177,7 @@ class TerrainRenderer {
     hipStream_t own_stream_ = nullptr, stream_ = nullptr;
     static constexpr int kNumEvents = 9;
     static constexpr int kEvRing = 32;
+    static constexpr uint64_t kStatusRing = 64;
     uint64_t frame_seq_ = 0;          // frames submitted by this renderer
     hipEvent_t load_ev_[3] = {};      // recompute_normals: start, end, between the tables and the normals
     bool load_timed_ = false;
@@ -171,30 +200,23 @@ class TerrainRenderer {
         hipStream_t last_stream = nullptr;
         // a frame queued with pipeline depth > 1 that join() has not waited for yet (at depth 1 every wait synchronizes stream_)
         bool timed = false, pending = false;
-        // pinned ring of the last kStatusRing frames' 16 counter words, each stored by its frame's k_resolve (the bounds-checking build: copied out behind it);
+        // pinned ring of the last kStatusRing frames' kStatusWords counter words, each stored by its frame's k_resolve (the bounds-checking build: copied out behind it);
         // frames [checked, submitted) have not been looked at by check_frames yet
         uint32_t* h_status = nullptr;
         uint64_t submitted = 0, checked = 0;
-        void* d_vis = nullptr;      size_t cap_vis = 0;
-        void* d_dirty = nullptr;    size_t cap_dirty = 0;   // one mark per 64 visibility keys (topo_kernels.hip: struct Vis)
-        void* d_work = nullptr;     size_t cap_work = 0;
-        void* d_work2 = nullptr;    size_t cap_work2 = 0;
-        void* d_far = nullptr;      size_t cap_far = 0;
-        void* d_big = nullptr;      size_t cap_big = 0;
-        void* d_rare = nullptr;     size_t cap_rare = 0;
-        void* d_counters = nullptr; size_t cap_counters = 0;
-        void* d_pre_rgba = nullptr; size_t cap_pre_rgba = 0;      // the pixelise branch: the render-target image k_post_pixelize samples,
-        void* d_pre_depth = nullptr; size_t cap_pre_depth = 0;    // and a depth image when the caller wants none
+        uint32_t* status_words(uint64_t frame) const { return h_status + (frame % kStatusRing) * kStatusWords; }
+        const uint32_t* latest_status() const { return status_words(submitted - 1); }
+        DeviceBuffer d_vis, d_dirty;      // d_dirty: one mark per 64 visibility keys (topo_kernels.hip: struct Vis)
+        DeviceBuffer d_work, d_work2, d_far, d_big, d_rare, d_counters;
+        DeviceBuffer d_pre_rgba, d_pre_depth;      // the pixelise branch: the render-target image k_post_pixelize samples, and a depth image when the caller wants none
         // the context's latest submission as the horizon query reads it (its keys and marks are d_vis / d_dirty until the next one)
         struct Submission {
-            uint32_t n_views = 0, W = 0, H = 0, n_tiles = 0, tris_per_tile = 0, hm1 = 0;
-            FastDiv div_tris{}, div_hm1{};
-            const uint32_t* counters = nullptr;     // its counter set (the sets alternate from frame to frame)
+            uint32_t n_views = 0;
             uint64_t tile_gen = 0;                  // tile_gen_ when it was rendered
+            HorizonParams query{};                  // a query's parameters, as far as the submission sets them (its keys, marks, counter set, shape)
         } sub;
     };
     static constexpr int kMaxPipeline = 4;
-    static constexpr uint64_t kStatusRing = 64;
     FrameCtx ctx_[kMaxPipeline];
     int pipeline_depth_ = 1, next_ctx_ = 0, last_ctx_ = 0;
     int init_ctx(FrameCtx& c, bool own_stream);
@@ -202,24 +224,28 @@ class TerrainRenderer {
     uint32_t last_status_[4] = {};             // status word + bounds record of the last frame looked at
     bool fold_frames(FrameCtx& c, uint64_t end);   // folds the finished, unchecked frames [checked, end) of c into last_status_; true if one overflowed
     bool fold_frames(FrameCtx& c) { return fold_frames(c, c.submitted); }
+    bool fold_idle();                              // fold_frames over every context no frame is in flight on
+    bool fold_latest(FrameCtx& c, bool retry);     // c's latest frame is the caller's own: folds c, true if that frame overflowed
+    void record_bounds(const uint32_t* words);
     bool overflow_pending_ = false;
-    int ensure_on(hipStream_t s, void** p, size_t* cap, size_t need);
     // slots: the frame resolved in several launches (k_resolve over block ranges), after_slot(i, stream) called behind each --
     // null / 0: one launch over the whole frame
     struct ResolveSlot { uint32_t block_first, block_count; };
     int render_frame(FrameCtx& c, hipStream_t s, uint32_t n, const topo_uniforms* views, uint32_t w, uint32_t h, const OutputParams& out,
                      const ResolveSlot* slots = nullptr, uint32_t n_slots = 0, const std::function<int(uint32_t, hipStream_t)>* after_slot = nullptr);
+    // render_frame's steps, in its order
+    int grow_frame_buffers(FrameCtx& c, hipStream_t s, uint32_t n, uint32_t w, uint32_t h, FrameParams& p);
+    int stage_views(FrameCtx& c, hipStream_t s, const topo_uniforms* views, FrameParams& p, ViewPack& pack, bool* pack_in_cull);
+    void fill_params(FrameCtx& c, FrameParams& p);
+    int queue_frame(FrameCtx& c, hipStream_t s, FrameParams& p, const ViewPack* pack_in_cull, bool far_phase, const OutputParams& out, const ResolveSlot* slots,
+                    uint32_t n_slots, const std::function<int(uint32_t, hipStream_t)>* after_slot);
+    void record_submission(FrameCtx& c, const FrameParams& p);
     int frame_durations(FrameCtx& c, int ring, float out[7]);
 
-    // grow-only device buffers
-    void* d_tiles_ = nullptr;    size_t cap_tiles_ = 0;
-    void* d_views_ = nullptr;    size_t cap_views_ = 0;
-    void* d_edge_jobs_ = nullptr;   size_t cap_edge_jobs_ = 0;
-    void* d_corner_jobs_ = nullptr; size_t cap_corner_jobs_ = 0;
-    void* d_out_rgba_ = nullptr; size_t cap_out_rgba_ = 0;
-    void* d_out_depth_ = nullptr; size_t cap_out_depth_ = 0;
+    DeviceBuffer d_tiles_, d_views_, d_edge_jobs_, d_corner_jobs_, d_out_rgba_, d_out_depth_;
     // topo_render's way out to host memory: a pinned staging image and the events of its slices; the buffers the caller pinned
-    uint8_t* h_stage_ = nullptr; size_t cap_stage_ = 0;
+    uint8_t* h_stage_ = nullptr;
+    size_t stage_bytes_ = 0;
     hipEvent_t stage_ev_[8] = {};
     std::vector<std::pair<uint8_t*, size_t>> pinned_;
     int download(uint8_t* dst, size_t dst_pitch, const uint8_t* src_dev, size_t row);
@@ -228,10 +254,10 @@ class TerrainRenderer {
     ViewDev* h_views_ = nullptr;          // pinned staging ring
     hipEvent_t view_ev_[kViewSlots] = {};
     bool view_used_[kViewSlots] = {};
-    void* d_peaks_ = nullptr;    size_t cap_peaks_ = 0;      // xyz in, then visible + xy out
-    void* d_proj_ = nullptr;     size_t cap_proj_ = 0;
-    void* d_overlay_geo_ = nullptr;  size_t cap_overlay_geo_ = 0;     // overlay vertices + indices
-    void* d_overlay_keys_ = nullptr; size_t cap_overlay_keys_ = 0;    // W*H overlay keys (depth | ~triangle), kept at the post quad's depth between calls
+    DeviceBuffer d_peaks_;            // xyz in, then visible + xy out
+    DeviceBuffer d_proj_;
+    DeviceBuffer d_overlay_geo_;      // overlay vertices + indices
+    DeviceBuffer d_overlay_keys_;     // W*H overlay keys (depth | ~triangle), kept at the post quad's depth between calls
     uint32_t overlay_w_ = 0, overlay_h_ = 0;
     bool have_depth_ = false;
     uint32_t depth_w_ = 0, depth_h_ = 0;
@@ -240,8 +266,8 @@ class TerrainRenderer {
     // viewshed: render_frame launches k_viewshed while vs_on_; the masks exist (every tile has one) once vs_ever_.  The masks are shared
     // by every frame context: frames in flight only OR into them, so they need no order among themselves.
     bool vs_on_ = false, vs_ever_ = false;
-    void* d_vs_table_ = nullptr; size_t cap_vs_table_ = 0;      // rank -> the tile's mask, rebuilt with the tile table
-    unsigned long long* d_vs_stats_ = nullptr;                   // kViewshedStatSlots x 4 counters of k_viewshed
+    DeviceBuffer d_vs_table_;      // rank -> the tile's mask, rebuilt with the tile table
+    DeviceBuffer d_vs_stats_;      // kViewshedStatSlots x 4 counters of k_viewshed
     // horizon: the frame context of the latest submission (-1: none, or one that failed half-way), and the tile set's generation
     // (add_terrain / unload_terrain bump it: a submission rendered with another tile order can no longer be decoded).  The rank ->
     // (lat, lon) table and the host read's device buffer are made by the first query.
@@ -249,9 +275,8 @@ class TerrainRenderer {
     uint64_t tile_gen_ = 0;
     std::vector<int32_t> hz_ll_;                                 // the table's host copy (the source of its upload)
     uint64_t hz_ll_gen_ = ~0ull;
-    void* d_hz_ll_ = nullptr;    size_t cap_hz_ll_ = 0;
-    void* d_hz_out_ = nullptr;   size_t cap_hz_out_ = 0;
-    uint32_t* d_hz_check_ = nullptr;      // TOPO_BOUNDS_CHECK build: k_horizon's bounds record, folded into topo_frame_status
+    DeviceBuffer d_hz_ll_, d_hz_out_;
+    DeviceBuffer d_hz_check_;             // TOPO_BOUNDS_CHECK build: k_horizon's bounds record, folded into topo_frame_status
     int horizon_prepare(uint32_t first_view, uint32_t n_views, size_t view_stride, FrameCtx** c, hipStream_t* s);
     int horizon_launch(FrameCtx& c, uint32_t first_view, uint32_t n_views, HorizonPoint* out, size_t view_stride, hipStream_t s);
     int horizon_fold_check();
@@ -259,23 +284,11 @@ class TerrainRenderer {
     std::string err_;
 };
 
-// host-side restatements of the reference's CPU math (glam 0.31)
-void camera_uniforms(const float eye[3], float yaw, float pitch, float fov_y, float width, float height,
-                     float sun_theta_deg, float sun_phi_deg, int32_t view_mode, topo_uniforms* out);
-void panorama_uniforms(const float eye[3], float yaw0, float pitch, uint32_t sector_w, uint32_t sector_h, float sun_theta_deg, float sun_phi_deg,
-                       int32_t view_mode, uint32_t n_sectors, topo_uniforms* out);
 int comm_unique_id(uint8_t out[128], std::string* err);
 int comm_init(Comm** out, int device, const uint8_t id128[128], int rank, int world, std::string* err);
 int comm_from_nccl(Comm** out, void* nccl_comm, int rank, int world, std::string* err);
 void comm_destroy(Comm* c);
 void panorama_sector_range(int rank, int world, uint32_t* first, uint32_t* count);
 uint32_t panorama_slots(int world, uint32_t sector_w, uint32_t sector_h, topo_panorama_slot* out, uint32_t cap);
-void geometry_transform(float h, float lon_deg, float lat_deg, float out[3]);
-void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n, const float* xy, double* az_el);
-void terrain_rotation(float model_lon_deg, float model_lat_deg, float rot3x3_colmajor[9]);
-uint32_t locations_range(float latitude, float longitude, float range_dist, int32_t* out_lat_lon, uint32_t cap);
-void change_location_plan(float latitude, float longitude, float range_dist, const int32_t* loaded, uint32_t n_loaded,
-                          std::vector<std::pair<int32_t, int32_t>>& unload, std::vector<std::pair<int32_t, int32_t>>& request);
-void synth_tile(int32_t lat, int32_t lon, uint32_t w, uint32_t h, uint32_t seed, float* out);
 
 }  // namespace topo

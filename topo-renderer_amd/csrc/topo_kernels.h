@@ -49,10 +49,8 @@ struct FrameParams {
     uint64_t* vis;             // n_views * W * H visibility keys: depth bits << 32 | id
     uint8_t* dirty;            // one byte per 64 consecutive keys: 1 = some key of the segment was written this frame
     WorkItem* work;
-    uint32_t* counters;        // [0] near work count, [1] big count, [2] status bits, [3] rare count, [4] far candidates,
-                               // [5] far survivors, [6] big start, [7] rare start (of the current phase), [8..10] first
-                               // bounds violation (check build); 16 words; two sets per frame context, alternating: a frame's set was zeroed by the clear of the frame before
-    uint32_t* status_out;      // pinned host memory, or null: k_resolve's first workgroup stores the frame's 16 counter words there (nothing
+    uint32_t* counters;        // kCounterWords words (kCtr*, below); two sets per frame context, alternating: a frame's set was zeroed by the clear of the frame before
+    uint32_t* status_out;      // pinned host memory, or null: k_resolve's first workgroup stores the frame's kStatusWords counter words there (nothing
                                // changes them once the raster kernels are done), instead of a copy operation behind the frame
     BigItem* big;
     RareItem* rare;
@@ -91,9 +89,18 @@ struct OutputParams {
 constexpr uint32_t kStatusBigOverflow = 1u;    // big-triangle queue full: handled in-lane (slower, still exact)
 constexpr uint32_t kStatusRareOverflow = 2u;   // rare-triangle queue full: triangles were DROPPED -> the frame is invalid
 constexpr uint32_t kFarLists = 64;             // the far-candidate list is kept as 64 sub-lists, each with a counter on a cache line of its own
-constexpr uint32_t kCounterWords = 16 + 16 * kFarLists;      // queue counters and status words of one frame, then the sub-list counters (word 16 + 16 q)
+constexpr uint32_t kStatusWords = 16;          // queue counters and status words of one frame: what reaches the host (the status ring)
+constexpr uint32_t kCounterWords = kStatusWords + 16 * kFarLists;      // ... then the sub-list counters, each on a cache line of its own
 constexpr uint32_t kStatusBounds = 4u;         // TOPO_BOUNDS_CHECK build only: an out-of-range index was formed (and not used);
-                                               // counters[8] = site tag, counters[9..10] = the offending value
+                                               // kCtrBoundsTag = site tag, kCtrBoundsLo / Hi = the offending value
+// the words of a counter set (the experiment builds of k_resolve count in words 8..15 as well)
+constexpr uint32_t kCtrWork = 0, kCtrBig = 1;                  // near work items, big-triangle items
+constexpr uint32_t kCtrStatus = 2;                             // kStatus* bits
+constexpr uint32_t kCtrRare = 3;                               // rare-triangle entries WANTED (beyond rare_cap: dropped)
+constexpr uint32_t kCtrFarTested = 4, kCtrFarSurvived = 5;     // occlusion-test candidates, survivors (work2 entries)
+constexpr uint32_t kCtrBigStart = 6, kCtrRareStart = 7;        // where the current phase's big / rare items start
+constexpr uint32_t kCtrBoundsTag = 8, kCtrBoundsLo = 9, kCtrBoundsHi = 10;      // the first bounds violation (check build)
+constexpr uint32_t far_list_counter(uint32_t q) { return kStatusWords + 16 * q; }      // the counter of far sub-list q
 
 // load phase (add_terrain).  Every pass of the reference's add_terrain writes a disjoint set of texels (interior
 // / one seam per adjacent pair / one corner per 2x2 block), so any number of them can run in one launch each;
@@ -155,8 +162,8 @@ struct HorizonPoint {      // = topo_horizon_point (32 bytes)
 struct HorizonParams {
     const uint64_t* vis;          // the submission's keys: n_keys = n_views * W * H
     const uint8_t* dirty;         // its segment marks, one per 64 keys
-    const uint32_t* counters;     // its counter set (status word [2])
-    uint32_t* check;              // TOPO_BOUNDS_CHECK build: 16-word status record of the query (bounds violations); else unused
+    const uint32_t* counters;     // its counter set (status word kCtrStatus)
+    uint32_t* check;              // TOPO_BOUNDS_CHECK build: kStatusWords-word status record of the query (bounds violations); else unused
     const int32_t* tile_ll;       // rank -> (lat, lon) of the submission's tile order, n_tiles pairs
     HorizonPoint* out;            // view v's records at out + v * view_stride
     size_t view_stride;           // records

@@ -40,15 +40,15 @@ struct Vis {
 
 // TOPO_BOUNDS_CHECK build (libtopo_hip_check.so, `make check`): every index this file forms into the visibility buffer,
 // the segment marks, the queues, the tile rasters and the outputs is tested first; a violation sets kStatusBounds,
-// records (site tag, offending value) of the first one in counters[8..10] and the access is skipped instead of made.
+// records (site tag, offending value) of the first one in counters[kCtrBoundsTag .. kCtrBoundsHi] and the access is skipped instead of made.
 // It is the address sanitizer this pool does not offer for the GPU (tests/test_gpu_parity.py runs the suite's scenes
 // through it once).  In the product build TOPO_CHK is `true` and costs nothing.
 #ifdef TOPO_BOUNDS_CHECK
 __device__ __noinline__ void bounds_violation(uint32_t* counters, uint32_t tag, uint64_t value) {
-    if ((atomicOr(&counters[2], kStatusBounds) & kStatusBounds) == 0) {
-        counters[8] = tag;
-        counters[9] = (uint32_t)value;
-        counters[10] = (uint32_t)(value >> 32);
+    if ((atomicOr(&counters[kCtrStatus], kStatusBounds) & kStatusBounds) == 0) {
+        counters[kCtrBoundsTag] = tag;
+        counters[kCtrBoundsLo] = (uint32_t)value;
+        counters[kCtrBoundsHi] = (uint32_t)(value >> 32);
     }
 }
 #define TOPO_CHK(counters, ok, tag, value) ((ok) ? true : (bounds_violation((counters), (tag), (uint64_t)(value)), false))
@@ -696,13 +696,13 @@ __device__ __forceinline__ void emit_near(const FrameParams& P, uint32_t view, u
         const uint32_t by = blk / P.bx_count;
         const uint32_t cell_rows = min(kBCY, P.tile_h - 1 - by * kBCY);
         const uint32_t strip = P.near_strip, n = (cell_rows + strip - 1) / strip;
-        const uint32_t base = atomicAdd(&P.counters[0], n);
+        const uint32_t base = atomicAdd(&P.counters[kCtrWork], n);
         for (uint32_t k = 0; k < n; ++k)
             if (base + k < P.near_cap && TOPO_CHK(P.counters, blk < (1u << 24) && strip * k < 16u, 4u, blk))
                 P.work[base + k] = WorkItem{(view << 16) | rank, blk | ((strip * k) << 24) | (min(strip, cell_rows - strip * k) << 28)};
         return;
     }
-    const uint32_t slot = atomicAdd(&P.counters[0], 1u);
+    const uint32_t slot = atomicAdd(&P.counters[kCtrWork], 1u);
     if (slot < P.near_cap) P.work[slot] = WorkItem{(view << 16) | rank, blk};
 }
 
@@ -798,7 +798,7 @@ __device__ __forceinline__ void cull_body(const FrameParams& P, uint32_t block) 
         // 10^5 candidates appended through ONE counter cost this kernel 12 of its 43 us (atomics on one address are served one
         // at a time, ~12 ns each, however the waves aggregate them): the list is kept as kFarLists sub-lists, workgroup b
         // appending to sub-list b % kFarLists
-        const uint32_t q = block % kFarLists, slot = atomicAdd(&P.counters[16 + 16 * q], 1u);
+        const uint32_t q = block % kFarLists, slot = atomicAdd(&P.counters[far_list_counter(q)], 1u);
         if (TOPO_CHK(P.counters, slot < P.far_sub_cap, 5u, slot)) {
             FarItem fi;
             fi.view_rank = (view << 16) | rank; fi.block = blk;
@@ -852,22 +852,22 @@ __global__ __launch_bounds__(256) void k_occlusion(FrameParams P) {
     // between the two raster phases: the rare/big queues keep growing, the second phase starts where the first ended
     // (nothing enqueues while this kernel runs, and the consumers of the marks are launched after it)
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        P.counters[6] = P.counters[1];
-        P.counters[7] = P.counters[3];
+        P.counters[kCtrBigStart] = P.counters[kCtrBig];
+        P.counters[kCtrRareStart] = P.counters[kCtrRare];
     }
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave_global = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wave_count = gridDim.x * 4;
     // The sub-lists are walked as one list: lane k of every wave holds the number of entries in sub-lists 0 .. k (an inclusive
     // scan of the 64 counts), entry g of the whole lies in the sub-list q with incl[q - 1] <= g < incl[q].
     static_assert(kFarLists == 64, "one sub-list per lane");
-    uint32_t incl = min(P.counters[16 + 16 * lane], P.far_sub_cap);
+    uint32_t incl = min(P.counters[far_list_counter(lane)], P.far_sub_cap);
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
         if ((int)lane >= o) incl += up;
     }
     const uint32_t count = (uint32_t)__shfl((int)incl, 63);
-    if (blockIdx.x == 0 && threadIdx.x == 0) P.counters[4] = count;      // the candidate count, for the frame's statistics
+    if (blockIdx.x == 0 && threadIdx.x == 0) P.counters[kCtrFarTested] = count;      // the candidate count, for the frame's statistics
     auto entry = [&](uint32_t g) -> const FarItem& {
         const uint32_t q = (uint32_t)__popcll(__ballot(incl <= g));      // sub-lists that end at or before g
         const uint32_t start = q ? (uint32_t)__shfl((int)incl, (int)q - 1) : 0u;
@@ -903,7 +903,7 @@ __global__ __launch_bounds__(256) void k_occlusion(FrameParams P) {
             const uint32_t blk = fi.block, by = blk / P.bx_count;
             const uint32_t cell_rows = min(kBCY, P.tile_h - 1 - by * kBCY);
             const uint32_t strip = P.near_strip, n = (cell_rows + strip - 1) / strip;
-            const uint32_t base = atomicAdd(&P.counters[5], n);
+            const uint32_t base = atomicAdd(&P.counters[kCtrFarSurvived], n);
             for (uint32_t k = 0; k < n; ++k)
                 if (base + k < P.near_cap)
                     P.work2[base + k] = WorkItem{fi.view_rank, blk | ((strip * k) << 24) | (min(strip, cell_rows - strip * k) << 28)};
@@ -930,7 +930,7 @@ __device__ bool enqueue_big(const FrameParams& P, uint32_t view, uint32_t id, co
                             int32_t px0, int32_t px1, int32_t py0, int32_t py1) {
     const int32_t rx0 = px0 >> 6, rx1 = px1 >> 6, ry0 = py0 >> 6, ry1 = py1 >> 6;
     const uint32_t n = (uint32_t)((rx1 - rx0 + 1) * (ry1 - ry0 + 1));
-    const uint32_t base = atomicAdd(&P.counters[1], n);
+    const uint32_t base = atomicAdd(&P.counters[kCtrBig], n);
     BigItem it;
     it.view = view;
     it.id = id;
@@ -938,7 +938,7 @@ __device__ bool enqueue_big(const FrameParams& P, uint32_t view, uint32_t id, co
     it.Y[0] = s0.Y; it.Y[1] = s1.Y; it.Y[2] = s2.Y;
     it.z[0] = s0.z; it.z[1] = s1.z; it.z[2] = s2.z;
     if (base >= P.big_cap || n > P.big_cap - base) {
-        atomicOr(&P.counters[2], kStatusBigOverflow);
+        atomicOr(&P.counters[kCtrStatus], kStatusBigOverflow);
         // neutralise whatever part of the reservation lies inside the queue
         it.id = kNoTri;
         it.region = 0;
@@ -957,9 +957,9 @@ __device__ bool enqueue_big(const FrameParams& P, uint32_t view, uint32_t id, co
 
 // Triangles the lean kernel does not handle go to k_raster_rare.
 __device__ __forceinline__ void enqueue_rare(const FrameParams& P, uint32_t view, uint32_t draw) {
-    const uint32_t slot = atomicAdd(&P.counters[3], 1u);
+    const uint32_t slot = atomicAdd(&P.counters[kCtrRare], 1u);
     if (slot < P.rare_cap) P.rare[slot] = RareItem{view, draw};
-    else atomicOr(&P.counters[2], kStatusRareOverflow);
+    else atomicOr(&P.counters[kCtrStatus], kStatusRareOverflow);
 }
 
 // Fragment staging: lanes of k_raster do not touch the visibility buffer while they walk their triangles (the
@@ -1091,7 +1091,7 @@ __global__ __launch_bounds__(256, TOPO_RASTER_WAVES) void k_raster(FrameParams P
     __shared__ FragList s_fl[4];
     __shared__ TriList s_tl[4];
     const WorkItem* __restrict__ work = phase == 0 ? P.work : P.work2;
-    uint32_t count = P.counters[phase == 0 ? 0 : 5];
+    uint32_t count = P.counters[phase == 0 ? kCtrWork : kCtrFarSurvived];
     const uint32_t cap = P.near_cap;      // both lists hold strips
     if (count > cap) count = cap;
     // the wave index is wave-uniform: say so (readfirstlane), or the compiler treats everything derived from the
@@ -1218,10 +1218,10 @@ __global__ __launch_bounds__(256, TOPO_RASTER_WAVES) void k_raster(FrameParams P
 // been done.
 constexpr uint32_t kCoopRegions = 24;
 __global__ __launch_bounds__(256) void k_raster_rare(FrameParams P) {
-    uint32_t count = P.counters[3];
+    uint32_t count = P.counters[kCtrRare];
     if (count > P.rare_cap) count = P.rare_cap;
     const uint32_t lane = threadIdx.x & 63;
-    for (uint32_t item = P.counters[7] + blockIdx.x * blockDim.x + threadIdx.x; item < count; item += gridDim.x * blockDim.x) {
+    for (uint32_t item = P.counters[kCtrRareStart] + blockIdx.x * blockDim.x + threadIdx.x; item < count; item += gridDim.x * blockDim.x) {
         const RareItem ri = P.rare[item];
         const uint32_t rank = fastdiv(ri.draw, P.div_tris), tri = ri.draw - rank * P.tris_per_tile;
         if (!TOPO_CHK(P.counters, rank < P.n_tiles && ri.view < P.n_views, 10u, ri.draw)) continue;
@@ -1259,10 +1259,10 @@ __global__ __launch_bounds__(256) void k_raster_rare(FrameParams P) {
                     const int32_t jx0 = from(rx0), jy0 = from(ry0);
                     const uint32_t jw = (uint32_t)from((int32_t)rw), n = (uint32_t)from((int32_t)n_regions);
                     uint32_t base = 0;
-                    if ((int)lane == L) base = atomicAdd(&P.counters[1], n);
+                    if ((int)lane == L) base = atomicAdd(&P.counters[kCtrBig], n);
                     base = (uint32_t)from((int32_t)base);
                     if (base >= P.big_cap || n > P.big_cap - base) {      // no room: neutralise the part of the reservation inside the queue; the owner rasterises
-                        if ((int)lane == L) { atomicOr(&P.counters[2], kStatusBigOverflow); in_lane = true; }
+                        if ((int)lane == L) { atomicOr(&P.counters[kCtrStatus], kStatusBigOverflow); in_lane = true; }
                         it.id = kNoTri;
                         it.region = 0;
                         for (uint32_t k = mine; k < n && base + k < P.big_cap; k += n_act) P.big[base + k] = it;
@@ -1297,12 +1297,12 @@ __global__ __launch_bounds__(256) void k_raster_big(FrameParams P) {
     // each.  Instead of one mark store beside every atomic instruction (half of this kernel's memory instructions), the
     // lanes note the rows they hit in LDS and lane r marks row r's segment(s) once per item.
     __shared__ uint8_t s_rows[4][64];
-    uint32_t count = P.counters[1];
+    uint32_t count = P.counters[kCtrBig];
     if (count > P.big_cap) count = P.big_cap;
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     s_rows[wave][lane] = 0;
     const uint32_t wave_global = blockIdx.x * 4 + wave, wave_count = gridDim.x * 4;
-    for (uint32_t item = P.counters[6] + wave_global; item < count; item += wave_count) {
+    for (uint32_t item = P.counters[kCtrBigStart] + wave_global; item < count; item += wave_count) {
         // The item is the same for the whole wave, but the compiler cannot use scalar loads for it (the queue is
         // written by other kernels through the same pointer type): say so field by field, and the integer setup
         // runs on the scalar unit instead of 64 times over on the vector one.
@@ -1557,7 +1557,7 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
     const uint8_t* lut = reinterpret_cast<const uint8_t*>(s_lut);
     // the frame's counters (queue fills, status bits) for whoever waits for the frame: final since the last raster kernel, stored to
     // the host's pinned ring from here (a copy operation behind the frame was a blit kernel of its own: ~10 us of every frame)
-    if (P.status_out && blockIdx.x == 0 && threadIdx.x < 16) P.status_out[threadIdx.x] = P.counters[threadIdx.x];
+    if (P.status_out && blockIdx.x == 0 && threadIdx.x < kStatusWords) P.status_out[threadIdx.x] = P.counters[threadIdx.x];
     __syncthreads();                   // the only barrier
 #ifdef TOPO_RESOLVE_PROF      // experiment build: where do a wave's cycles go?  counters[8..15], units of 1024 cycles summed over waves
     uint32_t pf_t = (uint32_t)__builtin_amdgcn_s_memtime(), pf_acc[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -1894,7 +1894,7 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
 // then their mask loads -- are in flight together.
 // stats (per workgroup, 4 words): [0] terrain keys, [1] combined updates (run tails), [2] atomics issued.
 __global__ __launch_bounds__(256) void k_viewshed(FrameParams P, uint32_t* const* __restrict__ masks, unsigned long long* __restrict__ stats) {
-    if (P.counters[2] & kStatusRareOverflow) return;
+    if (P.counters[kCtrStatus] & kStatusRareOverflow) return;
     constexpr int kBatch = 4;
     constexpr uint32_t kSky = 0xFFFFFFFFu;
     const uint32_t lane = threadIdx.x & 63;
@@ -1993,7 +1993,7 @@ __global__ __launch_bounds__(256) void k_horizon(HorizonParams P) {
     const uint32_t ncols = P.W - x0 < 64u ? P.W - x0 : 64u;
     const bool valid = lane < ncols;
     HorizonPoint* const dst = P.out + (size_t)v * P.view_stride + x0 + lane;
-    if (P.counters[2] & kStatusRareOverflow) {
+    if (P.counters[kCtrStatus] & kStatusRareOverflow) {
         if (valid) horizon_store(dst, -2, 0u, 0, 0, 0u, 0u, 0u);
         return;
     }
