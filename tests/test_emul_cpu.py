@@ -1,4 +1,4 @@
-"""The product's device arithmetic (topo_math.h / topo_pipeline.h, the very headers the HIP kernels compile)
+"""The product's device arithmetic (topo_math.h / topo_pipeline.h, the very headers the HIP kernels in kernels_*.h compile)
 executed on the CPU by tests/host_emul.cpp and compared bit for bit with the independently written oracle.
 This is what lets a CPU-only run vouch for the kernels' arithmetic; the GPU run (-m gpu) then only has to show
 that hipcc's code generation agrees with g++'s."""

@@ -1,5 +1,6 @@
-"""Register budget of k_resolve, checked without a GPU: a device-only compile of topo_kernels.hip with the Makefile's flags,
-read back from the code object's metadata.  k_resolve is bound by instruction issue, and every spilled register costs issue
+"""Register budget of k_resolve (kernels_resolve.h), checked without a GPU: a device-only compile of topo_kernels.hip, the one
+device translation unit, with the Makefile's flags, read back from the code object's metadata.
+k_resolve is bound by instruction issue, and every spilled register costs issue
 slots (v_writelane / v_readlane, scratch traffic) in the loops around the rows; these ceilings keep a change from quietly
 bringing the spills back."""
 import os
@@ -29,7 +30,7 @@ def _makefile_flags():
 
 
 def _resolve_wgs():
-    src = open(os.path.join(CSRC, "topo_kernels.hip")).read()
+    src = open(os.path.join(CSRC, "kernels_resolve.h")).read()
     return int(re.search(r"^#define TOPO_RESOLVE_WGS (\d+)", src, re.M).group(1))
 
 

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static VALU/SALU/memory instruction counts of one kernel, attributed to source lines.
+"""Static VALU/SALU/memory instruction counts of one kernel, attributed to source lines (of the kernels_*.h phase file that defines it
+   and of the headers it inlines; topo_kernels.hip is what is compiled).
    tools/isa_by_line.py <kernel-name-substring> [min_count]   (needs hipcc; writes scratch files under /tmp)"""
 import collections, os, re, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

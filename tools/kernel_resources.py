@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Register / LDS / scratch use of every kernel in topo_kernels.hip (code-object metadata of a device-only compile).
+"""Register / LDS / scratch use of every kernel of the device translation unit, topo_kernels.hip with its kernels_*.h phase files
+   (code-object metadata of a device-only compile).
    tools/kernel_resources.py [extra hipcc flags...]"""
 import os, re, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -7,7 +7,7 @@
 // 32-bit words) / floating point (3, Adobe Photoshop TIFF Technical Note 3).
 //
 // Host: parse the first IFD, undo the byte-stream compression of every strip/tile (zlib for Deflate).  Device
-// (topo_kernels.hip: k_tiff_rows): undo the predictor, fix the byte order, place the segments into the w x h raster --
+// (kernels_tiff.h: k_tiff_rows): undo the predictor, fix the byte order, place the segments into the w x h raster --
 // the samples never exist as floats on the host.
 #pragma once
 #include <cstddef>

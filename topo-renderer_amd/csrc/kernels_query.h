@@ -1,0 +1,189 @@
+// kernels_query.h -- queries that read a finished frame's visibility buffer.
+//
+//   k_viewshed   behind the frame's last k_resolve: the DEM cells that own a pixel, OR-ed into per-tile bit masks
+//   k_horizon    per view and column, the topmost pixel that shows terrain, decoded to its tile and cell
+#pragma once
+
+#include "kernels_common.h"
+
+namespace topo {
+namespace {
+
+// Viewshed (topo_viewshed_*): after the frame's last k_resolve, every DEM cell that owns at least one pixel of the visibility
+// buffer gets its bit set in the mask of its tile.  A key's low word is draw << 1 | fan (the two halves of a near-clipped triangle),
+// draw = rank * tris_per_tile + triangle; bit = cell = triangle >> 1 = x (h-1) + y; masks[rank] is the mask of the tile at that
+// rank.  A frame whose rare-triangle queue overflowed is incomplete -- farther triangles won pixels they should not have -- and
+// marks nothing.  A wave takes 64 segments at a time (one coalesced read of their marks, as k_clear); unmarked
+// segments are sky.  Of each marked segment's 64 keys, a run of neighbouring lanes that hit the same mask word is combined into its
+// last lane (a segmented OR over as many doubling steps as the longest run needs), and only that lane updates the word: a load,
+// and the atomicOr only when it would set a bit (issued blind, the atomics cost 6x as much at c4: DESIGN.md §5,
+// tools/experiments/viewshed_blind_atomics_experiment.patch).  kBatch segments are taken at once so that their key loads -- and
+// then their mask loads -- are in flight together.
+// stats (per workgroup, 4 words): [0] terrain keys, [1] combined updates (run tails), [2] atomics issued.
+__global__ __launch_bounds__(256) void k_viewshed(FrameParams P, uint32_t* const* __restrict__ masks, unsigned long long* __restrict__ stats) {
+    if (P.counters[kCtrStatus] & kStatusRareOverflow) return;
+    constexpr int kBatch = 4;
+    constexpr uint32_t kSky = 0xFFFFFFFFu;
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t n = (size_t)P.n_views * P.W * P.H, nseg = (n + 63) >> 6;
+    const size_t wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwave = (size_t)gridDim.x * 4;
+    const uint32_t cells = P.tris_per_tile >> 1, words = (cells + 31) >> 5;
+    uint64_t n_keys = 0, n_tails = 0, n_atomics = 0;
+    for (size_t g = wave * 64; g < nseg; g += nwave * 64) {
+        uint64_t todo = __ballot(g + lane < nseg && P.dirty[g + lane] != 0);
+        while (todo) {
+            uint32_t t[kBatch], rank[kBatch], word[kBatch], bit[kBatch], cur[kBatch];
+            uint64_t heads[kBatch];
+            bool tail[kBatch];
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) {
+                t[b] = kSky;
+                if (todo) {
+                    const size_t at = (g + (size_t)__builtin_ctzll(todo)) * 64 + lane;
+                    todo &= todo - 1;
+                    if (at < n) t[b] = (uint32_t)P.vis[at];      // the key's low word: draw << 1 | fan
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) {
+                rank[b] = 0; word[b] = 0; bit[b] = 0;
+                if (t[b] != kSky) {
+                    const uint32_t draw = t[b] >> 1;
+                    rank[b] = fastdiv(draw, P.div_tris);
+                    const uint32_t cell = (draw - rank[b] * P.tris_per_tile) >> 1;
+                    word[b] = cell >> 5;
+                    bit[b] = 1u << (cell & 31u);
+                    t[b] = rank[b] * words + word[b];      // the run key: one mask word of one tile (< 2^26: ids are < 2^31)
+                }
+                n_keys += (uint64_t)__popcll(__ballot(t[b] != kSky));
+                const uint32_t prev = __shfl_up(t[b], 1);
+                heads[b] = __ballot(lane == 0 || prev != t[b]);
+                // The OR takes a lane d back whenever it holds the same word, with no segment flag: a run is contiguous, so a lane of
+                // ANOTHER run with the same word (A B A) only adds bits of that same word -- still right for the word the tail updates --
+                // and every lane of the tail's own run is reached, because a step's source lane outside the run has nothing of the run
+                // behind it either.
+                uint64_t need = ~heads[b];      // lanes whose run reaches back further than the bits gathered so far
+                for (uint32_t d = 1; need; d <<= 1) {
+                    const uint32_t tp = __shfl_up(t[b], d), bp = __shfl_up(bit[b], d);
+                    if (lane >= d && tp == t[b]) bit[b] |= bp;      // (a lane further back with the same word: its bits belong there too)
+                    need &= need << d;
+                }
+                tail[b] = t[b] != kSky && (lane == 63 || ((heads[b] >> (lane + 1)) & 1u));
+                n_tails += (uint64_t)__popcll(__ballot(tail[b]));
+                // (the table index is tested in the product build too: what it reads is a pointer)
+                if (tail[b] && !(TOPO_CHK(P.counters, rank[b] < P.n_tiles && word[b] < words, 16u, t[b]) && rank[b] < P.n_tiles && word[b] < words))
+                    tail[b] = false;
+            }
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) cur[b] = tail[b] ? masks[rank[b]][word[b]] : 0u;
+#pragma unroll
+            for (int b = 0; b < kBatch; ++b) {
+                const bool issue = tail[b] && (cur[b] & bit[b]) != bit[b];
+                n_atomics += (uint64_t)__popcll(__ballot(issue));
+                if (issue) atomicOr(&masks[rank[b]][word[b]], bit[b]);
+            }
+        }
+    }
+    if (lane == 0 && n_keys) {      // (n_keys == 0: nothing else is either)
+        unsigned long long* s = stats + (size_t)blockIdx.x * 4;
+        atomicAdd(&s[0], (unsigned long long)n_keys);
+        atomicAdd(&s[1], (unsigned long long)n_tails);
+        atomicAdd(&s[2], (unsigned long long)n_atomics);
+    }
+}
+
+// One horizon record, as two 16-byte vector stores.
+__device__ __forceinline__ void horizon_store(HorizonPoint* dst, int32_t row, uint32_t depth_bits, int32_t lat, int32_t lon, uint32_t cx, uint32_t cy,
+                                              uint32_t fan) {
+    int4* d = reinterpret_cast<int4*>(dst);
+    d[0] = make_int4(row, (int32_t)depth_bits, lat, lon);
+    d[1] = make_int4((int32_t)cx, (int32_t)cy, (int32_t)fan, 0);
+}
+
+// Horizon (topo_horizon_*): for every column of every queried view of a finished submission, the topmost pixel whose key names a
+// triangle (the smallest row whose low word is not kNoTri), and what it shows: the key's depth, the tile (rank -> (lat, lon) in the
+// submission's tile order) and the cell (draw = rank * tris_per_tile + tri, cell = tri >> 1 = x (h-1) + y, as k_viewshed decodes it).
+// Launched by the query on the submission's stream, behind it; it reads the keys, the marks and the status word and writes only
+// `out` (the next k_clear trusts the marks).  A frame whose rare-triangle queue overflowed is incomplete: every record reads row -2.
+// One wave per (view, 64-column group), a lane per column; no column is walked row by row from the top.  A step takes the marks of
+// kWin x 64 rows at once (lane l: row y0 + 64 j + l, both segments the group's <= 64 keys of that row can touch) and ballots them into
+// row masks: an unmarked segment holds only kVisClear, so a row without a mark is sky for the whole group.  The marked rows then go
+// in ascending order, kBatch at a time with their key loads in flight together, until every lane has found terrain or the rows run
+// out.  Linear indices are 64-bit: a submission holds up to 2^32 - 1 keys.
+__global__ __launch_bounds__(256) void k_horizon(HorizonParams P) {
+    constexpr int kWin = 4, kBatch = 8;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t groups = (P.W + 63) >> 6;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave >= (uint64_t)groups * P.n_views) return;      // (whole waves)
+    const uint32_t v = (uint32_t)(wave / groups), x0 = (uint32_t)(wave - (uint64_t)v * groups) * 64;
+    const uint32_t ncols = P.W - x0 < 64u ? P.W - x0 : 64u;
+    const bool valid = lane < ncols;
+    HorizonPoint* const dst = P.out + (size_t)v * P.view_stride + x0 + lane;
+    if (P.counters[kCtrStatus] & kStatusRareOverflow) {
+        if (valid) horizon_store(dst, -2, 0u, 0, 0, 0u, 0u, 0u);
+        return;
+    }
+    const size_t vbase = (size_t)(P.first_view + v) * P.W * P.H + x0;      // the key of (row 0, column x0) of the view
+    [[maybe_unused]] const size_t nseg = (P.n_keys + 63) >> 6;      // (the check build's bound)
+    const uint64_t* const col = P.vis + vbase + lane;
+    uint64_t key = kVisClear;
+    int32_t row = -1;
+    bool searching = valid;
+    for (uint32_t y0 = 0; y0 < P.H && __ballot(searching); y0 += 64 * kWin) {
+        uint64_t rows[kWin];
+#pragma unroll
+        for (int j = 0; j < kWin; ++j) {
+            const uint32_t y = y0 + 64 * j + lane;
+            bool m = false;
+            if (y < P.H) {
+                const size_t a = vbase + (size_t)y * P.W, sa = a >> 6, sb = (a + ncols - 1) >> 6;
+                if (TOPO_CHK(P.check, sb < nseg, 17u, sb)) m = (P.dirty[sa] | P.dirty[sb]) != 0;
+            }
+            rows[j] = __ballot(m);
+        }
+#pragma unroll
+        for (int j = 0; j < kWin; ++j) {
+            uint64_t todo = rows[j];
+            while (todo && __ballot(searching)) {
+                uint32_t r[kBatch];
+                uint64_t k[kBatch];
+#pragma unroll
+                for (int b = 0; b < kBatch; ++b) {
+                    r[b] = todo ? y0 + 64 * j + (uint32_t)__builtin_ctzll(todo) : P.H;      // (P.H: no row left)
+                    todo &= todo - 1;
+                }
+#pragma unroll
+                for (int b = 0; b < kBatch; ++b) {
+                    const size_t at = (size_t)r[b] * P.W;
+                    k[b] = searching && r[b] < P.H && TOPO_CHK(P.check, vbase + lane + at < P.n_keys, 17u, vbase + lane + at) ? col[at] : kVisClear;
+                }
+#pragma unroll
+                for (int b = 0; b < kBatch; ++b)
+                    if (searching && (uint32_t)k[b] != kNoTri) {      // (rows ascend within the batch: the first hit is the topmost)
+                        key = k[b];
+                        row = (int32_t)r[b];
+                        searching = false;
+                    }
+            }
+        }
+    }
+    if (!valid) return;
+    if (row < 0) {
+        horizon_store(dst, -1, (uint32_t)(kVisClear >> 32), 0, 0, 0u, 0u, 0u);      // sky: depth 1.0
+        return;
+    }
+    const uint32_t id = (uint32_t)key, draw = id >> 1;
+    const uint32_t rank = fastdiv(draw, P.div_tris), cell = (draw - rank * P.tris_per_tile) >> 1;
+    const uint32_t cx = fastdiv(cell, P.div_hm1), cy = cell - cx * P.hm1;
+    int32_t lat = 0, lon = 0;
+    // (the rank is tested in the product build too: what it indexes is a table)
+    if (TOPO_CHK(P.check, rank < P.n_tiles, 17u, id) && rank < P.n_tiles) {
+        lat = P.tile_ll[2 * (size_t)rank];
+        lon = P.tile_ll[2 * (size_t)rank + 1];
+    }
+    horizon_store(dst, row, (uint32_t)(key >> 32), lat, lon, cx, cy, id & 1u);
+}
+
+}  // namespace
+}  // namespace topo

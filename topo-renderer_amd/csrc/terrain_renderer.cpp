@@ -643,7 +643,7 @@ void TerrainRenderer::fill_params(FrameCtx& c, FrameParams& p) {
     // this frame's counters (queue fills, status bits), for whoever waits for the frame (check_frames, get_counters): stored by
     // k_resolve into the pinned ring.  The bounds-checking build, whose k_resolve may still set a status bit, copies them
     // behind the frame instead.
-#if defined(TOPO_BOUNDS_CHECK) || defined(TOPO_RESOLVE_PROF)
+#ifdef TOPO_BOUNDS_CHECK
     p.status_out = nullptr;
 #else
     p.status_out = switches().status_by_copy ? nullptr : c.status_words(c.submitted);

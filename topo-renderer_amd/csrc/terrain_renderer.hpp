@@ -206,7 +206,7 @@ class TerrainRenderer {
         uint64_t submitted = 0, checked = 0;
         uint32_t* status_words(uint64_t frame) const { return h_status + (frame % kStatusRing) * kStatusWords; }
         const uint32_t* latest_status() const { return status_words(submitted - 1); }
-        DeviceBuffer d_vis, d_dirty;      // d_dirty: one mark per 64 visibility keys (topo_kernels.hip: struct Vis)
+        DeviceBuffer d_vis, d_dirty;      // d_dirty: one mark per 64 visibility keys (kernels_common.h: struct Vis)
         DeviceBuffer d_work, d_work2, d_far, d_big, d_rare, d_counters;
         DeviceBuffer d_pre_rgba, d_pre_depth;      // the pixelise branch: the render-target image k_post_pixelize samples, and a depth image when the caller wants none
         // the context's latest submission as the horizon query reads it (its keys and marks are d_vis / d_dirty until the next one)

@@ -1,4 +1,4 @@
-// topo_kernels.h -- launch interface of the gfx950 kernels (topo_kernels.hip).
+// topo_kernels.h -- launch interface of the gfx950 kernels (topo_kernels.hip: the launchers; kernels_*.h: the kernels, by phase).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -93,7 +93,7 @@ constexpr uint32_t kStatusWords = 16;          // queue counters and status word
 constexpr uint32_t kCounterWords = kStatusWords + 16 * kFarLists;      // ... then the sub-list counters, each on a cache line of its own
 constexpr uint32_t kStatusBounds = 4u;         // TOPO_BOUNDS_CHECK build only: an out-of-range index was formed (and not used);
                                                // kCtrBoundsTag = site tag, kCtrBoundsLo / Hi = the offending value
-// the words of a counter set (the experiment builds of k_resolve count in words 8..15 as well)
+// the words of a counter set
 constexpr uint32_t kCtrWork = 0, kCtrBig = 1;                  // near work items, big-triangle items
 constexpr uint32_t kCtrStatus = 2;                             // kStatus* bits
 constexpr uint32_t kCtrRare = 3;                               // rare-triangle entries WANTED (beyond rare_cap: dropped)

@@ -101,7 +101,7 @@ TOPO_HD float div_f(float x, float y) { return div_by(x, recip_of(y)); }
 // sqrt(x), correctly rounded: the hardware estimate (1 ulp) moved to whichever neighbour the two residuals pick,
 // i.e. the compiler's own expansion of sqrtf without its input scaling (x is 0.01 .. 1e15 on this path).
 TOPO_HD float sqrt_f(float x) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TOPO_EXP_OLD_SQRT)
+#if defined(__HIP_DEVICE_COMPILE__)
     float s = __builtin_amdgcn_sqrtf(x);
     const float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
     const float rdn = fmaf(-dn, s, x), rup = fmaf(-up, s, x);
@@ -377,7 +377,7 @@ TOPO_HD void shade_fragment(int view_mode, f3 sun, float cam_x, float cam_y, flo
         return;
     }
     const float px = frag_x + cam_x - wpos.x, py = frag_y + cam_y - wpos.y;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TOPO_EXP_SPEC_FRACT)      // (experiment build TOPO_EXP_SPEC_FRACT: the two-instruction form everywhere)
+#if defined(__HIP_DEVICE_COMPILE__)
     // The twelve first-level fractions take (p + c) * m with c in {0, 0.07, 0.11, 0.13, 0.13 + 0.07, 0.13 + 0.11} and m > 5: such
     // an operand is a negative above -2^-24 only if p + c lies in (-1.2e-8, 0), i.e. p within 2e-8 of -c, and every -c lies in
     // [-0.25, 0].  So a pixel with neither coordinate in [-0.3, 0] may use the instruction throughout (18 issue slots for 36);

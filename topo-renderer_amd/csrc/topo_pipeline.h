@@ -2,7 +2,7 @@
 //
 // The reference draws every tile's mesh through the fixed-function rasteriser (pipeline.rs:221-246);
 // here the same semantics are spelled out as plain functions (DESIGN.md "Raster spec") that the HIP
-// kernels in topo_kernels.hip call.  All functions are pure (TOPO_HD) so tests can also execute them
+// kernels (topo_kernels.hip, kernels_*.h) call.  All functions are pure (TOPO_HD) so tests can also execute them
 // under g++ (tests/host_emul.cpp); the product only ever runs them on the GPU.
 #pragma once
 
