@@ -1692,3 +1692,47 @@ def test_host_outputs_staged_and_pinned(topo, orc):
         assert e.value.code == topo.TOPO_ERR_NOT_FOUND
         g.render_into(big, dbig)                                             # and the staged route again for the same arrays
         assert_same_frame((big, dbig), ref, f"staged after unpin {W}x{H}")
+
+
+def test_renderer_lifecycle_returns_device_memory(topo):
+    """Everything a renderer allocates goes with it, on the success paths: eight lifecycles -- tiles added, one of them replaced, the
+    viewshed masks, two frame contexts with frames in flight, a horizon query, a frame through the pinned staging block, a tile
+    unloaded, close() -- leave the device's free memory where a warm-up lifecycle left it.  The bound is half of what losing ONE
+    replaced tile per lifecycle would cost: 8 x pool_bytes, pool_bytes = the heights and normals of a 1200 x 1200 tile (the whole
+    pool is larger; a lost frame context, >= 224 MiB of queues, is far above it).  Device-wide free memory: another process on
+    the card can move it."""
+    import torch
+    W, H, tile = 256, 128, 1200
+    a = topo.synth_tile(45, 15, tile, tile)
+    b = a + np.float32(25.0)
+    eye = topo.geometry_transform(topo.synth.height_at(a, 45, 15, 15.52, 45.51) + 60.0, 15.52, 45.51)
+    views = [topo.camera_uniforms(eye, math.radians(yaw), 0.0, math.radians(60.0), W, H, 15.52, 45.51, 0) for yaw in (0.0, 120.0, 240.0)]
+    rgba = torch.empty((len(views), H, W, 4), dtype=torch.uint8, device="cuda")
+
+    def cycle():
+        g = topo.TerrainRenderer(W, H, device=0)
+        g.add_terrain(45, 15, a, *topo.synth.tile_transform(45, 15, tile, tile))
+        g.add_terrain(45, 15, b, *topo.synth.tile_transform(45, 15, tile, tile))      # replaces the tile
+        g.add_terrain(45, 16, a, *topo.synth.tile_transform(45, 16, tile, tile))
+        g.viewshed_enable(True)
+        g.set_pipeline_depth(2)
+        for u, out in zip(views, rgba):
+            g.render_views_device([u], W, H, out.data_ptr(), H * W * 4, W * 4)
+        g.join()
+        assert g.horizon().shape == (1, W)
+        g.update(W, H, views[0], topo.post_uniforms(W, H))
+        frame, depth = g.render()                                                     # host arrays: the pinned staging block
+        assert frame.shape == (H, W, 4) and (depth < 1).any()
+        g.unload_terrain(45, 16)
+        g.close()
+
+    cycle()      # loads the code object, fills the runtime's own pools
+    torch.cuda.synchronize()
+    free0, _ = torch.cuda.mem_get_info()
+    for _ in range(8):
+        cycle()
+    torch.cuda.synchronize()
+    free1, _ = torch.cuda.mem_get_info()
+    pool_bytes = 2 * tile * tile * 4
+    print(f"free0 - free1 = {free0 - free1} bytes (bound {4 * pool_bytes})")
+    assert free0 - free1 < 4 * pool_bytes

@@ -113,9 +113,9 @@ struct Comm {
     int device = -1;           // the communicator's device (ncclCommCuDevice), -1 = unknown
     bool owned = false;        // created by topo_comm_init (destroyed with the Comm) or borrowed (topo_comm_from_nccl)
     // the exchange runs on a stream of its own, behind the part of the frame it ships and beside the rest of it
-    hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> ready;      // one per exchange slot of a panorama: "this part of the strip is final"
-    hipEvent_t done = nullptr;
+    Stream stream;
+    std::vector<Event> ready;      // one per exchange slot of a panorama: "this part of the strip is final"
+    Event done;
 };
 
 int comm_unique_id(uint8_t out[128], std::string* err) {
@@ -129,8 +129,8 @@ int comm_unique_id(uint8_t out[128], std::string* err) {
 
 static int comm_streams(Comm* c, int device, std::string* err) {
     if (c->world <= 1) return TOPO_OK;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream.h, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&c->done.h, hipEventDisableTiming) != hipSuccess) {
         *err = "HIP stream/event creation for the exchange failed";
         return TOPO_ERR_HIP;
     }
@@ -185,9 +185,7 @@ int comm_from_nccl(Comm** out, void* nccl_comm, int rank, int world, std::string
 
 void comm_destroy(Comm* c) {
     if (!c) return;
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    for (hipEvent_t e : c->ready) (void)hipEventDestroy(e);
-    if (c->done) (void)hipEventDestroy(c->done);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->owned && c->nccl && rccl().CommDestroy) (void)rccl().CommDestroy(c->nccl);
     delete c;
 }
@@ -263,9 +261,9 @@ int TerrainRenderer::render_panorama(Comm* comm, const float eye[3], float yaw0,
     if (force_slots)      // (the two-rank plan covers four sectors: repeat it for the other four)
         for (uint32_t i = n_slots / 2; i < n_slots; ++i) plan[i] = topo_panorama_slot{plan[i - n_slots / 2].sector + 4u, plan[i - n_slots / 2].row0, plan[i - n_slots / 2].rows};
     while (world > 1 && comm->ready.size() < n_slots) {
-        hipEvent_t e = nullptr;
-        TOPO_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        comm->ready.push_back(e);
+        Event e;
+        TOPO_HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+        comm->ready.push_back(std::move(e));
     }
     const uint32_t rblocks_x = (sector_w + kResolveBlockW - 1) / kResolveBlockW;
     const uint32_t rblocks_view = rblocks_x * ((sector_h + kResolveBlockH - 1) / kResolveBlockH);

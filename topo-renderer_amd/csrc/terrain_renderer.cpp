@@ -30,6 +30,14 @@ const Switches& switches() { static const Switches s; return s; }
 bool is_linear(uint32_t format) { return format == TOPO_FORMAT_RGBA8_UNORM || format == TOPO_FORMAT_BGRA8_UNORM; }
 bool is_bgra(uint32_t format) { return format == TOPO_FORMAT_BGRA8_UNORM_SRGB || format == TOPO_FORMAT_BGRA8_UNORM; }
 
+// Timing slot [0]..[5] of topo_get_timings / topo_set_timing_slots -> the stages whose durations it adds up: what queue_frame records
+// events by and frame_durations sums by.  A stage needs the two events around it; the total, the frame's first and last.
+constexpr int kTimingSlots = 6;
+constexpr uint32_t kStagesOfSlot[kTimingSlots] = {1u << kStClear, 1u << kStCull, (1u << kStRasterNear) | (1u << kStRasterFar), 1u << kStOcclusion,
+                                                  (1u << kStRareBigNear) | (1u << kStRareBigFar), 1u << kStResolve};
+constexpr uint32_t stage_events(int stage) { return 3u << stage; }
+constexpr uint32_t kLastEvent = 1u << kNumStages, kTotalEvents = 1u | kLastEvent;
+
 }  // namespace
 
 int TerrainRenderer::fail(int code, const std::string& msg) {
@@ -68,20 +76,21 @@ int TerrainRenderer::create(TerrainRenderer** out, int device, uint32_t w, uint3
     r->W_ = w;
     r->H_ = h;
     r->format_ = format;
-    e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreate(&r->own_stream_);
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&r->load_ev_[i]);
-    for (int k = 0; k < kEvRing && e == hipSuccess; ++k)
-        for (int i = 0; i < kNumEvents && e == hipSuccess; ++i) e = hipEventCreate(&r->ctx_[0].evr[k][i]);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ctx_[0].done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        *err = std::string("HIP initialisation failed: ") + hipGetErrorString(e);
+    if (r->init() != TOPO_OK) {
+        *err = "HIP initialisation failed: " + r->err_;
         delete r;
         return TOPO_ERR_HIP;
     }
-    r->stream_ = r->own_stream_;
     *out = r;
     return TOPO_OK;
+}
+
+int TerrainRenderer::init() {
+    TOPO_HIP_TRY(hipSetDevice(device_));
+    TOPO_HIP_TRY(hipStreamCreate(&own_stream_.h));
+    stream_ = own_stream_;
+    for (auto& e : load_ev_) TOPO_HIP_TRY(hipEventCreate(&e.h));
+    return init_ctx(ctx_[0], false);
 }
 
 TerrainRenderer::~TerrainRenderer() {
@@ -89,26 +98,8 @@ TerrainRenderer::~TerrainRenderer() {
     if (stream_) (void)hipStreamSynchronize(stream_);
     for (auto& c : ctx_)
         if (c.stream) (void)hipStreamSynchronize(c.stream);
-    for (auto& kv : tiles_) free_tile(kv.second);
-    for (auto& c : ctx_) {
-        for (auto& set : c.evr)
-            for (auto& e : set)
-                if (e) (void)hipEventDestroy(e);
-        if (c.done) (void)hipEventDestroy(c.done);
-        if (c.stream) (void)hipStreamDestroy(c.stream);
-        if (c.h_status) (void)hipHostFree(c.h_status);
-    }
-    for (auto& e : load_ev_)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : view_ev_)
-        if (e) (void)hipEventDestroy(e);
-    if (h_views_) (void)hipHostFree(h_views_);
-    if (h_stage_) (void)hipHostFree(h_stage_);
-    for (auto& e : stage_ev_)
-        if (e) (void)hipEventDestroy(e);
-    for (const auto& pin : pinned_) (void)hipHostUnregister(pin.first);
-    if (own_stream_) (void)hipStreamDestroy(own_stream_);
-    // (the DeviceBuffer members go now: the device is bound and every stream has been waited for)
+    // (the members go now -- tiles, buffers, pinned memory, registrations, events, streams: the device is bound and every stream
+    // has been waited for)
 }
 
 int TerrainRenderer::ensure(hipStream_t s, DeviceBuffer& b, size_t need) {
@@ -124,16 +115,18 @@ int TerrainRenderer::ensure(hipStream_t s, DeviceBuffer& b, size_t need) {
     return TOPO_OK;
 }
 
+int TerrainRenderer::ensure_pinned(PinnedBuffer& b, size_t need) {
+    if (need <= b.cap) return TOPO_OK;
+    b.reset();
+    TOPO_HIP_TRY(hipHostMalloc(&b.p, need));
+    b.cap = need;
+    return TOPO_OK;
+}
+
 int TerrainRenderer::wait_all() {
     if (int rc = join()) return rc;
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
     return TOPO_OK;
-}
-
-void TerrainRenderer::free_tile(Tile& t) {
-    (void)hipFree(t.d_pool);
-    if (t.d_mask) (void)hipFree(t.d_mask);
-    t.d_pool = t.d_mask = nullptr;
 }
 
 Tile* TerrainRenderer::find(int lat, int lon) {
@@ -223,37 +216,35 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
     const size_t tile_floats = (size_t)bxc * byc * 2 + 2 * ((size_t)w + h);
     auto up256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
     const size_t off_normals = up256(texels * 4), off_tables = off_normals + up256(texels * 4), off_bounds = off_tables + up256(tile_floats * sizeof(float));
-    TOPO_HIP_TRY(hipMalloc(&t.d_pool, off_bounds + (size_t)bxc * byc * 17 * sizeof(double)));
-    t.d_heights = reinterpret_cast<float*>(t.d_pool);
-    t.d_normals = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(t.d_pool) + off_normals);
-    t.d_minmax = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(t.d_pool) + off_tables);
-    const hipError_t e = hipMemcpyAsync(t.d_heights, heights, texels * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_);
+    if (int rc = ensure(stream_, t.pool, off_bounds + (size_t)bxc * byc * 17 * sizeof(double))) return rc;
+    t.d_heights = t.pool.as<float>();
+    t.d_normals = reinterpret_cast<uint32_t*>(t.pool.as<uint8_t>() + off_normals);
+    t.d_minmax = reinterpret_cast<float*>(t.pool.as<uint8_t>() + off_tables);
     // (the zero-initialised normal texture: k_normals_interior writes the untouched border ring as zero)
-    if (e != hipSuccess) {
-        free_tile(t);
+    if (const hipError_t e = hipMemcpyAsync(t.d_heights, heights, texels * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_))
         return hip_fail(e, "tile upload");
-    }
     if (vs_ever_)      // (a replaced tile's mask goes with it: the new one starts empty)
-        if (int rc = alloc_mask(t)) {
-            free_tile(t);
-            return rc;
-        }
+        if (int rc = alloc_mask(t)) return rc;
     // TerrainUniforms::new (render/data.rs:124-151)
     t.dev.heights = t.d_heights;
     t.dev.normals = t.d_normals;
     t.dev.block_minmax = t.d_minmax;
     t.dev.trig_lon = t.d_minmax + (size_t)bxc * byc * 2;
     t.dev.trig_lat = t.dev.trig_lon + 2 * (size_t)w;
-    t.dev.block_bounds = reinterpret_cast<const double*>(reinterpret_cast<uint8_t*>(t.d_pool) + off_bounds);
+    t.dev.block_bounds = reinterpret_cast<const double*>(t.pool.as<uint8_t>() + off_bounds);
     t.dev.raster_x = rp[0]; t.dev.raster_y = rp[1];
     t.dev.model_x = mp[0]; t.dev.model_y = mp[1];
     t.dev.scale_x = ps[0]; t.dev.scale_y = ps[1];
     terrain_rotation(mp[0], mp[1], t.dev.rot);
-    // BTreeMap::insert replaces an existing entry; its GPU resources are dropped after the passes below
-    Tile old{};
-    bool had_old = false;
-    if (Tile* ex = find(lat, lon)) { old = *ex; had_old = true; tiles_.erase(geo_key(lat, lon)); }
-    Tile& nt = tiles_[geo_key(lat, lon)] = t;
+    // BTreeMap::insert replaces an existing entry; its GPU resources are dropped when this call returns, on whichever path, once
+    // stream_ has been waited for (where that wait itself fails, hipFree waits for the device)
+    struct Retired {
+        Tile tile;
+        hipStream_t stream;
+        ~Retired() { if (tile.pool.p) (void)hipStreamSynchronize(stream); }
+    } old{Tile{}, stream_};
+    if (Tile* ex = find(lat, lon)) { old.tile = std::move(*ex); tiles_.erase(geo_key(lat, lon)); }
+    Tile& nt = tiles_[geo_key(lat, lon)] = std::move(t);
     table_dirty_ = true;
     ++tile_gen_;
     if (int rc = upload_tile_table()) return rc;
@@ -283,10 +274,6 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
         nt.centres[0] = c[0]; nt.centres[1] = c[1]; nt.centres[2] = c[2];
         nt.centres[3] = finite ? std::sqrt(r2) : -1.0;
     }
-    if (had_old) {
-        TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-        free_tile(old);
-    }
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
 }
@@ -314,7 +301,6 @@ int TerrainRenderer::unload_terrain(int32_t lat, int32_t lon) {
     Tile* t = find(lat, lon);
     if (!t) return TOPO_OK;   // BTreeMap::remove of a missing key is a no-op
     if (int rc = wait_all()) return rc;
-    free_tile(*t);
     tiles_.erase(geo_key(lat, lon));
     table_dirty_ = true;
     ++tile_gen_;
@@ -370,7 +356,7 @@ int TerrainRenderer::upload_tile_table() {
         TOPO_HIP_TRY(hipMemcpy(d_tiles_.p, table.data(), table.size() * sizeof(TileDev), hipMemcpyHostToDevice));
         if (vs_ever_) {      // the viewshed's rank -> mask table: ranks shift whenever tiles come and go
             std::vector<uint32_t*> masks;
-            for (auto& kv : tiles_) masks.push_back(kv.second.d_mask);
+            for (auto& kv : tiles_) masks.push_back(kv.second.mask.as<uint32_t>());
             if (int rc = ensure(stream_, d_vs_table_, masks.size() * sizeof(uint32_t*))) return rc;
             TOPO_HIP_TRY(hipMemcpy(d_vs_table_.p, masks.data(), masks.size() * sizeof(uint32_t*), hipMemcpyHostToDevice));
         }
@@ -380,13 +366,11 @@ int TerrainRenderer::upload_tile_table() {
 }
 
 int TerrainRenderer::init_ctx(FrameCtx& c, bool own_stream) {
-    if (!c.done) {
-        for (auto& set : c.evr)
-            for (auto& e : set)
-                if (!e) TOPO_HIP_TRY(hipEventCreate(&e));
-        TOPO_HIP_TRY(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
-    }
-    if (own_stream && !c.stream) TOPO_HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    for (auto& f : c.timed_frames)
+        for (auto& e : f.ev)
+            if (!e) TOPO_HIP_TRY(hipEventCreate(&e.h));
+    if (!c.done) TOPO_HIP_TRY(hipEventCreateWithFlags(&c.done.h, hipEventDisableTiming));
+    if (own_stream && !c.stream) TOPO_HIP_TRY(hipStreamCreateWithFlags(&c.stream.h, hipStreamNonBlocking));
     return TOPO_OK;
 }
 
@@ -430,7 +414,7 @@ void TerrainRenderer::record_bounds(const uint32_t* w) {
 bool TerrainRenderer::fold_idle() {
     bool overflow = false;
     for (auto& c : ctx_)
-        if (!c.pending && c.h_status) overflow |= fold_frames(c);
+        if (!c.pending && c.h_status.p) overflow |= fold_frames(c);
     return overflow;
 }
 
@@ -575,7 +559,7 @@ int TerrainRenderer::grow_frame_buffers(FrameCtx& c, hipStream_t stream, uint32_
         if (int rc = ensure(stream, c.d_counters, 2 * kCounterWords * sizeof(uint32_t))) return rc;      // two sets, alternating
         TOPO_HIP_TRY(hipMemsetAsync(c.d_counters.p, 0, 2 * kCounterWords * sizeof(uint32_t), stream));
     }
-    if (!c.h_status) TOPO_HIP_TRY(hipHostMalloc((void**)&c.h_status, kStatusRing * kStatusWords * sizeof(uint32_t)));
+    if (int rc = ensure_pinned(c.h_status, kStatusRing * kStatusWords * sizeof(uint32_t))) return rc;
     if (c.submitted - c.checked == kStatusRing) {      // nobody has waited for this context's frames for a whole ring: fold them now
         if (c.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(c.last_stream));      // (where the latest of them was queued)
         overflow_pending_ |= fold_frames(c);
@@ -619,12 +603,13 @@ int TerrainRenderer::stage_views(FrameCtx& c, hipStream_t stream, const topo_uni
         if (!*pack_in_cull) launch_put_views(pack, n, d_slot, stream);
         return TOPO_OK;
     }
-    if (!h_views_) {
-        TOPO_HIP_TRY(hipHostMalloc((void**)&h_views_, sizeof(ViewDev) * kMaxViewsPerSlot * kViewSlots));
-        for (int i = 0; i < kViewSlots; ++i) TOPO_HIP_TRY(hipEventCreateWithFlags(&view_ev_[i], hipEventDisableTiming));
+    if (!view_ev_[kViewSlots - 1]) {      // first use (or whatever of it an earlier, failed one left undone)
+        if (int rc = ensure_pinned(h_views_, sizeof(ViewDev) * kMaxViewsPerSlot * kViewSlots)) return rc;
+        for (auto& e : view_ev_)
+            if (!e) TOPO_HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
     }
     if (view_used_[slot]) TOPO_HIP_TRY(hipEventSynchronize(view_ev_[slot]));
-    ViewDev* vd = h_views_ + (size_t)slot * kMaxViewsPerSlot;
+    ViewDev* vd = h_views_.as<ViewDev>() + (size_t)slot * kMaxViewsPerSlot;
     fill_views(vd);
     TOPO_HIP_TRY(hipMemcpyAsync(d_slot, vd, n * sizeof(ViewDev), hipMemcpyHostToDevice, stream));
     TOPO_HIP_TRY(hipEventRecord(view_ev_[slot], stream));
@@ -673,59 +658,54 @@ void TerrainRenderer::fill_params(FrameCtx& c, FrameParams& p) {
 }
 
 // clear -> cull -> [near blocks: raster, rare, big] -> occlusion test of the far blocks -> [survivors: raster,
-// rare, big] -> resolve.  Event slots: 0 clear, 1 cull, 2 raster(near), 3 rare+big(near), 4 occlusion,
-// 5 raster(far), 6 rare+big(far), 7 resolve.
+// rare, big] -> resolve: the stages of `Stage`, event i in front of stage i and the last one behind the frame.
 int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p, const ViewPack* pack_in_cull, bool far_phase, const OutputParams& out,
                                  const ResolveSlot* slots, uint32_t n_slots, const std::function<int(uint32_t, hipStream_t)>* after_slot) {
     const uint32_t n = p.n_views, w = (uint32_t)p.W, h = (uint32_t)p.H;
     uint32_t* const counters_next = c.d_counters.as<uint32_t>() + ((c.frames & 1u) ^ 1u) * kCounterWords;
     // A timing event between two kernels costs ~6 us of idle GPU (the next kernel waits for the marker), so only the
-    // events the selected timing slots need are recorded (topo_set_timing_slots); slot -> stages: 0:{0} 1:{1} 2:{2,5} 3:{4}
-    // 4:{3,6} 5:{7}, stage i = ev[i]..ev[i+1]; the total (ev[0], ev[8]) is always kept.
-    uint32_t ev_need = timing_total_ ? 0x101u : 0u;
-    {
-        static const uint32_t stages_of_slot[6] = {1u << 0, 1u << 1, (1u << 2) | (1u << 5), 1u << 4, (1u << 3) | (1u << 6), 1u << 7};
-        for (int sl = 0; sl < 6; ++sl)
-            if (timing_slots_ & (1u << sl))
-                for (int st = 0; st < 8; ++st)
-                    if (stages_of_slot[sl] & (1u << st)) ev_need |= (3u << st);
-    }
+    // events the selected timing slots need are recorded (topo_set_timing_slots); the total's pair unless that is switched off too.
+    uint32_t ev_need = timing_total_ ? kTotalEvents : 0u;
+    for (int sl = 0; sl < kTimingSlots; ++sl)
+        for (int st = 0; st < kNumStages; ++st)
+            if ((timing_slots_ & (1u << sl)) && (kStagesOfSlot[sl] & (1u << st))) ev_need |= stage_events(st);
     // With nothing but k_resolve's duration and / or the total selected (bench.py's timed region) the events are not markers between
-    // the kernels but the kernels' own start and end times (hipExtLaunchKernel: ev[0] = start of the frame's first kernel, ev[7] /
-    // ev[8] = start / end of k_resolve): a pair of markers costs a frame 8-10 us, these next to nothing.
+    // the kernels but the kernels' own start and end times (hipExtLaunchKernel: the first event = start of the frame's first kernel,
+    // the last two = start / end of k_resolve): a pair of markers costs a frame 8-10 us, these next to nothing.
     const bool pixelize = post_.pixelize_n < 99.99999f;
-    const bool own_times = !switches().events_by_marker && !pixelize && (timing_slots_ & ~(1u << 5)) == 0;
-    const int ring = (int)(c.frames % kEvRing);
-    hipEvent_t* const ev = c.evr[ring];
-    c.evr_recorded[ring] = ev_need;
-    c.evr_slots[ring] = timing_slots_;
-    c.evr_frame[ring] = ++frame_seq_;
-    ++c.frames;
-    if ((ev_need & (1u << 0)) && !own_times) TOPO_HIP_TRY(hipEventRecord(ev[0], stream));
-    const hipEvent_t ev_first = (ev_need & (1u << 0)) && own_times ? ev[0] : nullptr;
+    const bool own_times = !switches().events_by_marker && !pixelize && (ev_need & ~(kTotalEvents | stage_events(kStResolve))) == 0;
+    FrameCtx::TimedFrame& tf = c.timed_frames[c.frames++ % kEvRing];
+    tf.recorded = ev_need;
+    tf.slots = timing_slots_;
+    tf.frame = ++frame_seq_;
+    // event i, if it is needed: a marker on the stream (mark), or -- the three own_times hands to a launch instead -- the kernel's own (own)
+    auto mark = [&](int i, bool may_be_own = false) { return (ev_need >> i & 1u) && !(may_be_own && own_times) ? hipEventRecord(tf.ev[i], stream) : hipSuccess; };
+    auto own = [&](int i) -> hipEvent_t { return (ev_need >> i & 1u) && own_times ? (hipEvent_t)tf.ev[i] : nullptr; };
+    TOPO_HIP_TRY(mark(kStClear, true));
+    const hipEvent_t ev_first = own(kStClear);
     // clear and cull side by side in one launch (timing slot "clear" then holds both, "cull" nothing); TOPO_FUSE_CLEAR_CULL=0 or
     // an empty tile set: one after the other
     const bool fuse = fused_clear_cull(p);
     if (fuse) launch_clear_cull(p, counters_next, stream, ev_first, pack_in_cull, n);
     else launch_clear(p, counters_next, stream, ev_first);
-    if (ev_need & (1u << 1)) TOPO_HIP_TRY(hipEventRecord(ev[1], stream));
+    TOPO_HIP_TRY(mark(kStCull));
     if (!fuse) launch_cull(p, stream);
-    if (ev_need & (1u << 2)) TOPO_HIP_TRY(hipEventRecord(ev[2], stream));
+    TOPO_HIP_TRY(mark(kStRasterNear));
     launch_raster(p, 0, stream);
-    if (ev_need & (1u << 3)) TOPO_HIP_TRY(hipEventRecord(ev[3], stream));
+    TOPO_HIP_TRY(mark(kStRareBigNear));
     launch_raster_rare(p, stream);
     launch_raster_big(p, stream);
-    if (ev_need & (1u << 4)) TOPO_HIP_TRY(hipEventRecord(ev[4], stream));
+    TOPO_HIP_TRY(mark(kStOcclusion));
     if (far_phase) launch_occlusion(p, stream);
-    if (ev_need & (1u << 5)) TOPO_HIP_TRY(hipEventRecord(ev[5], stream));
+    TOPO_HIP_TRY(mark(kStRasterFar));
     if (far_phase) launch_raster(p, 1, stream);
-    if (ev_need & (1u << 6)) TOPO_HIP_TRY(hipEventRecord(ev[6], stream));
+    TOPO_HIP_TRY(mark(kStRareBigFar));
     if (far_phase) {
         launch_raster_rare(p, stream);
         launch_raster_big(p, stream);
     }
-    if ((ev_need & (1u << 7)) && !own_times) TOPO_HIP_TRY(hipEventRecord(ev[7], stream));
-    const hipEvent_t ev_rstart = (ev_need & (1u << 7)) && own_times ? ev[7] : nullptr, ev_rstop = (ev_need & (1u << 8)) && own_times ? ev[8] : nullptr;
+    TOPO_HIP_TRY(mark(kStResolve, true));
+    const hipEvent_t ev_rstart = own(kStResolve), ev_rstop = own(kNumStages);
     // The pixelise branch of the post shader (pixelize_n < 99.99999; the reference never takes it) samples the render target
     // away from the pixel's own texel: k_resolve then stores the render-target texels into an image of the frame context's
     // (post_off) and k_post_pixelize makes the surface image from it and the depth image.  The images belong to the context,
@@ -762,7 +742,7 @@ int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p
     }
     if (vs_on_)      // behind the frame's last k_resolve (and its last slot): the cells that won a pixel, into the tiles' masks
         launch_viewshed(p, d_vs_table_.as<uint32_t* const>(), d_vs_stats_.as<unsigned long long>(), stream);
-    if ((ev_need & (1u << 8)) && !own_times) TOPO_HIP_TRY(hipEventRecord(ev[8], stream));
+    TOPO_HIP_TRY(mark(kNumStages, true));
     if (!p.status_out) TOPO_HIP_TRY(hipMemcpyAsync(c.status_words(c.submitted), p.counters, kStatusWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     return TOPO_OK;
 }
@@ -791,13 +771,10 @@ void TerrainRenderer::record_submission(FrameCtx& c, const FrameParams& p) {
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
 
 int TerrainRenderer::alloc_mask(Tile& t) {
-    TOPO_HIP_TRY(hipMalloc(&t.d_mask, mask_bytes()));
-    const hipError_t e = hipMemsetAsync(t.d_mask, 0, mask_bytes(), stream_);      // (frames on other streams are ordered after stream_)
-    if (e != hipSuccess) {
-        (void)hipFree(t.d_mask);
-        t.d_mask = nullptr;
-        return hip_fail(e, "viewshed mask");
-    }
+    DeviceBuffer m;      // (the tile gets it once it is zeroed)
+    if (int rc = ensure(stream_, m, mask_bytes())) return rc;
+    TOPO_HIP_TRY(hipMemsetAsync(m.p, 0, mask_bytes(), stream_));      // (frames on other streams are ordered after stream_)
+    t.mask = std::move(m);
     return TOPO_OK;
 }
 
@@ -813,7 +790,7 @@ int TerrainRenderer::viewshed_enable(bool on) {
             TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_.p, 0, stats, stream_));
         }
         for (auto& kv : tiles_)
-            if (!kv.second.d_mask)
+            if (!kv.second.mask.p)
                 if (int rc = alloc_mask(kv.second)) return rc;
         vs_ever_ = true;
         table_dirty_ = true;      // the next submission uploads the rank -> mask table with the tile table
@@ -826,7 +803,7 @@ int TerrainRenderer::viewshed_reset() {
     if (int rc = bind_device()) return rc;
     if (!vs_ever_) return TOPO_OK;
     if (int rc = join()) return rc;      // frames in flight on the contexts' own streams; later ones are ordered after stream_
-    for (auto& kv : tiles_) TOPO_HIP_TRY(hipMemsetAsync(kv.second.d_mask, 0, mask_bytes(), stream_));
+    for (auto& kv : tiles_) TOPO_HIP_TRY(hipMemsetAsync(kv.second.mask.p, 0, mask_bytes(), stream_));
     TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_.p, 0, (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long), stream_));
     return TOPO_OK;
 }
@@ -840,7 +817,7 @@ int TerrainRenderer::viewshed_read(int32_t lat, int32_t lon, uint8_t* mask_out, 
     if (pitch < wm1) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
     if (int rc = wait_all()) return rc;
     std::vector<uint32_t> words(mask_bytes() / 4);
-    TOPO_HIP_TRY(hipMemcpy(words.data(), t->d_mask, mask_bytes(), hipMemcpyDeviceToHost));
+    TOPO_HIP_TRY(hipMemcpy(words.data(), t->mask.p, mask_bytes(), hipMemcpyDeviceToHost));
     uint64_t count = 0;
     for (uint32_t x = 0, bit = 0; x < wm1; ++x)      // bit = x (h-1) + y: the cell of the draw id's triangle (triangle_vertices)
         for (uint32_t y = 0; y < hm1; ++y, ++bit) {
@@ -1026,27 +1003,22 @@ int TerrainRenderer::render(uint8_t* rgba, size_t rgba_pitch, float* depth, size
 int TerrainRenderer::download(uint8_t* dst, size_t dst_pitch, const uint8_t* src_dev, size_t row) {
     const size_t span = dst_pitch * (H_ - 1) + row;
     for (const auto& pin : pinned_)
-        if (dst >= pin.first && dst + span <= pin.first + pin.second) {
+        if (dst >= pin.as<uint8_t>() && dst + span <= pin.as<uint8_t>() + pin.cap) {
             TOPO_HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch, src_dev, row, row, H_, hipMemcpyDeviceToHost, stream_));
             TOPO_HIP_TRY(hipStreamSynchronize(stream_));
             return TOPO_OK;
         }
     const size_t total = row * H_;
-    if (total > stage_bytes_) {
-        if (h_stage_) (void)hipHostFree(h_stage_);
-        h_stage_ = nullptr;
-        stage_bytes_ = 0;
-        TOPO_HIP_TRY(hipHostMalloc((void**)&h_stage_, total));
-        stage_bytes_ = total;
-    }
+    if (int rc = ensure_pinned(h_stage_, total)) return rc;
+    uint8_t* const stage = h_stage_.as<uint8_t>();
     constexpr int kSlices = 8;
-    if (!stage_ev_[0])
-        for (auto& e : stage_ev_) TOPO_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : stage_ev_)
+        if (!e) TOPO_HIP_TRY(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
     const uint32_t rows_per = (H_ + kSlices - 1) / kSlices;
     int n_slices = 0;
     for (uint32_t r0 = 0; r0 < H_; r0 += rows_per, ++n_slices) {
         const uint32_t rows = std::min(rows_per, H_ - r0);
-        TOPO_HIP_TRY(hipMemcpyAsync(h_stage_ + (size_t)r0 * row, src_dev + (size_t)r0 * row, (size_t)rows * row, hipMemcpyDeviceToHost, stream_));
+        TOPO_HIP_TRY(hipMemcpyAsync(stage + (size_t)r0 * row, src_dev + (size_t)r0 * row, (size_t)rows * row, hipMemcpyDeviceToHost, stream_));
         TOPO_HIP_TRY(hipEventRecord(stage_ev_[n_slices], stream_));
     }
     const unsigned hw = std::thread::hardware_concurrency();
@@ -1058,9 +1030,9 @@ int TerrainRenderer::download(uint8_t* dst, size_t dst_pitch, const uint8_t* src
             if (hipEventSynchronize(stage_ev_[k]) != hipSuccess) { failed = 1; return; }
             const uint32_t r0 = (uint32_t)k * rows_per, rows = std::min(rows_per, H_ - r0);
             const uint32_t a = r0 + (uint32_t)((uint64_t)rows * t / n_threads), b = r0 + (uint32_t)((uint64_t)rows * (t + 1) / n_threads);
-            if (dst_pitch == row) memcpy(dst + (size_t)a * row, h_stage_ + (size_t)a * row, (size_t)(b - a) * row);
+            if (dst_pitch == row) memcpy(dst + (size_t)a * row, stage + (size_t)a * row, (size_t)(b - a) * row);
             else
-                for (uint32_t r = a; r < b; ++r) memcpy(dst + (size_t)r * dst_pitch, h_stage_ + (size_t)r * row, row);
+                for (uint32_t r = a; r < b; ++r) memcpy(dst + (size_t)r * dst_pitch, stage + (size_t)r * row, row);
         }
     };
     std::vector<std::thread> pool;
@@ -1076,19 +1048,20 @@ int TerrainRenderer::pin_host_buffer(void* p, size_t bytes) {
     if (!p || bytes == 0) return fail(TOPO_ERR_INVALID, "null/empty buffer");
     if (int rc = bind_device()) return rc;
     for (const auto& pin : pinned_)
-        if (pin.first == (uint8_t*)p) return pin.second == bytes ? TOPO_OK : fail(TOPO_ERR_INVALID, "buffer already pinned with another size");
+        if (pin.p == p) return pin.cap == bytes ? TOPO_OK : fail(TOPO_ERR_INVALID, "buffer already pinned with another size");
     TOPO_HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterDefault));
-    pinned_.emplace_back((uint8_t*)p, bytes);
+    pinned_.emplace_back();
+    pinned_.back().p = p;
+    pinned_.back().cap = bytes;
     return TOPO_OK;
 }
 
 int TerrainRenderer::unpin_host_buffer(void* p) {
     for (size_t i = 0; i < pinned_.size(); ++i)
-        if (pinned_[i].first == (uint8_t*)p) {
+        if (pinned_[i].p == p) {
             if (int rc = bind_device()) return rc;
             TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-            TOPO_HIP_TRY(hipHostUnregister(p));
-            pinned_.erase(pinned_.begin() + (long)i);
+            pinned_.erase(pinned_.begin() + (long)i);      // (unregisters it)
             return TOPO_OK;
         }
     return fail(TOPO_ERR_NOT_FOUND, "buffer was not pinned by topo_pin_host_buffer");
@@ -1262,24 +1235,18 @@ int TerrainRenderer::set_queue_caps(uint32_t big_cap, uint32_t rare_cap) {
     return join();
 }
 
-// Durations of the frame whose events are set `ring` of context c (out[0..6]; the frame must have completed).
-int TerrainRenderer::frame_durations(FrameCtx& c, int ring, float out[7]) {
-    hipEvent_t* ev = c.evr[ring];
-    float d[8];
-    for (int i = 0; i < 8; ++i) {
-        d[i] = 0.0f;
-        if ((c.evr_recorded[ring] >> i & 3u) == 3u) TOPO_HIP_TRY(hipEventElapsedTime(&d[i], ev[i], ev[i + 1]));
-    }
-    out[0] = d[0];                // clear
-    out[1] = d[1];                // cull
-    out[2] = d[2] + d[5];         // raster: near blocks + far survivors
-    out[3] = d[4];                // occlusion test
-    out[4] = d[3] + d[6];         // rare + big (both phases)
-    out[5] = d[7];                // resolve
-    for (int sl = 0; sl < 6; ++sl)
-        if (!(c.evr_slots[ring] & (1u << sl))) out[sl] = 0.0f;      // (a neighbour's events may have bracketed it by chance)
-    out[6] = 0.0f;
-    if ((c.evr_recorded[ring] & 0x101u) == 0x101u) TOPO_HIP_TRY(hipEventElapsedTime(&out[6], ev[0], ev[8]));
+// Durations of the frame timed by f (out[0..6]; the frame must have completed): a slot selected for it is the sum of its stages, any
+// other reads 0 (a neighbour's events may have bracketed its stages by chance).
+int TerrainRenderer::frame_durations(const FrameCtx::TimedFrame& f, float out[7]) {
+    for (int sl = 0; sl <= kTimingSlots; ++sl) out[sl] = 0.0f;
+    for (int sl = 0; sl < kTimingSlots; ++sl)
+        for (int st = 0; st < kNumStages; ++st)
+            if ((f.slots & (1u << sl)) && (kStagesOfSlot[sl] & (1u << st)) && (f.recorded & stage_events(st)) == stage_events(st)) {
+                float d = 0.0f;
+                TOPO_HIP_TRY(hipEventElapsedTime(&d, f.ev[st], f.ev[st + 1]));
+                out[sl] += d;
+            }
+    if ((f.recorded & kTotalEvents) == kTotalEvents) TOPO_HIP_TRY(hipEventElapsedTime(&out[kTimingSlots], f.ev[0], f.ev[kNumStages]));
     return TOPO_OK;
 }
 
@@ -1290,10 +1257,10 @@ int TerrainRenderer::get_timings(float out[TOPO_TIMING_SLOTS]) {
     // that reading timings every frame does not wait for the frame just submitted
     FrameCtx& c = ctx_[pipeline_depth_ > 1 ? next_ctx_ : last_ctx_];
     if (c.timed && c.frames) {
-        const int ring = (int)((c.frames - 1) % kEvRing);
-        if (c.evr_recorded[ring] & 0x100u) TOPO_HIP_TRY(hipEventSynchronize(c.evr[ring][8]));
+        const FrameCtx::TimedFrame& f = c.timed_frames[(c.frames - 1) % kEvRing];
+        if (f.recorded & kLastEvent) TOPO_HIP_TRY(hipEventSynchronize(f.ev[kNumStages]));
         else if (c.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(c.last_stream));      // (TOPO_TIMING_NO_TOTAL: no event behind the frame)
-        if (int rc = frame_durations(c, ring, out)) return rc;
+        if (int rc = frame_durations(f, out)) return rc;
     }
     if (load_timed_) {
         TOPO_HIP_TRY(hipEventSynchronize(load_ev_[1]));
@@ -1309,22 +1276,13 @@ int TerrainRenderer::get_timing_history(uint32_t n_frames, float* out_ms, uint32
     *n_out = 0;
     if (!out_ms && n_frames) return fail(TOPO_ERR_INVALID, "null argument");
     if (int rc = wait_all()) return rc;
-    struct Ref { uint64_t frame; int ctx, ring; };
-    std::vector<Ref> refs;
-    for (int ci = 0; ci < kMaxPipeline; ++ci) {
-        FrameCtx& c = ctx_[ci];
-        const uint64_t have = c.frames < (uint64_t)kEvRing ? c.frames : (uint64_t)kEvRing;
-        for (uint64_t k = 0; k < have; ++k) {
-            const int ring = (int)((c.frames - 1 - k) % kEvRing);
-            refs.push_back(Ref{c.evr_frame[ring], ci, ring});
-        }
-    }
-    std::sort(refs.begin(), refs.end(), [](const Ref& a, const Ref& b) { return a.frame < b.frame; });
+    std::vector<const FrameCtx::TimedFrame*> refs;
+    for (const FrameCtx& c : ctx_)
+        for (uint64_t k = 0; k < std::min<uint64_t>(c.frames, kEvRing); ++k) refs.push_back(&c.timed_frames[(c.frames - 1 - k) % kEvRing]);
+    std::sort(refs.begin(), refs.end(), [](const FrameCtx::TimedFrame* a, const FrameCtx::TimedFrame* b) { return a->frame < b->frame; });
     const size_t n = std::min<size_t>(n_frames, refs.size());
-    for (size_t i = 0; i < n; ++i) {
-        const Ref& r = refs[refs.size() - n + i];
-        if (int rc = frame_durations(ctx_[r.ctx], r.ring, out_ms + 7 * i)) return rc;
-    }
+    for (size_t i = 0; i < n; ++i)
+        if (int rc = frame_durations(*refs[refs.size() - n + i], out_ms + 7 * i)) return rc;
     *n_out = (uint32_t)n;
     return TOPO_OK;
 }
@@ -1332,7 +1290,7 @@ int TerrainRenderer::get_timing_history(uint32_t n_frames, float* out_ms, uint32
 int TerrainRenderer::get_counters(uint32_t out[6]) {
     for (int i = 0; i < 6; ++i) out[i] = 0;
     FrameCtx& fc = ctx_[last_ctx_];
-    if (!fc.h_status) return TOPO_OK;
+    if (!fc.h_status.p) return TOPO_OK;
     if (int rc = bind_device()) return rc;
     if (fc.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(fc.last_stream));      // the stream the frame was queued on
     uint32_t c[kStatusWords] = {};

@@ -38,35 +38,58 @@ inline GeoKey geo_key(int lat, int lon) {
     } while (0)
 
 // A block of device memory that only grows (TerrainRenderer::ensure) and goes with its owner.  Owners bind the device and wait
-// for their streams in their destructor's body; the blocks are freed behind it, as members.
-struct DeviceBuffer {
+// for their streams in their destructor's body; the blocks are freed behind it, as members.  The same shape owns pinned host
+// memory (TerrainRenderer::ensure_pinned) and a registration of the caller's memory: non-copyable, movable, null = nothing to release.
+template <hipError_t (*Free)(void*)>
+struct Block {
     void* p = nullptr;
     size_t cap = 0;
-    DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer&) = delete;
-    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
-    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    Block() = default;
+    Block(Block&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    Block& operator=(Block&& o) noexcept { if (this != &o) { reset(); p = std::exchange(o.p, nullptr); cap = std::exchange(o.cap, 0); } return *this; }
+    ~Block() { reset(); }
+    void reset() { if (p) (void)Free(p); p = nullptr; cap = 0; }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+using DeviceBuffer = Block<hipFree>;
+using PinnedBuffer = Block<hipHostFree>;
+using HostRegistration = Block<hipHostUnregister>;      // p, cap: the caller's buffer (hipHostRegister)
+
+// An event or a stream of the host layer's own, owned the same way; reads as the handle wherever HIP wants one.
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(Handle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Handle& operator=(Handle&& o) noexcept { if (this != &o) { reset(); h = std::exchange(o.h, nullptr); } return *this; }
+    ~Handle() { reset(); }
+    void reset() { if (h) (void)Destroy(h); h = nullptr; }
+    operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
 
 // Images of `rows` rows at the given pitches (bytes), one behind the other.
 inline OutputParams image_output(uint8_t* rgba, size_t rgba_pitch, float* depth, size_t depth_pitch, uint32_t rows) {
     return OutputParams{rgba, rgba_pitch * rows, rgba_pitch, depth, depth_pitch * rows, depth_pitch};
 }
 
-struct Tile {          // RenderBuffer (render_buffer.rs:23-31) minus the wgpu plumbing
+struct Tile {          // RenderBuffer (render_buffer.rs:23-31) minus the wgpu plumbing; move-only: it owns its device memory
     int lat = 0, lon = 0;
     uint64_t seq = 0;  // insertion order (for topo_recompute_normals)
+    DeviceBuffer pool;              // the one allocation the three pointers below (and dev) point into
     float* d_heights = nullptr;
     uint32_t* d_normals = nullptr;
     float* d_minmax = nullptr;
-    void* d_pool = nullptr;         // the one allocation the three pointers above point into
     // a sphere around the centres of the tile's block spheres (the cull's load-time table, read back once per tile): lets a
     // submission prove on the host that none of its blocks can be an occlusion-test candidate.  radius < 0: unknown.
     double centres[4] = {0.0, 0.0, 0.0, -1.0};
     TileDev dev{};
-    uint32_t* d_mask = nullptr;     // viewshed: 1 bit per cell (bit x (h-1) + y), once accumulation has been enabled; freed with the tile
+    DeviceBuffer mask;              // viewshed: 1 bit per cell (bit x (h-1) + y), once accumulation has been enabled; goes with the tile
 };
+
+// The eight stages of a frame, in launch order; stage i spans events i .. i + 1 of the frame's TimedFrame.
+enum Stage { kStClear, kStCull, kStRasterNear, kStRareBigNear, kStOcclusion, kStRasterFar, kStRareBigFar, kStResolve, kNumStages };
 
 class TerrainRenderer {
    public:
@@ -136,12 +159,13 @@ class TerrainRenderer {
 
    private:
     TerrainRenderer() = default;
+    int init();                                                   // create(): the stream and the events every renderer has
     int fail(int code, const std::string& msg);
     int hip_fail(hipError_t e, const char* what);
     int bind_device();
     int ensure(hipStream_t s, DeviceBuffer& b, size_t need);      // grows b to `need` bytes; s: the stream to wait for before the old block goes
+    int ensure_pinned(PinnedBuffer& b, size_t need);              // the same for pinned host memory nothing in flight uses
     int wait_all();                                               // join + stream_
-    void free_tile(Tile& t);
     void collect_jobs(const Tile& nt, const std::map<GeoKey, uint32_t>& rank, std::vector<EdgeJob>& edges,
                       std::vector<CornerJob>& corners);   // the seam/corner orchestration of add_terrain
     int run_seam_jobs(const std::vector<EdgeJob>& edges, const std::vector<CornerJob>& corners);
@@ -171,29 +195,31 @@ class TerrainRenderer {
     uint32_t big_cap_cfg_ = 0, rare_cap_cfg_ = 0;
     uint64_t rare_cap_auto_ = 0;           // rare-queue capacity topo_render grew to after an overflow (0 = default)
     uint32_t timing_slots_ = 0x3Fu;        // topo_set_timing_slots: which per-kernel durations to measure
-    bool timing_total_ = true;        // ev[0] and ev[8] (TOPO_TIMING_NO_TOTAL clears it)
+    bool timing_total_ = true;        // a frame's first and last event (TOPO_TIMING_NO_TOTAL clears it)
     float occlusion_split_m_ = 90000.0f;   // flat optimum 60..120 km at c4 (profiles/README.md)
 
-    hipStream_t own_stream_ = nullptr, stream_ = nullptr;
-    static constexpr int kNumEvents = 9;
+    Stream own_stream_;
+    hipStream_t stream_ = nullptr;      // own_stream_, or the caller's (topo_set_stream)
     static constexpr int kEvRing = 32;
     static constexpr uint64_t kStatusRing = 64;
     uint64_t frame_seq_ = 0;          // frames submitted by this renderer
-    hipEvent_t load_ev_[3] = {};      // recompute_normals: start, end, between the tables and the normals
+    Event load_ev_[3];                // recompute_normals: start, end, between the tables and the normals
     bool load_timed_ = false;
 
     // Everything one frame in flight owns.  With pipeline depth 1 (default) there is one context and it runs on
     // stream_; with depth d > 1 topo_render_views_device rotates through d contexts, each on a stream of its own, so
     // that the memory-latency-bound cull/raster phases of one frame run under the ALU-bound resolve of the previous one.
     struct FrameCtx {
-        hipStream_t stream = nullptr;        // own stream (depth > 1)
+        Stream stream;                       // own stream (depth > 1)
         // timing events of the last kEvRing frames of this context (a frame's durations stay readable while later frames are
         // submitted: topo_get_timing_history reads a whole timed region's frames after it, without a wait inside it)
-        hipEvent_t evr[kEvRing][kNumEvents] = {};
-        uint32_t evr_recorded[kEvRing] = {}, evr_slots[kEvRing] = {};
-        uint64_t evr_frame[kEvRing] = {};     // the renderer-wide number of the frame that used the set
+        struct TimedFrame {
+            Event ev[kNumStages + 1];
+            uint32_t recorded = 0, slots = 0;      // the events recorded (bit i: ev[i]); the timing slots selected then
+            uint64_t frame = 0;                    // the renderer-wide number of the frame that used the set
+        } timed_frames[kEvRing];
         uint64_t frames = 0;                  // frames submitted on this context
-        hipEvent_t done = nullptr;
+        Event done;
         // the stream the context's latest frame was queued on: its own stream (depth > 1), stream_ (depth 1, and the slot-by-slot
         // panorama at any depth); null once a wait has covered it.  A context's frames are ordered (a frame on the own stream waits
         // for stream_, the panorama joins the contexts first), so waiting for this stream waits for all of them.
@@ -202,9 +228,9 @@ class TerrainRenderer {
         bool timed = false, pending = false;
         // pinned ring of the last kStatusRing frames' kStatusWords counter words, each stored by its frame's k_resolve (the bounds-checking build: copied out behind it);
         // frames [checked, submitted) have not been looked at by check_frames yet
-        uint32_t* h_status = nullptr;
+        PinnedBuffer h_status;
         uint64_t submitted = 0, checked = 0;
-        uint32_t* status_words(uint64_t frame) const { return h_status + (frame % kStatusRing) * kStatusWords; }
+        uint32_t* status_words(uint64_t frame) const { return h_status.as<uint32_t>() + (frame % kStatusRing) * kStatusWords; }
         const uint32_t* latest_status() const { return status_words(submitted - 1); }
         DeviceBuffer d_vis, d_dirty;      // d_dirty: one mark per 64 visibility keys (kernels_common.h: struct Vis)
         DeviceBuffer d_work, d_work2, d_far, d_big, d_rare, d_counters;
@@ -240,19 +266,18 @@ class TerrainRenderer {
     int queue_frame(FrameCtx& c, hipStream_t s, FrameParams& p, const ViewPack* pack_in_cull, bool far_phase, const OutputParams& out, const ResolveSlot* slots,
                     uint32_t n_slots, const std::function<int(uint32_t, hipStream_t)>* after_slot);
     void record_submission(FrameCtx& c, const FrameParams& p);
-    int frame_durations(FrameCtx& c, int ring, float out[7]);
+    int frame_durations(const FrameCtx::TimedFrame& f, float out[7]);
 
     DeviceBuffer d_tiles_, d_views_, d_edge_jobs_, d_corner_jobs_, d_out_rgba_, d_out_depth_;
     // topo_render's way out to host memory: a pinned staging image and the events of its slices; the buffers the caller pinned
-    uint8_t* h_stage_ = nullptr;
-    size_t stage_bytes_ = 0;
-    hipEvent_t stage_ev_[8] = {};
-    std::vector<std::pair<uint8_t*, size_t>> pinned_;
+    PinnedBuffer h_stage_;
+    Event stage_ev_[8];
+    std::vector<HostRegistration> pinned_;
     int download(uint8_t* dst, size_t dst_pitch, const uint8_t* src_dev, size_t row);
     static constexpr int kViewSlots = 16;
     static constexpr uint32_t kMaxViewsPerSlot = 64;
-    ViewDev* h_views_ = nullptr;          // pinned staging ring
-    hipEvent_t view_ev_[kViewSlots] = {};
+    PinnedBuffer h_views_;                // pinned staging ring
+    Event view_ev_[kViewSlots];
     bool view_used_[kViewSlots] = {};
     DeviceBuffer d_peaks_;            // xyz in, then visible + xy out
     DeviceBuffer d_proj_;
