@@ -25,6 +25,13 @@ int topo_debug_set_queue_caps(topo_ctx* ctx, uint32_t big_cap, uint32_t rare_cap
  * TOPO_FAR_SKIP=0 in the environment always launches it. */
 int topo_debug_far_phase_launched(topo_ctx* ctx, int32_t* out);
 
+/* Test hooks of the cull's tile prefilter: the host drops the (view, tile) pairs whose tile lies wholly outside the view's frustum
+ * and launches the cull over the rest (TOPO_TILE_PREFILTER=0 in the environment: over every pair, as does on = 0 here, from the next
+ * submission on).  topo_debug_cull_pairs: out[0] = pairs the last submission's cull was launched over, out[1] = pairs in all
+ * (views x tiles); equal when the prefilter is off or the kept pairs' list does not fit the launch's arguments. */
+int topo_debug_set_tile_prefilter(topo_ctx* ctx, int32_t on);
+int topo_debug_cull_pairs(topo_ctx* ctx, uint32_t out[2]);
+
 /* Test accessor: what k_viewshed did since accumulation was first enabled or last reset (waits for the frames in flight):
  * out[0] = terrain keys it read, out[1] = mask-word updates left after combining neighbouring lanes, out[2] = atomics issued
  * (updates that set at least one new bit).  All 0 before accumulation was ever enabled. */

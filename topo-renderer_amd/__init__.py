@@ -96,6 +96,8 @@ def lib():
             "topo_set_normals_lds_rows": (C.c_int, [vp, C.c_int]),
             "topo_debug_set_queue_caps": (C.c_int, [vp, u32, u32]),
             "topo_debug_far_phase_launched": (C.c_int, [vp, vp]),
+            "topo_debug_set_tile_prefilter": (C.c_int, [vp, i32]),
+            "topo_debug_cull_pairs": (C.c_int, [vp, vp]),
             "topo_pin_host_buffer": (C.c_int, [vp, vp, sz]),
             "topo_unpin_host_buffer": (C.c_int, [vp, vp]),
             "topo_get_timings": (C.c_int, [vp, vp]),
@@ -550,6 +552,16 @@ class TerrainRenderer:
         out = np.zeros(1, np.int32)
         self._check(lib().topo_debug_far_phase_launched(self._h, _p(out)))
         return bool(out[0])
+
+    def debug_set_tile_prefilter(self, on: bool):
+        """The cull's host-side tile prefilter on / off, from the next submission on (include/topo_hip_test.h)."""
+        self._check(lib().topo_debug_set_tile_prefilter(self._h, 1 if on else 0))
+
+    def debug_cull_pairs(self) -> tuple:
+        """(pairs launched, pairs in all) of the last submission's cull (include/topo_hip_test.h)."""
+        out = np.zeros(2, np.uint32)
+        self._check(lib().topo_debug_cull_pairs(self._h, _p(out)))
+        return int(out[0]), int(out[1])
 
     def timings(self) -> dict:
         out = np.zeros(TIMING_SLOTS, np.float32)

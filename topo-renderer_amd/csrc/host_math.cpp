@@ -235,6 +235,44 @@ void change_location_plan(float latitude, float longitude, float range_dist, con
     }
 }
 
+// Tile prefilter (host_math.hpp).  The planes are k_cull's clip_plane, term for term: 0..3 = w +- x, w +- y, 4 = near
+// (z_clip >= 0), 5 = w - z, each with the norm of its (a, b, c).
+uint32_t tile_prefilter(const topo_uniforms* views, uint32_t n_views, const double* spheres, uint32_t n_tiles, uint16_t* out, uint32_t cap) {
+    uint32_t kept = 0;
+    for (uint32_t v = 0; v < n_views; ++v) {
+        const float* m = views[v].camera_proj;
+        double q[6][5];
+        for (int pl = 0; pl < 6; ++pl) {
+            const int row = pl >> 1;
+            const double sgn = (pl & 1) ? -1.0 : 1.0;
+            double a, b, c, d;
+            if (pl == 4) {
+                a = m[2]; b = m[6]; c = m[10]; d = m[14];
+            } else {
+                a = (double)m[3] + sgn * (double)m[row];
+                b = (double)m[7] + sgn * (double)m[4 + row];
+                c = (double)m[11] + sgn * (double)m[8 + row];
+                d = (double)m[15] + sgn * (double)m[12 + row];
+            }
+            q[pl][0] = a; q[pl][1] = b; q[pl][2] = c; q[pl][3] = d;
+            q[pl][4] = std::sqrt(a * a + b * b + c * c);
+        }
+        for (uint32_t t = 0; t < n_tiles; ++t) {
+            const double* s = spheres + (size_t)t * kTileSphereDoubles;
+            bool outside = false;
+            if (s[3] >= 0.0 && s[4] >= 0.0) {      // (NaN fails both, and every comparison below)
+                const double reach = s[3] + s[4] + 1.0;
+                for (int pl = 0; pl < 6 && !outside; ++pl)
+                    outside = q[pl][0] * s[0] + q[pl][1] * s[1] + q[pl][2] * s[2] + q[pl][3] < -reach * q[pl][4];
+            }
+            if (outside) continue;
+            if (kept < cap) out[kept] = (uint16_t)(v * n_tiles + t);
+            ++kept;
+        }
+    }
+    return kept;
+}
+
 // Synthetic COP90-shaped heights: 5-octave value-noise fBm over global texel coordinates with an integer
 // hash (same definition as topo-renderer_amd/synth.py; f32 ops in the same order).
 namespace {

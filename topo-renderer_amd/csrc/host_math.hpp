@@ -20,6 +20,16 @@ void terrain_rotation(float model_lon_deg, float model_lat_deg, float rot3x3_col
 uint32_t locations_range(float latitude, float longitude, float range_dist, int32_t* out_lat_lon, uint32_t cap);
 void change_location_plan(float latitude, float longitude, float range_dist, const int32_t* loaded, uint32_t n_loaded,
                           std::vector<std::pair<int32_t, int32_t>>& unload, std::vector<std::pair<int32_t, int32_t>>& request);
+// Tile-level frustum prefilter of the cull: which (view, tile) pairs can hold a raster block that the device's frustum test
+// (k_cull: the block's bounding sphere against the six clip planes of camera_proj, f64) keeps.  `spheres`: kTileSphereDoubles
+// doubles per tile, in draw order -- the centre and radius of a sphere around the centres of the tile's block spheres, then the
+// largest radius among those block spheres.  A pair is dropped only when that sphere, grown by the largest block radius and 1 m
+// (the device adds its terms in another order), lies wholly outside one plane: every block of the tile then fails the device's
+// test against the same plane.  An unknown sphere (radius < 0) or anything not finite keeps the pair.  The kept pairs' codes,
+// view * n_tiles + tile, go to out[0 .. cap) in ascending order; returns how many were kept (those beyond cap are not written).
+// Needs n_views * n_tiles <= 65536.  A function of its arguments alone: no HIP, no state.
+constexpr uint32_t kTileSphereDoubles = 5;
+uint32_t tile_prefilter(const topo_uniforms* views, uint32_t n_views, const double* spheres, uint32_t n_tiles, uint16_t* out, uint32_t cap);
 void synth_tile(int32_t lat, int32_t lon, uint32_t w, uint32_t h, uint32_t seed, float* out);
 
 }  // namespace topo

@@ -95,22 +95,53 @@ __device__ __forceinline__ void emit_near(const FrameParams& P, uint32_t view, u
     if (slot < P.near_cap) P.work[slot] = WorkItem{(view << 16) | rank, blk};
 }
 
-__device__ __forceinline__ void cull_body(const FrameParams& P, uint32_t block) {
-    const uint32_t blocks_per_tile = P.bx_count * P.by_count;
-    const size_t total = (size_t)P.n_views * P.n_tiles * blocks_per_tile;
-    const size_t gid0 = (size_t)block * blockDim.x, gid = gid0 + threadIdx.x;
+// Which (view, tile, block) a cull lane works on.  Full grid (wgs_per_pair == 0): lane g of the launch is triple g, views outermost.
+// Pair list (the host's tile prefilter, host_math.hpp: tile_prefilter): workgroup b takes blocks [256 (b % wgs_per_pair), + 256) of
+// kept pair b / wgs_per_pair; `pairs`: the list in the launch's argument segment, two 16-bit codes (view * n_tiles + rank) per word.
+struct CullMap {
+    uint32_t blocks_per_tile, wgs_per_pair;
+    size_t gid0;                // full grid: the workgroup's first triple
+    uint32_t view, rank, blk0;  // pair list: the workgroup's pair and first block
+    __device__ __forceinline__ CullMap(const FrameParams& P, uint32_t block, const_space_ptr<uint32_t> pairs, uint32_t wgs_per_pair_)
+        : blocks_per_tile(P.bx_count * P.by_count), wgs_per_pair(wgs_per_pair_), gid0((size_t)block * 256), view(0), rank(0), blk0(0) {
+        if (wgs_per_pair) {
+            const uint32_t pair = block / wgs_per_pair;
+            const uint32_t word = TOPO_CHK(P.counters, pair < kMaxCullPairs, 18u, pair) ? pairs[pair >> 1] : 0u;
+            uint32_t code = (word >> ((pair & 1u) * 16u)) & 0xFFFFu;
+            if (!TOPO_CHK(P.counters, code < P.n_views * P.n_tiles, 18u, code)) code = 0u;
+            view = code / P.n_tiles; rank = code % P.n_tiles;
+            blk0 = (block % wgs_per_pair) * 256u;
+        } else {
+            view = (uint32_t)(gid0 / ((size_t)blocks_per_tile * P.n_tiles));      // the first view the workgroup can meet
+        }
+    }
+    // lane `t` of the workgroup: its triple; false: past the end
+    __device__ __forceinline__ bool locate(const FrameParams& P, uint32_t t, uint32_t& v, uint32_t& r, uint32_t& b) const {
+        if (wgs_per_pair) {
+            v = view; r = rank; b = blk0 + t;
+            return b < blocks_per_tile;
+        }
+        const size_t g = gid0 + t;
+        b = (uint32_t)(g % blocks_per_tile);
+        r = (uint32_t)((g / blocks_per_tile) % P.n_tiles);
+        v = (uint32_t)(g / ((size_t)blocks_per_tile * P.n_tiles));
+        return g < (size_t)P.n_views * P.n_tiles * blocks_per_tile;
+    }
+};
+
+__device__ __forceinline__ void cull_body(const FrameParams& P, uint32_t block, const_space_ptr<uint32_t> pairs, uint32_t wgs_per_pair) {
+    const CullMap map(P, block, pairs, wgs_per_pair);
+    const uint32_t blocks_per_tile = map.blocks_per_tile;
     // the six clip planes (and their norms) of the first two views this workgroup can meet, once per workgroup
     __shared__ double s_plane[2][6][5];
     __shared__ uint32_t s_far[256], s_nfar;      // lanes whose block is an occlusion-test candidate
-    const uint32_t view0 = (uint32_t)(gid0 / ((size_t)blocks_per_tile * P.n_tiles));
+    const uint32_t view0 = map.view;
     if (threadIdx.x < 12 && view0 + threadIdx.x / 6 < P.n_views) clip_plane(P.views[view0 + threadIdx.x / 6].proj, threadIdx.x % 6, s_plane[threadIdx.x / 6][threadIdx.x % 6]);
     if (threadIdx.x == 0) s_nfar = 0;
     __syncthreads();
     // ---- phase A, one lane per (view, tile, block): frustum test, then near / far classification
-    if (gid < total) {
-        const uint32_t blk = (uint32_t)(gid % blocks_per_tile);
-        const uint32_t rank = (uint32_t)((gid / blocks_per_tile) % P.n_tiles);
-        const uint32_t view = (uint32_t)(gid / ((size_t)blocks_per_tile * P.n_tiles));
+    uint32_t blk, rank, view;
+    if (map.locate(P, threadIdx.x, view, rank, blk)) {
         const TileDev& t = P.tiles[rank];
         const double hmin = (double)t.block_minmax[2 * blk], hmax = (double)t.block_minmax[2 * blk + 1];
         const double* bs = t.block_bounds + (size_t)blk * 4;      // bounding sphere from the load phase
@@ -146,10 +177,7 @@ __device__ __forceinline__ void cull_body(const FrameParams& P, uint32_t block) 
     // ---- phase B, one lane per candidate (they are ~10 % of the lanes, scattered: handled in place, every wave would
     // pay for the f64 projection of the eight slab corners)
     for (uint32_t i = threadIdx.x; i < s_nfar; i += blockDim.x) {
-        const size_t g = gid0 + s_far[i];
-        const uint32_t blk = (uint32_t)(g % blocks_per_tile);
-        const uint32_t rank = (uint32_t)((g / blocks_per_tile) % P.n_tiles);
-        const uint32_t view = (uint32_t)(g / ((size_t)blocks_per_tile * P.n_tiles));
+        (void)map.locate(P, s_far[i], view, rank, blk);
         const TileDev& t = P.tiles[rank];
         const double hmin = (double)t.block_minmax[2 * blk], hmax = (double)t.block_minmax[2 * blk + 1];
         const double* bb = t.block_bounds + (size_t)blocks_per_tile * 4 + (size_t)blk * 12;   // corner directions
@@ -198,7 +226,17 @@ __device__ __forceinline__ void cull_body(const FrameParams& P, uint32_t block) 
     }
 }
 
-__global__ __launch_bounds__(256) void k_cull(FrameParams P) { cull_body(P, blockIdx.x); }
+// The kept (view, tile) pairs of a submission, as the launch's argument segment carries them (wgs_per_pair != 0): up to kMaxCullPairs
+// 16-bit codes.  With the ViewPack beside it the segment stays well inside the 4 KB a launch may pass.
+struct CullPairs { uint16_t code[kMaxCullPairs]; };
+struct CullArgs {               // k_cull's parameter list as the argument segment lays it out
+    FrameParams P;
+    uint32_t wgs_per_pair;
+    CullPairs pairs;
+};
+__global__ __launch_bounds__(256) void k_cull(FrameParams P, uint32_t wgs_per_pair, CullPairs pairs) {
+    cull_body(P, blockIdx.x, kernarg<uint32_t>(offsetof(CullArgs, pairs)), wgs_per_pair);
+}
 // The clear and the cull of a frame in ONE launch: they share nothing (the clear rewrites visibility keys and zeroes the NEXT
 // frame's counters, the cull reads the load-time tables and appends through this frame's counters), one is bound by its
 // stores, the other by f64 arithmetic and gathers -- side by side they take what the clear takes alone (c4: 0.046 + 0.031 ->
@@ -206,16 +244,22 @@ __global__ __launch_bounds__(256) void k_cull(FrameParams P) { cull_body(P, bloc
 // `pack_words` != 0: the submission's view constants ride in this launch's own argument segment (`pack`: up to kPackViews views, 22
 // words each).  The cull reads them there -- the segment is ordinary device-visible memory behind a constant-address-space pointer --
 // and the launch's first workgroup copies them into the device slot the frame's later kernels read (P.views): no upload in front of
-// the frame, not even a kernel's.
+// the frame, not even a kernel's.  n_cull_blocks may be 0 (no pair survived the prefilter): the launch is the clear alone.
 struct ClearCullArgs {          // the kernel's parameter list as the argument segment lays it out (natural alignment, in order)
     FrameParams P;
     uint32_t n_cull_blocks, n_clear_blocks;
     uint32_t* zero;
     ViewPack pack;
     uint32_t pack_words;
+    uint32_t wgs_per_pair;
+    CullPairs pairs;
 };
+static_assert(sizeof(ClearCullArgs) <= 3584 && sizeof(CullArgs) <= 3584, "a launch's argument segment holds 4 KB, the hidden arguments included");
+static_assert(offsetof(ClearCullArgs, pairs) % 4 == 0 && offsetof(CullArgs, pairs) % 4 == 0, "the pair list is read in words");
+// (the offsets the code object's metadata gives for the two kernels' arguments: tools/kernel_resources.py leaves the object to read them from)
+static_assert(offsetof(ClearCullArgs, pack) == 232 && offsetof(ClearCullArgs, pairs) == 944 && offsetof(CullArgs, pairs) == 220, "the argument segment's layout");
 __global__ __launch_bounds__(256) void k_clear_cull(FrameParams P, uint32_t n_cull_blocks, uint32_t n_clear_blocks, uint32_t* __restrict__ zero, ViewPack pack,
-                                                    uint32_t pack_words) {
+                                                    uint32_t pack_words, uint32_t wgs_per_pair, CullPairs pairs) {
     if (pack_words) {
         const auto src = kernarg<uint32_t>(offsetof(ClearCullArgs, pack));
         if (blockIdx.x == 0 && threadIdx.x < pack_words) const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(P.views))[threadIdx.x] = src[threadIdx.x];
@@ -226,7 +270,7 @@ __global__ __launch_bounds__(256) void k_clear_cull(FrameParams P, uint32_t n_cu
     const uint32_t total = n_cull_blocks + n_clear_blocks;
     const uint32_t before = (uint32_t)((uint64_t)blockIdx.x * n_clear_blocks / total), upto = (uint32_t)((uint64_t)(blockIdx.x + 1u) * n_clear_blocks / total);
     if (upto > before) clear_body(P.vis, P.dirty, (size_t)P.n_views * P.W * P.H, P.counters, zero, before, n_clear_blocks);
-    else cull_body(P, blockIdx.x - before);
+    else cull_body(P, blockIdx.x - before, kernarg<uint32_t>(offsetof(ClearCullArgs, pairs)), wgs_per_pair);
 }
 
 // One wave per far candidate: the block is dropped iff EVERY pixel of its footprint already holds a depth below

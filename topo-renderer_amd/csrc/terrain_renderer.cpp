@@ -23,6 +23,7 @@ struct Switches {
     const bool far_skip = env("TOPO_FAR_SKIP", 1) != 0;
     const bool events_by_marker = env("TOPO_EVENTS_BY_MARKER", 0) != 0;
     const bool fuse_clear_cull = env("TOPO_FUSE_CLEAR_CULL", 1) != 0;
+    const bool tile_prefilter = env("TOPO_TILE_PREFILTER", 1) != 0;
     const int near_strip = env("TOPO_NEAR_STRIP", 0);      // 1..15; anything else: the default
 };
 const Switches& switches() { static const Switches s; return s; }
@@ -89,6 +90,7 @@ int TerrainRenderer::init() {
     TOPO_HIP_TRY(hipSetDevice(device_));
     TOPO_HIP_TRY(hipStreamCreate(&own_stream_.h));
     stream_ = own_stream_;
+    tile_prefilter_ = switches().tile_prefilter;
     for (auto& e : load_ev_) TOPO_HIP_TRY(hipEventCreate(&e.h));
     return init_ctx(ctx_[0], false);
 }
@@ -260,11 +262,12 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
     {   // the sphere around the block spheres' centres (see Tile::centres); any non-finite entry leaves it unknown
         std::vector<double> sph((size_t)bxc * byc * 4);
         TOPO_HIP_TRY(hipMemcpy(sph.data(), nt.dev.block_bounds, sph.size() * sizeof(double), hipMemcpyDeviceToHost));
-        double c[3] = {0.0, 0.0, 0.0}, r2 = 0.0;
+        double c[3] = {0.0, 0.0, 0.0}, r2 = 0.0, rmax = 0.0;
         bool finite = true;
         for (size_t i = 0; i < sph.size(); i += 4) {
             finite = finite && std::isfinite(sph[i]) && std::isfinite(sph[i + 1]) && std::isfinite(sph[i + 2]) && std::isfinite(sph[i + 3]);
             for (int k = 0; k < 3; ++k) c[k] += sph[i + k];
+            rmax = std::max(rmax, sph[i + 3]);
         }
         for (int k = 0; k < 3; ++k) c[k] /= (double)(sph.size() / 4);
         for (size_t i = 0; i < sph.size() && finite; i += 4) {
@@ -273,6 +276,7 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
         }
         nt.centres[0] = c[0]; nt.centres[1] = c[1]; nt.centres[2] = c[2];
         nt.centres[3] = finite ? std::sqrt(r2) : -1.0;
+        nt.block_radius = finite ? rmax : -1.0;
     }
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
@@ -513,10 +517,35 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     fill_params(c, p);
     last_blocks_tested_ = p.work_cap;
     last_far_phase_ = p.split_m > 0.0f && !(switches().far_skip && far_phase_empty(views, n, tiles_, &p.split_m));
-    if (int rc = queue_frame(c, stream, p, pack_in_cull ? &pack : nullptr, last_far_phase_, out, slots, n_slots, after_slot)) return rc;
+    const CullList cull = cull_pairs(views, p);
+    if (int rc = queue_frame(c, stream, p, pack_in_cull ? &pack : nullptr, cull, last_far_phase_, out, slots, n_slots, after_slot)) return rc;
     record_submission(c, p);
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
+}
+
+// The (view, tile) pairs the cull is launched over: those the host's prefilter keeps (host_math.hpp: tile_prefilter), when the
+// prefilter is on (TOPO_TILE_PREFILTER=0, topo_debug_set_tile_prefilter: off) and their list fits the launch's argument segment;
+// otherwise every pair, as the full grid (`codes` null).  The tiles' spheres are gathered once per tile set.
+TerrainRenderer::CullList TerrainRenderer::cull_pairs(const topo_uniforms* views, const FrameParams& p) {
+    const size_t all = (size_t)p.n_views * p.n_tiles;
+    last_cull_pairs_[0] = last_cull_pairs_[1] = (uint32_t)all;
+    CullList list{nullptr, 0};
+    if (!tile_prefilter_ || all == 0 || all > 65536) return list;
+    if (tile_spheres_gen_ != tile_gen_) {
+        tile_spheres_.clear();
+        for (const auto& kv : tiles_) {
+            tile_spheres_.insert(tile_spheres_.end(), kv.second.centres, kv.second.centres + 4);
+            tile_spheres_.push_back(kv.second.block_radius);
+        }
+        tile_spheres_gen_ = tile_gen_;
+    }
+    const uint32_t kept = tile_prefilter(views, p.n_views, tile_spheres_.data(), p.n_tiles, cull_codes_, kMaxCullPairs);
+    if (kept > kMaxCullPairs) return list;
+    last_cull_pairs_[0] = kept;
+    list.codes = cull_codes_;
+    list.n = kept;
+    return list;
 }
 
 // Sizes the frame's queues and lists (into p) and grows the context's buffers to them; the status ring of the context.
@@ -551,7 +580,7 @@ int TerrainRenderer::grow_frame_buffers(FrameCtx& c, hipStream_t stream, uint32_
     if (int rc = ensure(stream, c.d_work, (near_cap ? near_cap : 1) * sizeof(WorkItem))) return rc;
     if (int rc = ensure(stream, c.d_work2, (near_cap ? near_cap : 1) * sizeof(WorkItem))) return rc;   // far survivors, in strips too
     // the far-candidate list: kFarLists sub-lists, cull workgroup b (256 blocks) appending to sub-list b % kFarLists
-    const size_t far_sub_cap = ((work_cap + 255) / 256 + kFarLists - 1) / kFarLists * 256;
+    const size_t far_sub_cap = (cull_workgroups_max(n, p.n_tiles, p.bx_count * p.by_count) + kFarLists - 1) / kFarLists * 256;
     if (int rc = ensure(stream, c.d_far, (far_sub_cap ? far_sub_cap * kFarLists : 1) * sizeof(FarItem))) return rc;
     if (int rc = ensure(stream, c.d_big, p.big_cap * sizeof(BigItem))) return rc;
     if (int rc = ensure(stream, c.d_rare, p.rare_cap * sizeof(RareItem))) return rc;
@@ -659,7 +688,7 @@ void TerrainRenderer::fill_params(FrameCtx& c, FrameParams& p) {
 
 // clear -> cull -> [near blocks: raster, rare, big] -> occlusion test of the far blocks -> [survivors: raster,
 // rare, big] -> resolve: the stages of `Stage`, event i in front of stage i and the last one behind the frame.
-int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p, const ViewPack* pack_in_cull, bool far_phase, const OutputParams& out,
+int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p, const ViewPack* pack_in_cull, const CullList& cull, bool far_phase, const OutputParams& out,
                                  const ResolveSlot* slots, uint32_t n_slots, const std::function<int(uint32_t, hipStream_t)>* after_slot) {
     const uint32_t n = p.n_views, w = (uint32_t)p.W, h = (uint32_t)p.H;
     uint32_t* const counters_next = c.d_counters.as<uint32_t>() + ((c.frames & 1u) ^ 1u) * kCounterWords;
@@ -686,10 +715,10 @@ int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p
     // clear and cull side by side in one launch (timing slot "clear" then holds both, "cull" nothing); TOPO_FUSE_CLEAR_CULL=0 or
     // an empty tile set: one after the other
     const bool fuse = fused_clear_cull(p);
-    if (fuse) launch_clear_cull(p, counters_next, stream, ev_first, pack_in_cull, n);
+    if (fuse) launch_clear_cull(p, counters_next, stream, ev_first, pack_in_cull, n, cull.codes, cull.n);
     else launch_clear(p, counters_next, stream, ev_first);
     TOPO_HIP_TRY(mark(kStCull));
-    if (!fuse) launch_cull(p, stream);
+    if (!fuse) launch_cull(p, stream, cull.codes, cull.n);
     TOPO_HIP_TRY(mark(kStRasterNear));
     launch_raster(p, 0, stream);
     TOPO_HIP_TRY(mark(kStRareBigNear));

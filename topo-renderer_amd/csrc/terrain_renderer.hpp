@@ -84,6 +84,7 @@ struct Tile {          // RenderBuffer (render_buffer.rs:23-31) minus the wgpu p
     // a sphere around the centres of the tile's block spheres (the cull's load-time table, read back once per tile): lets a
     // submission prove on the host that none of its blocks can be an occlusion-test candidate.  radius < 0: unknown.
     double centres[4] = {0.0, 0.0, 0.0, -1.0};
+    double block_radius = -1.0;     // the largest radius among those block spheres (read back with them); < 0: unknown
     TileDev dev{};
     DeviceBuffer mask;              // viewshed: 1 bit per cell (bit x (h-1) + y), once accumulation has been enabled; goes with the tile
 };
@@ -100,6 +101,8 @@ class TerrainRenderer {
                     const float rp[2], const float mp[2], const float ps[2]);
     int unload_terrain(int32_t lat, int32_t lon);
     bool last_far_phase() const { return last_far_phase_; }
+    void set_tile_prefilter(bool on) { tile_prefilter_ = on; }                                                 // test hook
+    void last_cull_pairs(uint32_t out[2]) const { out[0] = last_cull_pairs_[0]; out[1] = last_cull_pairs_[1]; }   // test hook: pairs launched, pairs in all
     int update(uint32_t w, uint32_t h, const topo_uniforms* u, const topo_post_uniforms* pu);
     int render(uint8_t* rgba, size_t rgba_pitch, float* depth, size_t depth_pitch);
     int render_views_device(uint32_t n, const topo_uniforms* views, uint32_t w, uint32_t h, const OutputParams& out);
@@ -263,8 +266,10 @@ class TerrainRenderer {
     int grow_frame_buffers(FrameCtx& c, hipStream_t s, uint32_t n, uint32_t w, uint32_t h, FrameParams& p);
     int stage_views(FrameCtx& c, hipStream_t s, const topo_uniforms* views, FrameParams& p, ViewPack& pack, bool* pack_in_cull);
     void fill_params(FrameCtx& c, FrameParams& p);
-    int queue_frame(FrameCtx& c, hipStream_t s, FrameParams& p, const ViewPack* pack_in_cull, bool far_phase, const OutputParams& out, const ResolveSlot* slots,
-                    uint32_t n_slots, const std::function<int(uint32_t, hipStream_t)>* after_slot);
+    struct CullList { const uint16_t* codes; uint32_t n; };      // the kept (view, tile) pairs; codes null: every pair (the full grid)
+    CullList cull_pairs(const topo_uniforms* views, const FrameParams& p);
+    int queue_frame(FrameCtx& c, hipStream_t s, FrameParams& p, const ViewPack* pack_in_cull, const CullList& cull, bool far_phase, const OutputParams& out,
+                    const ResolveSlot* slots, uint32_t n_slots, const std::function<int(uint32_t, hipStream_t)>* after_slot);
     void record_submission(FrameCtx& c, const FrameParams& p);
     int frame_durations(const FrameCtx::TimedFrame& f, float out[7]);
 
@@ -288,6 +293,13 @@ class TerrainRenderer {
     uint32_t depth_w_ = 0, depth_h_ = 0;
     uint32_t last_blocks_tested_ = 0;
     bool last_far_phase_ = true;           // whether the last submission launched the far phase (test hook)
+    // the cull's tile prefilter: on / off, the tiles' spheres (kTileSphereDoubles each, draw order) and the tile set they were gathered
+    // from, the last submission's kept pairs (the launch copies them) and its counts (pairs launched, pairs in all: test hook)
+    bool tile_prefilter_ = true;
+    std::vector<double> tile_spheres_;
+    uint64_t tile_spheres_gen_ = ~0ull;
+    uint16_t cull_codes_[kMaxCullPairs] = {};
+    uint32_t last_cull_pairs_[2] = {0, 0};
     // viewshed: render_frame launches k_viewshed while vs_on_; the masks exist (every tile has one) once vs_ever_.  The masks are shared
     // by every frame context: frames in flight only OR into them, so they need no order among themselves.
     bool vs_on_ = false, vs_ever_ = false;

@@ -134,6 +134,19 @@ int topo_debug_far_phase_launched(topo_ctx* ctx, int32_t* out) {
     return TOPO_OK;
 }
 
+int topo_debug_set_tile_prefilter(topo_ctx* ctx, int32_t on) {
+    TOPO_GUARD(ctx);
+    ctx->r->set_tile_prefilter(on != 0);
+    return TOPO_OK;
+}
+
+int topo_debug_cull_pairs(topo_ctx* ctx, uint32_t out[2]) {
+    TOPO_GUARD(ctx);
+    if (!out) return TOPO_ERR_INVALID;
+    ctx->r->last_cull_pairs(out);
+    return TOPO_OK;
+}
+
 int topo_get_timings(topo_ctx* ctx, float out_ms[TOPO_TIMING_SLOTS]) {
     TOPO_GUARD(ctx);
     TOPO_CALL(ctx->r->get_timings(out_ms));

@@ -137,9 +137,16 @@ struct ViewPack { ViewDev v[kPackViews]; };
 void launch_put_views(const ViewPack& pack, uint32_t n, ViewDev* dst, hipStream_t s);
 // (`start` / `stop`, where a launcher has them: events that take the kernel's own start / end time -- hipExtLaunchKernel: the
 // dispatch's completion signal carries both, no marker packet stands between two kernels)
+// The cull's grid: every (view, tile) pair (`pairs` null), or the n_pairs <= kMaxCullPairs pairs the host's tile prefilter kept
+// (host_math.hpp: tile_prefilter), each a 16-bit code view * n_tiles + rank; the list travels in the launch's argument segment.
+// n_pairs == 0: nothing to cull (launch_clear_cull still clears).
+constexpr uint32_t kMaxCullPairs = 1024;
 void launch_clear(const FrameParams& p, uint32_t* zero, hipStream_t s, hipEvent_t start = nullptr);        // re-initialises the marked segments
-void launch_clear_cull(const FrameParams& p, uint32_t* zero, hipStream_t s, hipEvent_t start = nullptr, const ViewPack* pack = nullptr, uint32_t n_pack_views = 0);   // the clear and the cull in one launch, side by side
-void launch_cull(const FrameParams& p, hipStream_t s);
+void launch_clear_cull(const FrameParams& p, uint32_t* zero, hipStream_t s, hipEvent_t start = nullptr, const ViewPack* pack = nullptr, uint32_t n_pack_views = 0,
+                       const uint16_t* pairs = nullptr, uint32_t n_pairs = 0);   // the clear and the cull in one launch, side by side
+void launch_cull(const FrameParams& p, hipStream_t s, const uint16_t* pairs = nullptr, uint32_t n_pairs = 0);
+// workgroups of the cull (256 raster blocks each) for a submission's shape: the larger of the two grids, which sizes the far sub-lists
+size_t cull_workgroups_max(uint32_t n_views, uint32_t n_tiles, uint32_t blocks_per_tile);
 void launch_raster(const FrameParams& p, int phase, hipStream_t s);   // phase 0: near list, 1: far survivors
 void launch_occlusion(const FrameParams& p, hipStream_t s);
 void launch_raster_rare(const FrameParams& p, hipStream_t s);

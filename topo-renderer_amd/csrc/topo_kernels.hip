@@ -17,7 +17,9 @@
 //
 // One translation unit on purpose: the kernels share force-inlined helpers, and splitting the unit changes the code that comes out.
 // Compiled with -ffp-contract=off: results must match the arithmetic spec bit for bit.
+#include <algorithm>
 #include <atomic>
+#include <cstring>
 
 #include "kernels_common.h"
 #include "kernels_load.h"
@@ -151,19 +153,44 @@ void launch_put_views(const ViewPack& pack, uint32_t n, ViewDev* dst, hipStream_
     hipLaunchKernelGGL(k_put_views, dim3(1), dim3(256), 0, s, pack, n * (uint32_t)(sizeof(ViewDev) / 4), (uint32_t*)dst);
 }
 
-void launch_clear_cull(const FrameParams& p, uint32_t* zero, hipStream_t s, hipEvent_t start, const ViewPack* pack, uint32_t n_pack_views) {
-    const size_t total = (size_t)p.n_views * p.n_tiles * p.bx_count * p.by_count;
-    const unsigned n_cull = (unsigned)((total + 255) / 256), n_clear = 2048;
+// The cull's grid and pair list as its two launchers pass them.
+namespace {
+struct CullGrid {
+    unsigned n_blocks;
+    uint32_t wgs_per_pair;      // 0: the full grid
+    CullPairs list{};
+    CullGrid(const FrameParams& p, const uint16_t* pairs, uint32_t n_pairs) {
+        const uint32_t blocks_per_tile = p.bx_count * p.by_count;
+        if (pairs && n_pairs <= kMaxCullPairs && blocks_per_tile) {
+            wgs_per_pair = (blocks_per_tile + 255) / 256;
+            n_blocks = n_pairs * wgs_per_pair;
+            memcpy(list.code, pairs, n_pairs * sizeof(uint16_t));
+        } else {
+            wgs_per_pair = 0;
+            n_blocks = (unsigned)(((size_t)p.n_views * p.n_tiles * blocks_per_tile + 255) / 256);
+        }
+    }
+};
+}  // namespace
+size_t cull_workgroups_max(uint32_t n_views, uint32_t n_tiles, uint32_t blocks_per_tile) {
+    const size_t pairs = (size_t)n_views * n_tiles;
+    return std::max((pairs * blocks_per_tile + 255) / 256, pairs * ((blocks_per_tile + 255) / 256));
+}
+
+void launch_clear_cull(const FrameParams& p, uint32_t* zero, hipStream_t s, hipEvent_t start, const ViewPack* pack, uint32_t n_pack_views, const uint16_t* pairs,
+                       uint32_t n_pairs) {
+    const CullGrid g(p, pairs, n_pairs);
+    const unsigned n_clear = 2048;
     static const ViewPack none{};
     const ViewPack& pk = pack ? *pack : none;
     const uint32_t words = pack ? n_pack_views * (uint32_t)(sizeof(ViewDev) / 4) : 0u;
-    launch_timed(k_clear_cull, dim3(n_cull + n_clear), dim3(256), s, start, nullptr, p, n_cull, n_clear, zero, pk, words);
+    launch_timed(k_clear_cull, dim3(g.n_blocks + n_clear), dim3(256), s, start, nullptr, p, g.n_blocks, n_clear, zero, pk, words, g.wgs_per_pair, g.list);
 }
 
-void launch_cull(const FrameParams& p, hipStream_t s) {
-    const size_t total = (size_t)p.n_views * p.n_tiles * p.bx_count * p.by_count;
-    if (total == 0) return;
-    hipLaunchKernelGGL(k_cull, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
+void launch_cull(const FrameParams& p, hipStream_t s, const uint16_t* pairs, uint32_t n_pairs) {
+    const CullGrid g(p, pairs, n_pairs);
+    if (g.n_blocks == 0) return;
+    hipLaunchKernelGGL(k_cull, dim3(g.n_blocks), dim3(256), 0, s, p, g.wgs_per_pair, g.list);
 }
 
 void launch_raster(const FrameParams& p, int phase, hipStream_t s) {
