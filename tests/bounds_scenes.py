@@ -57,6 +57,10 @@ def run(T):
     host_frame("mosaic3x3", Scene(48, 3, 3), 160, 96, 200, 30, 79.28)
     host_frame("below_surface", Scene(64, 2, 2, eye_dh=-300.0), 128, 128, 40, 10, 60)
     host_frame("far_above", Scene(64, 2, 2, eye_dh=250000.0), 128, 128, 40, 89, 60)
+    import void_scenes                                          # tiles with holes in them: NaN, -inf and GDAL's float nodata
+    for value in ("nan", "ninf", "fmin"):
+        _, void, W, H, pose = void_scenes.relief_case("ne_2x2", value)
+        host_frame("void_" + value, void, W, H, *pose)
 
     # device entry points: a 64-view submission, then frames in flight, then a full-size config-2 panorama
     def strip(r, views, sw, sh):

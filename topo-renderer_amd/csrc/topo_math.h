@@ -98,6 +98,17 @@ TOPO_HD float div_by(float x, Recip d) {
 #endif
 }
 TOPO_HD float div_f(float x, float y) { return div_by(x, recip_of(y)); }
+// The same quotient where a void height ("Void heights") can push the divisor out of that range -- GDAL's nodata
+// -3.4e38 puts a vertex 1e38 m away: w_clip, and the z_clip difference of an edge that ends there.  Beyond 2^+-96 (and for a
+// NaN) the core is not the IEEE quotient (the reciprocal estimate of a divisor above 2^126 is flushed to zero, that of an
+// infinity turns the refinement into NaN), so those divisors take the compiler's full division; all others the core, as before.
+TOPO_HD float div_wide(float x, float y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float ay = fabsf(y);
+    if (__builtin_expect(!(ay <= 0x1p+96f && ay >= 0x1p-96f), 0)) return x / y;
+#endif
+    return div_f(x, y);
+}
 // sqrt(x), correctly rounded: the hardware estimate (1 ulp) moved to whichever neighbour the two residuals pick,
 // i.e. the compiler's own expansion of sqrtf without its input scaling (x is 0.01 .. 1e15 on this path).
 TOPO_HD float sqrt_f(float x) {
@@ -272,7 +283,18 @@ TOPO_HD uint32_t normal_texel(float x, float y, float hT, float hL, float hR, fl
 #if defined(__HIP_DEVICE_COMPILE__)
     // dxv.y and dyv.x are exact zeros, so with finite heights cross3's products by them are zeros too and each component
     // is a single product (up to the sign of a zero component, which the + 1 below erases): same texel, 5 operations for 9
-    f3 n = normalize3(f3{-(dxv.z * dyv.y), -(dxv.x * dyv.z), dxv.x * dyv.y});
+    f3 n = {-(dxv.z * dyv.y), -(dxv.x * dyv.z), dxv.x * dyv.y};
+    const float d2 = dot3(n, n);
+    if (__builtin_expect(d2 >= 1.0e-30f && d2 <= 1.0e30f, 1)) {
+        n = normalize3(n);
+    } else {
+        // a void height among the four ("Void heights"): the squared length overflows, is NaN or vanishes, outside the
+        // range of normalize3's division core.  The full cross product (an infinite difference times an exact zero is NaN)
+        // and IEEE square root and quotients, as the shader's normalize() spells out.
+        n = cross3(dxv, dyv);
+        const float len = sqrtf(dot3(n, n));
+        n = {n.x / len, n.y / len, n.z / len};
+    }
 #else
     f3 n = normalize3(cross3(dxv, dyv));
 #endif

@@ -93,7 +93,7 @@ TOPO_HD int clip_to_screen(const float clip[4], float W, float H, SVert& s) {
         s.flag = kVtxNear;
         return kVtxNear;
     }
-    const float iw = div_f(1.0f, clip[3]);           // perspective divide = one reciprocal + multiplies (w >= near here)
+    const float iw = div_wide(1.0f, clip[3]);        // perspective divide = one reciprocal + multiplies (w >= near here; a void vertex: up to inf)
     const float nx = clip[0] * iw, ny = clip[1] * iw, nz = clip[2] * iw;
     const float hw = 0.5f * W, hh = 0.5f * H;       // exact: W, H are small integers
     const float xf = fmaf(nx, hw, hw);              // 0.5*(ndc.x + 1)*W
@@ -459,7 +459,7 @@ TOPO_HD VFull lerp_vertex(const VFull& I, const VFull& O, float t) {
 }
 
 TOPO_HD VFull clip_edge(const VFull& I, const VFull& O) {   // I inside (z_clip >= 0), O outside
-    return lerp_vertex(I, O, div_f(I.clip[2], I.clip[2] - O.clip[2]));
+    return lerp_vertex(I, O, div_wide(I.clip[2], I.clip[2] - O.clip[2]));
 }
 
 // Triangle number `fan` (0 or 1) of the clipped polygon, written out case by case so that nothing is indexed at
@@ -504,6 +504,22 @@ TOPO_HD bool clip_near_fan(const VFull& v0, const VFull& v1, const VFull& v2, ui
             return false;
     }
 }
+// The vertex of a four-vertex clipped polygon that piece `fan` leaves out (p3 for piece 0, p1 for piece 1), as clip
+// coordinates: the guard band discards the primitive as a whole (Raster spec 3), so a piece is drawn only if this vertex
+// passes clip_to_screen() as well.  Returns false for the three-vertex polygons, whose one piece holds every vertex.
+TOPO_HD bool clip_near_rest(const VFull& v0, const VFull& v1, const VFull& v2, uint32_t fan, float rest[4]) {
+    const uint32_t mask = (v0.clip[2] >= 0.0f ? 1u : 0u) | (v1.clip[2] >= 0.0f ? 2u : 0u) | (v2.clip[2] >= 0.0f ? 4u : 0u);
+    VFull d;
+    switch (mask) {
+        case 3u: d = fan == 0 ? clip_edge(v0, v2) : v1; break;
+        case 6u: d = fan == 0 ? clip_edge(v2, v0) : v1; break;
+        case 5u: d = fan == 0 ? v2 : clip_edge(v0, v1); break;
+        default: return false;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rest[k] = d.clip[k];
+    return true;
+}
 
 // ---- perspective-correct varyings --------------------------------------------------------------------
 // a = (a0*q0 + a1*q1 + a2*q2) * (1 / (q0+q1+q2)), sums as fma chains
@@ -516,9 +532,22 @@ TOPO_HD void interpolate_q(const VFull& v0, const VFull& v1, const VFull& v2, fl
     wnrm.y = fmaf(v2.wnrm.y, q2, fmaf(v1.wnrm.y, q1, v0.wnrm.y * q0)) * iq;
     wnrm.z = fmaf(v2.wnrm.z, q2, fmaf(v1.wnrm.z, q1, v0.wnrm.z * q0)) * iq;
 }
+// 1 / w of the three vertices of an uncut triangle that won a pixel (w >= near).  One test for the three: a void vertex
+// (div_wide, topo_math.h) sends all of them through the full division.
+TOPO_HD void recip_w3(float w0, float w1, float w2, float& i0, float& i1, float& i2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_expect(!(fmaxf(fmaxf(w0, w1), w2) <= 0x1p+96f), 0)) {
+        i0 = 1.0f / w0; i1 = 1.0f / w1; i2 = 1.0f / w2;
+        return;
+    }
+#endif
+    i0 = div_f(1.0f, w0); i1 = div_f(1.0f, w1); i2 = div_f(1.0f, w2);
+}
 // Weights of an uncut triangle from its screen-space barycentrics: q_i = b_i * (1/w_i).
 TOPO_HD void interpolate(const VFull& v0, const VFull& v1, const VFull& v2, const float b[3], f3& wpos, f3& wnrm) {
-    interpolate_q(v0, v1, v2, b[0] * div_f(1.0f, v0.clip[3]), b[1] * div_f(1.0f, v1.clip[3]), b[2] * div_f(1.0f, v2.clip[3]), wpos, wnrm);
+    float i0, i1, i2;
+    recip_w3(v0.clip[3], v1.clip[3], v2.clip[3], i0, i1, i2);
+    interpolate_q(v0, v1, v2, b[0] * i0, b[1] * i1, b[2] * i2, wpos, wnrm);
 }
 // Weights for a fragment of a primitive cut by the near plane (Raster spec 8): homogeneous barycentrics of the pixel
 // centre with respect to the primitive's own three vertices, q = adj([x y w]) . (gx, gy, 1) with (gx, gy) the centre in
@@ -591,6 +620,9 @@ TOPO_HD bool resolve_vertices(const TileDev& t, uint32_t tile_w, FastDiv div_hm1
     } else if (!all_in) {   // near-plane clipping: replace the vertices by those of fan triangle `fan`
         VFull a, b, c;
         if (!clip_near_fan(r.v[0], r.v[1], r.v[2], fan, a, b, c)) return false;
+        float rest[4];      // the guard band looks at every vertex of the clipped polygon, not only at this piece's three
+        SVert srest;
+        if (clip_near_rest(r.v[0], r.v[1], r.v[2], fan, rest) && clip_to_screen(rest, (float)W, (float)H, srest) != kVtxOk) return false;
         r.v[0] = a; r.v[1] = b; r.v[2] = c;
     } else if (fan != 0) {
         return false;
@@ -616,7 +648,9 @@ TOPO_HD bool resolve_varyings(const TileDev& t, uint32_t tile_w, FastDiv div_hm1
     if (resolve_vertices<true, kTableOnly>(t, tile_w, div_hm1, hm1, view, W, H, tri, fan, ndec, r, &cut)) {
         float b[3];
         if (fan != 0 || !triangle_bary(r.s[0], r.s[1], r.s[2], px, py, b)) return false;
-        q[0] = b[0] * div_f(1.0f, r.v[0].clip[3]); q[1] = b[1] * div_f(1.0f, r.v[1].clip[3]); q[2] = b[2] * div_f(1.0f, r.v[2].clip[3]);
+        float i0, i1, i2;
+        recip_w3(r.v[0].clip[3], r.v[1].clip[3], r.v[2].clip[3], i0, i1, i2);
+        q[0] = b[0] * i0; q[1] = b[1] * i1; q[2] = b[2] * i2;
     } else if (cut) {
         homogeneous_weights(r.v[0], r.v[1], r.v[2], (float)W, (float)H, px, py, q);
     } else {
@@ -720,9 +754,9 @@ TOPO_HD void resolve_setup(const TileDev& t, uint32_t tile_w, FastDiv div_hm1, u
             u6 = f64_lo(A2); u7 = f64_hi(A2); u8 = f64_lo(B2); u9 = f64_hi(B2); u10 = f64_lo(C2d); u11 = f64_hi(C2d);
             u12 = f64_lo(AR); u13 = f64_hi(AR);
             iA = f_bits(div_f(1.0f, (float)(-area2)));
-            iw0 = f_bits(div_f(1.0f, r.v[0].clip[3]));
-            iw1 = f_bits(div_f(1.0f, r.v[1].clip[3]));
-            iw2 = f_bits(div_f(1.0f, r.v[2].clip[3]));
+            float i0, i1, i2;
+            recip_w3(r.v[0].clip[3], r.v[1].clip[3], r.v[2].clip[3], i0, i1, i2);
+            iw0 = f_bits(i0); iw1 = f_bits(i1); iw2 = f_bits(i2);
         }
     } else if (cut) {
         kind = 3;
