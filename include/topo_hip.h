@@ -346,6 +346,47 @@ int topo_horizon_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, to
  * (x, y) = (column + 0.5, row + 0.5) a horizon record becomes the skyline's azimuth and elevation. */
 void topo_pixel_angles(const topo_uniforms* view, uint32_t width, uint32_t height, uint32_t n, const float* xy, double* az_el_out);
 
+/* ---- ground: the terrain point under a pixel of the latest submission ------------------------------------------------------------
+ * "What am I pointing at?"  For pixel (x, y) of view `view` of the latest submission (as the horizon calls define it) the query takes
+ * the triangle that won the pixel, reads its three vertex heights from the tile's resident DEM and reports the point of that
+ * triangle's plane which the view's camera_proj maps to the pixel centre (x + 0.5, y + 0.5): longitude and latitude (degrees,
+ * lon = atan2(Y, X), lat = asin(Z / |p|)), height = |p| - R0 (R0 = 6 371 000 m, the reference's sphere), range = |p - camera_pos|.
+ * The arithmetic is f64 throughout -- the f32 tile transform, height, camera_proj and camera_pos are widened and taken as exact --
+ * so the answer does not share the frame depth's error (topo_dist_from_depth(depth) is only good to about 2 / w: hundreds of metres
+ * of range at 20 km).  The point may lie marginally outside its triangle (the rasteriser snaps vertices to 1/256 px); a piece of a
+ * near-clipped triangle (fan) answers with its original triangle's plane.  w1, w2: the plane's barycentric weights of the
+ * triangle's second and third vertex (index-buffer order).  Errors, stream order and tile changes are those of the horizon calls:
+ * TOPO_ERR_INVALID when nothing was rendered yet, for a view or pixel outside the submission and once tiles were added, replaced or
+ * unloaded after it; TOPO_ERR_CAPACITY, once, from the host read of a submission that overflowed its rare-triangle queue.  The
+ * queries write nothing but their outputs. */
+typedef struct topo_ground_point {       /* 64 bytes; written as 16-byte stores */
+    double lon_deg, lat_deg;
+    float height_m, range_m;             /* the f64 values rounded once */
+    float depth;                         /* the key's depth = the frame's depth output at the pixel; 1.0 for sky */
+    int32_t kind;                        /* TOPO_GROUND_*; every other field of a sky / incomplete / outside record is 0 (sky: depth 1.0) */
+    int32_t tile_lat_deg, tile_lon_deg;  /* tile of the winning triangle */
+    uint32_t cell_x, cell_y;             /* its cell: viewshed / horizon numbering */
+    uint32_t tri, fan;                   /* tri = triangle & 1 (index-buffer order within the cell); fan = piece of a near-clipped triangle */
+    float w1, w2;
+} topo_ground_point;
+#define TOPO_GROUND_TERRAIN 1
+#define TOPO_GROUND_SKY 0
+#define TOPO_GROUND_OUTSIDE (-1)         /* device list only: the query names a view or pixel outside the submission (nothing was read) */
+#define TOPO_GROUND_INCOMPLETE (-2)      /* device list only: the submission overflowed its rare-triangle queue */
+#define TOPO_GROUND_DEGENERATE (-3)      /* no finite point: a void (non-finite) vertex height or a vanishing determinant; the tile, cell,
+                                          * triangle and depth are still reported, the position and weights are 0 */
+typedef struct topo_ground_query { uint32_t view, x, y, _reserved; } topo_ground_query;
+/* Host memory, n queries -> n records; waits for the submission. */
+int topo_ground_read(topo_ctx* ctx, uint32_t n, const topo_ground_query* queries, topo_ground_point* out);
+/* Device memory (both 16-byte aligned); asynchronous: queued on the stream that submission ran on, behind it. */
+int topo_ground_device(topo_ctx* ctx, uint32_t n, const topo_ground_query* queries_dev, topo_ground_point* out_dev);
+/* The dense form: for every pixel of views [first_view, first_view + n_views) a float4 (lon_deg, lat_deg, height_m, range_m), each the
+ * f64 result rounded once to f32 -- bit for bit (float) of what the list calls report -- view i at out_dev + i * view_stride_bytes,
+ * rows pitch_bytes apart (device memory; pointer and strides multiples of 16; bytes between rows and views are left alone).  Pixels
+ * without a terrain point (sky, degenerate, incomplete submission) get four quiet NaNs.  f32 longitude is good to about 0.85 m on
+ * the ground at |lon| >= 128 degrees (half that below 128, and so on); the list calls give f64.  Asynchronous, as topo_ground_device. */
+int topo_ground_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, float* out_dev, size_t view_stride_bytes, size_t pitch_bytes);
+
 /* ---- host-side helpers mirroring the reference's CPU code ---------------------------------------------- */
 
 /* Uniforms::new(&camera, bounds) with Camera{eye, yaw, pitch, fov_y, NEAR, FAR, view_mode, sun_angle{theta,phi}}:

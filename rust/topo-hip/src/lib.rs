@@ -172,6 +172,16 @@ impl TerrainRenderer {
         check(self.ctx, unsafe { sys::topo_horizon_read(self.ctx, 0, n, out.as_mut_ptr(), w as usize) })?;
         Ok((n, w, out))
     }
+
+    /// Ground points (new): the terrain point under each queried pixel `(view, x, y)` of the latest submission -- longitude and
+    /// latitude in f64, height, range, the winning triangle's tile and cell (`kind` 1 terrain, 0 sky, -3 degenerate); waits for that
+    /// submission.  A query outside the submission is refused (`TOPO_ERR_INVALID`).
+    pub fn ground(&mut self, queries: &[(u32, u32, u32)]) -> Result<Vec<sys::topo_ground_point>, TopoError> {
+        let q: Vec<sys::topo_ground_query> = queries.iter().map(|&(view, x, y)| sys::topo_ground_query { view, x, y, _reserved: 0 }).collect();
+        let mut out = vec![sys::topo_ground_point::default(); q.len()];
+        check(self.ctx, unsafe { sys::topo_ground_read(self.ctx, q.len() as u32, q.as_ptr(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
 }
 
 impl Drop for TerrainRenderer {

@@ -38,6 +38,12 @@ HORIZON_SKY, HORIZON_INCOMPLETE = -1, -2
 # topo_horizon_point (include/topo_hip.h), 32 bytes
 HORIZON_DTYPE = np.dtype([("row", "<i4"), ("depth", "<f4"), ("lat_deg", "<i4"), ("lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"),
                           ("fan", "<u4"), ("_reserved", "<u4")])
+GROUND_TERRAIN, GROUND_SKY, GROUND_OUTSIDE, GROUND_INCOMPLETE, GROUND_DEGENERATE = 1, 0, -1, -2, -3
+# topo_ground_point, 64 bytes, and topo_ground_query, 16 bytes
+GROUND_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f4"), ("range_m", "<f4"), ("depth", "<f4"), ("kind", "<i4"),
+                         ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("fan", "<u4"),
+                         ("w1", "<f4"), ("w2", "<f4")])
+GROUND_QUERY_DTYPE = np.dtype([("view", "<u4"), ("x", "<u4"), ("y", "<u4"), ("_reserved", "<u4")])
 
 
 class TopoError(RuntimeError):
@@ -153,6 +159,9 @@ def lib():
             "topo_horizon_read": (C.c_int, [vp, u32, u32, vp, sz]),
             "topo_horizon_device": (C.c_int, [vp, u32, u32, vp, sz]),
             "topo_pixel_angles": (None, [vp, u32, u32, u32, vp, vp]),
+            "topo_ground_read": (C.c_int, [vp, u32, vp, vp]),
+            "topo_ground_device": (C.c_int, [vp, u32, vp, vp]),
+            "topo_ground_map_device": (C.c_int, [vp, u32, u32, vp, sz, sz]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -272,6 +281,17 @@ def geotiff_info(data: bytes):
     if rc != 0:
         raise TopoError(rc, "GeoTIFF container or geo tags not usable")
     return int(w.value), int(h.value), CoordinateTransform(rp, mp, sc)
+
+
+def ground_queries(queries) -> np.ndarray:
+    """GROUND_QUERY_DTYPE records from such records or from an (n, 3) integer array of (view, x, y)."""
+    q = np.asarray(queries)
+    if q.dtype == GROUND_QUERY_DTYPE:
+        return np.ascontiguousarray(q).reshape(-1)
+    q = q.reshape(-1, 3)
+    out = np.zeros(len(q), GROUND_QUERY_DTYPE)
+    out["view"], out["x"], out["y"] = q[:, 0], q[:, 1], q[:, 2]
+    return out
 
 
 def pixel_angles(view_uniforms, width: int, height: int, xy) -> np.ndarray:
@@ -669,6 +689,30 @@ class TerrainRenderer:
         total, w, _ = self.horizon_shape()
         n = total - first_view if n_views is None else n_views
         self._check(lib().topo_horizon_device(self._h, first_view, n, C.c_void_p(out_ptr), w if view_stride is None else view_stride))
+
+    # ground: the terrain point under pixels of the latest submission (include/topo_hip.h)
+    def ground(self, queries) -> np.ndarray:
+        """topo_ground_read.  queries: GROUND_QUERY_DTYPE records, or an (n, 3) integer array of (view, x, y); returns n
+        GROUND_DTYPE records (f64 longitude / latitude); waits for the submission.  Raises TopoError(INVALID) for a query outside
+        it, TopoError(CAPACITY) if it overflowed its rare-triangle queue."""
+        q = ground_queries(queries)
+        out = np.zeros(len(q), GROUND_DTYPE)
+        self._check(lib().topo_ground_read(self._h, len(q), _p(q) if len(q) else None, _p(out) if len(q) else None))
+        return out
+
+    def ground_device(self, queries_ptr: int, out_ptr: int, n: int):
+        """topo_ground_device: n topo_ground_query at queries_ptr -> n topo_ground_point at out_ptr (device memory, 16-byte
+        aligned), queued behind the latest submission on its stream."""
+        self._check(lib().topo_ground_device(self._h, n, C.c_void_p(queries_ptr), C.c_void_p(out_ptr)))
+
+    def ground_map_device(self, out_ptr: int, first_view: int = 0, n_views: int = None, view_stride_bytes: int = None, pitch_bytes: int = None):
+        """topo_ground_map_device: float4 (lon, lat, height, range) for every pixel of the views, NaN where there is no terrain
+        point; view i at out_ptr + i * view_stride_bytes, rows pitch_bytes apart (defaults: densely packed)."""
+        total, w, h = self.horizon_shape()
+        n = total - first_view if n_views is None else n_views
+        pitch = 16 * w if pitch_bytes is None else pitch_bytes
+        stride = pitch * h if view_stride_bytes is None else view_stride_bytes
+        self._check(lib().topo_ground_map_device(self._h, first_view, n, C.c_void_p(out_ptr), stride, pitch))
 
     def probe_div(self, kind: int, x: np.ndarray, y: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -2,9 +2,11 @@
 //
 //   k_viewshed   behind the frame's last k_resolve: the DEM cells that own a pixel, OR-ed into per-tile bit masks
 //   k_horizon    per view and column, the topmost pixel that shows terrain, decoded to its tile and cell
+//   k_ground     per queried pixel, the terrain point under it (f64: topo_ground.h); k_ground_map: the same for every pixel of whole views
 #pragma once
 
 #include "kernels_common.h"
+#include "topo_ground.h"
 
 namespace topo {
 namespace {
@@ -183,6 +185,139 @@ __global__ __launch_bounds__(256) void k_horizon(HorizonParams P) {
         lon = P.tile_ll[2 * (size_t)rank + 1];
     }
     horizon_store(dst, row, (uint32_t)(key >> 32), lat, lon, cx, cy, id & 1u);
+}
+
+// ---- ground (topo_ground_*) --------------------------------------------------------------------------------------------------
+// The terrain point under a pixel of a finished submission.  The pixel's key names its winning triangle (decoded as k_horizon decodes
+// it); the triangle's three vertex texels (triangle_vertices) get their heights from the tile's resident DEM and the sin / cos of
+// their longitude and latitude from the tiles' f64 tables (k_ground_tables); ground_solve (topo_ground.h, f64 throughout) finds the
+// point of the triangle's plane that the view maps to the pixel centre.  Launched by the query on the submission's stream, behind it;
+// the kernels read the keys, the marks, the status word, the tile table, the DEMs and the tables and write only their output.  Both
+// kernels answer a pixel through ground_answer: with -ffp-contract=off the list and the map agree bit for bit.
+struct GroundAnswer {
+    int32_t kind;
+    int32_t lat, lon;
+    GroundTri t;
+    GroundResult r;
+};
+
+// The per-triangle part of an answer: the key's low word decoded, the tile, and the ECEF positions of the three vertices.  false
+// (a.kind = degenerate) where the id names nothing of the tile set.
+__device__ __forceinline__ bool ground_triangle(const GroundParams& P, uint32_t id, GroundAnswer& a, double p[3][3]) {
+    a.kind = kGroundDegenerate;
+    a.t = ground_decode(id, P.q.tris_per_tile, P.q.hm1);
+    // (the rank and the vertex texels are tested in the product build too: what they index are tables and the DEM)
+    if (!(TOPO_CHK(P.q.check, a.t.rank < P.q.n_tiles, 18u, id) && a.t.rank < P.q.n_tiles)) return false;
+    a.lat = P.q.tile_ll[2 * (size_t)a.t.rank];
+    a.lon = P.q.tile_ll[2 * (size_t)a.t.rank + 1];
+    const TileDev& t = P.tiles[a.t.rank];
+    uint32_t vx[3], vy[3];
+    triangle_vertices(a.t.tri, P.q.hm1, vx, vy);
+    const size_t tab = (size_t)a.t.rank * ground_table_doubles(P.tile_w, P.tile_h);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const bool inside = vx[i] < P.tile_w && vy[i] < P.tile_h;
+        if (!(TOPO_CHK(P.q.check, inside, 18u, ((uint64_t)vy[i] << 32) | vx[i]) && inside)) return false;
+        const size_t lo = tab + 2 * (size_t)vx[i], la = tab + 2 * ((size_t)P.tile_w + vy[i]);
+        if (!TOPO_CHK(P.q.check, la + 1 < P.trig_doubles, 18u, la)) return false;
+        const double2 clo_slo = *reinterpret_cast<const double2*>(P.trig + lo), cla_sla = *reinterpret_cast<const double2*>(P.trig + la);
+        ground_vertex_from(TOPO_GLOBAL_F32(t.heights)[(size_t)vy[i] * P.tile_w + vx[i]], clo_slo.x, clo_slo.y, cla_sla.x, cla_sla.y, p[i]);
+    }
+    return true;
+}
+
+__device__ __forceinline__ GroundAnswer ground_answer(const GroundParams& P, uint64_t key, uint32_t view, uint32_t x, uint32_t y) {
+    GroundAnswer a{};
+    const uint32_t id = (uint32_t)key;
+    if (id == kNoTri) return a;      // kind 0: sky
+    double p[3][3];
+    if (!ground_triangle(P, id, a, p)) return a;
+    a.r = ground_solve(p, P.views[view], ground_ndc_x(x, P.q.W), ground_ndc_y(y, P.q.H));
+    if (a.r.ok) a.kind = kGroundTerrain;
+    return a;
+}
+
+// The tiles' f64 (cos, sin) tables (ground_table_doubles each, draw order): a lane per column or row, once per tile set.
+__global__ __launch_bounds__(256) void k_ground_tables(const TileDev* __restrict__ tiles, double* __restrict__ trig, uint32_t w, uint32_t h) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= w + h) return;
+    const TileDev& t = tiles[blockIdx.y];
+    double c, s;
+    if (i < w) ground_trig_lon(t, i, c, s);
+    else ground_trig_lat(t, i - w, c, s);
+    *reinterpret_cast<double2*>(trig + (size_t)blockIdx.y * ground_table_doubles(w, h) + 2 * (size_t)i) = make_double2(c, s);
+}
+
+// One ground record, as four 16-byte vector stores.  Only a terrain record carries a position; a degenerate one keeps what the key
+// itself says (depth, tile, cell, triangle).
+__device__ __forceinline__ void ground_store(GroundPoint* dst, const GroundAnswer& a, uint32_t depth_bits) {
+    int4* d = reinterpret_cast<int4*>(dst);
+    const bool pos = a.kind == kGroundTerrain;
+    const double lon = pos ? a.r.lon_deg : 0.0, lat = pos ? a.r.lat_deg : 0.0;
+    const float h = pos ? (float)a.r.height : 0.0f, rg = pos ? (float)a.r.range : 0.0f;
+    const float w1 = pos ? (float)a.r.w1 : 0.0f, w2 = pos ? (float)a.r.w2 : 0.0f;
+    d[0] = make_int4(__double2loint(lon), __double2hiint(lon), __double2loint(lat), __double2hiint(lat));
+    d[1] = make_int4(__float_as_int(h), __float_as_int(rg), (int32_t)depth_bits, a.kind);
+    d[2] = make_int4(a.lat, a.lon, (int32_t)a.t.cell_x, (int32_t)a.t.cell_y);
+    d[3] = make_int4((int32_t)(a.t.tri & 1u), (int32_t)a.t.fan, __float_as_int(w1), __float_as_int(w2));
+}
+
+// The list form: one lane per query.  A query outside the submission (the host variant has refused those) reads nothing and
+// answers kind -1; a submission whose rare-triangle queue overflowed is incomplete: kind -2.
+__global__ __launch_bounds__(256) void k_ground(GroundParams P, const GroundQuery* __restrict__ queries, GroundPoint* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const GroundQuery q = queries[i];
+    GroundAnswer a{};
+    if (P.q.counters[kCtrStatus] & kStatusRareOverflow) {
+        a.kind = kGroundIncomplete;
+        ground_store(out + i, a, 0u);
+        return;
+    }
+    if (q.view >= P.sub_views || q.x >= P.q.W || q.y >= P.q.H) {
+        a.kind = kGroundOutside;
+        ground_store(out + i, a, 0u);
+        return;
+    }
+    const size_t at = ((size_t)q.view * P.q.H + q.y) * P.q.W + q.x;
+    const uint64_t key = TOPO_CHK(P.q.check, at < P.q.n_keys, 18u, at) ? P.q.vis[at] : kVisClear;
+    a = ground_answer(P, key, q.view, q.x, q.y);
+    ground_store(out + i, a, (uint32_t)(key >> 32));
+}
+
+// The dense form: float4 (lon, lat, height, range) -- each the f64 value rounded once -- for every pixel of views
+// [first_view, first_view + n_views), four quiet NaNs where there is no terrain point (sky, degenerate, incomplete frame).  One wave
+// per 64-key segment of the visibility buffer, grid-stride; a segment without a mark holds only sky and costs no key load, only the
+// 64 coalesced 16-byte stores -- non-temporal: nothing here reads them again.  Linear key indices are 64-bit (a submission holds up
+// to 2^32 - 1 keys, so the index of one view's pixel fits 32 bits for the divisions).
+__global__ __launch_bounds__(256) void k_ground_map(GroundParams P, uint8_t* __restrict__ out, size_t view_stride, size_t pitch) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwave = (uint64_t)gridDim.x * 4;
+    const uint64_t view_keys = (uint64_t)P.q.W * P.q.H;
+    const uint64_t k0 = P.q.first_view * view_keys, k1 = k0 + P.q.n_views * view_keys;
+    const bool incomplete = (P.q.counters[kCtrStatus] & kStatusRareOverflow) != 0;
+    [[maybe_unused]] const uint64_t nseg = ((uint64_t)P.q.n_keys + 63) >> 6;      // (the check build's bound)
+    const uint32_t qnan = 0x7FC00000u;
+    for (uint64_t seg = (k0 >> 6) + wave; seg * 64 < k1; seg += nwave) {
+        const uint64_t k = seg * 64 + lane;
+        if (k < k0 || k >= k1) continue;
+        const bool marked = !incomplete && TOPO_CHK(P.q.check, seg < nseg, 18u, seg) && P.q.dirty[seg] != 0;
+        const uint64_t key = marked && TOPO_CHK(P.q.check, k < P.q.n_keys, 18u, k) ? P.q.vis[k] : kVisClear;
+        const uint32_t v = (uint32_t)k / (uint32_t)view_keys, rem = (uint32_t)k - v * (uint32_t)view_keys;      // (k < 2^32)
+        const uint32_t y = rem / P.q.W, x = rem - y * P.q.W;
+        u32x4_t val = {qnan, qnan, qnan, qnan};
+        if ((uint32_t)key != kNoTri) {
+            const GroundAnswer a = ground_answer(P, key, v, x, y);
+            if (a.kind == kGroundTerrain) {
+                val.x = __float_as_uint((float)a.r.lon_deg);
+                val.y = __float_as_uint((float)a.r.lat_deg);
+                val.z = __float_as_uint((float)a.r.height);
+                val.w = __float_as_uint((float)a.r.range);
+            }
+        }
+        uint8_t* const dst = out + (size_t)(v - P.q.first_view) * view_stride + (size_t)y * pitch + (size_t)x * 16;
+        __builtin_nontemporal_store(val, reinterpret_cast<u32x4_t*>(dst));
+    }
 }
 
 }  // namespace

@@ -519,7 +519,7 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     last_far_phase_ = p.split_m > 0.0f && !(switches().far_skip && far_phase_empty(views, n, tiles_, &p.split_m));
     const CullList cull = cull_pairs(views, p);
     if (int rc = queue_frame(c, stream, p, pack_in_cull ? &pack : nullptr, cull, last_far_phase_, out, slots, n_slots, after_slot)) return rc;
-    record_submission(c, p);
+    record_submission(c, p, views);
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
 }
@@ -776,12 +776,19 @@ int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p
     return TOPO_OK;
 }
 
-// The submission as the status ring, the timings and the horizon query see it.
-void TerrainRenderer::record_submission(FrameCtx& c, const FrameParams& p) {
+// The submission as the status ring, the timings and the horizon and ground queries see it.
+void TerrainRenderer::record_submission(FrameCtx& c, const FrameParams& p, const topo_uniforms* views) {
     ++c.submitted;
     c.timed = true;
     c.sub.n_views = p.n_views;
     c.sub.tile_gen = tile_gen_;
+    c.sub.views.resize(p.n_views);
+    for (uint32_t i = 0; i < p.n_views; ++i) {
+        memcpy(c.sub.views[i].proj, views[i].camera_proj, sizeof c.sub.views[i].proj);
+        memcpy(c.sub.views[i].pos, views[i].camera_pos, sizeof c.sub.views[i].pos);
+        c.sub.views[i].pad_ = 0.0f;
+    }
+    c.sub.views_on_device = false;
     HorizonParams& q = c.sub.query;
     q.vis = p.vis;
     q.dirty = p.dirty;
@@ -886,22 +893,21 @@ int TerrainRenderer::horizon_shape(uint32_t* n_views, uint32_t* w, uint32_t* h) 
 
 // The latest submission, if views [first, first + n) of it can be answered: its context and the stream it was queued on (the one a
 // query is queued on, behind it).  Tiles added, replaced or unloaded since have taken its draw order with them.
-int TerrainRenderer::horizon_prepare(uint32_t first, uint32_t n, size_t view_stride, FrameCtx** out_c, hipStream_t* out_s) {
+int TerrainRenderer::query_prepare(uint32_t first, uint32_t n, FrameCtx** out_c, hipStream_t* out_s) {
     if (latest_ctx_ < 0) return fail(TOPO_ERR_INVALID, "no submission to query");
     FrameCtx& c = ctx_[latest_ctx_];
     if (c.sub.tile_gen != tile_gen_) return fail(TOPO_ERR_INVALID, "tiles were added or unloaded since the latest submission: its draw order is gone");
     if (n == 0 || first >= c.sub.n_views || n > c.sub.n_views - first) return fail(TOPO_ERR_INVALID, "views outside the latest submission");
-    if (view_stride < c.sub.query.W) return fail(TOPO_ERR_INVALID, "view stride smaller than a view's width");
     if (int rc = bind_device()) return rc;
     *out_c = &c;
     *out_s = c.last_stream ? c.last_stream : stream_;      // (null: a wait covered it and the stream may be gone; the frame is done)
     return TOPO_OK;
 }
 
-// k_horizon over views [first, first + n) of c's latest submission into `out` (device), on s.  The rank -> (lat, lon) table is the
-// current tile order, which horizon_prepare has checked to be the submission's; it is rebuilt after the tile set changed, once every
-// earlier query has finished (add_terrain / unload_terrain join the frames, and a query on a context's own stream marks it pending).
-int TerrainRenderer::horizon_launch(FrameCtx& c, uint32_t first, uint32_t n, HorizonPoint* out, size_t view_stride, hipStream_t s) {
+// The tables a query kernel reads besides the submission's own.  The rank -> (lat, lon) table is the current tile order, which
+// query_prepare has checked to be the submission's; it is rebuilt after the tile set changed, once every earlier query has finished
+// (add_terrain / unload_terrain join the frames, and a query on a context's own stream marks it pending).  The check build's bounds record.
+int TerrainRenderer::query_tables(hipStream_t s) {
     if (hz_ll_gen_ != tile_gen_) {
         if (int rc = wait_all()) return rc;
         hz_ll_.clear();
@@ -919,6 +925,12 @@ int TerrainRenderer::horizon_launch(FrameCtx& c, uint32_t first, uint32_t n, Hor
         TOPO_HIP_TRY(hipMemsetAsync(d_hz_check_.p, 0, kStatusWords * sizeof(uint32_t), s));
     }
 #endif
+    return TOPO_OK;
+}
+
+// k_horizon over views [first, first + n) of c's latest submission into `out` (device), on s.
+int TerrainRenderer::horizon_launch(FrameCtx& c, uint32_t first, uint32_t n, HorizonPoint* out, size_t view_stride, hipStream_t s) {
+    if (int rc = query_tables(s)) return rc;
     HorizonParams p = c.sub.query;
     p.check = d_hz_check_.as<uint32_t>();
     p.tile_ll = d_hz_ll_.as<const int32_t>();
@@ -931,8 +943,8 @@ int TerrainRenderer::horizon_launch(FrameCtx& c, uint32_t first, uint32_t n, Hor
     return TOPO_OK;
 }
 
-// The bounds-checking build: what k_horizon recorded, into the status topo_frame_status reports (the queries have finished).
-int TerrainRenderer::horizon_fold_check() {
+// The bounds-checking build: what the query kernels recorded, into the status topo_frame_status reports (the queries have finished).
+int TerrainRenderer::query_fold_check() {
 #ifdef TOPO_BOUNDS_CHECK
     if (!d_hz_check_.p) return TOPO_OK;
     uint32_t w[kStatusWords];
@@ -945,25 +957,33 @@ int TerrainRenderer::horizon_fold_check() {
     return TOPO_OK;
 }
 
-// Host read: waits for the submission and the query.  The submission's status is folded as topo_render folds its own frame: the
-// frames of its context in front of it go to the next topo_join (their overflow stays pending there), and its own overflow is this
-// call's error -- the horizon of an incomplete frame -- and is not reported again by the next topo_join.
+// The end of a host read: waits for the submission and the query queued behind it on s.  The submission's status is folded as
+// topo_render folds its own frame: the frames of its context in front of it go to the next topo_join (their overflow stays pending
+// there), and its own overflow is this call's error -- the query of an incomplete frame -- and is not reported again by the next
+// topo_join.
+int TerrainRenderer::query_finish_read(FrameCtx& c, hipStream_t s, const char* what) {
+    TOPO_HIP_TRY(hipStreamSynchronize(s));      // (the stream of the context's latest frame: all its frames are done)
+    c.pending = false;
+    const bool overflow = fold_latest(c, false);
+    if (int rc = query_fold_check()) return rc;
+    if (overflow) return fail(TOPO_ERR_CAPACITY, std::string("rare-triangle queue overflowed: the latest submission is incomplete, and so is its ") + what);
+    return TOPO_OK;
+}
+
+static const char* const kStrideError = "view stride smaller than a view's width";
+
+// Host read: waits for the submission and the query.
 int TerrainRenderer::horizon_read(uint32_t first, uint32_t n, topo_horizon_point* out, size_t view_stride) {
     if (!out) return fail(TOPO_ERR_INVALID, "null argument");
     FrameCtx* c = nullptr;
     hipStream_t s = nullptr;
-    if (int rc = horizon_prepare(first, n, view_stride, &c, &s)) return rc;
+    if (int rc = query_prepare(first, n, &c, &s)) return rc;
+    if (view_stride < c->sub.query.W) return fail(TOPO_ERR_INVALID, kStrideError);
     const size_t row = (size_t)c->sub.query.W * sizeof(HorizonPoint);
     if (int rc = ensure(s, d_hz_out_, row * n)) return rc;
     if (int rc = horizon_launch(*c, first, n, d_hz_out_.as<HorizonPoint>(), c->sub.query.W, s)) return rc;
     TOPO_HIP_TRY(hipMemcpy2DAsync(out, view_stride * sizeof(topo_horizon_point), d_hz_out_.p, row, row, n, hipMemcpyDeviceToHost, s));
-    TOPO_HIP_TRY(hipStreamSynchronize(s));      // (the stream of the context's latest frame: all its frames are done)
-    c->pending = false;
-    const bool overflow = fold_latest(*c, false);
-    if (int rc = horizon_fold_check()) return rc;
-    if (overflow)
-        return fail(TOPO_ERR_CAPACITY, "rare-triangle queue overflowed: the latest submission is incomplete, and so is its horizon");
-    return TOPO_OK;
+    return query_finish_read(*c, s, "horizon");
 }
 
 // Device variant: queued behind the submission on its stream; an incomplete frame writes row TOPO_HORIZON_INCOMPLETE.
@@ -972,9 +992,105 @@ int TerrainRenderer::horizon_device(uint32_t first, uint32_t n, topo_horizon_poi
     if ((uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "out_dev must be 16-byte aligned");
     FrameCtx* c = nullptr;
     hipStream_t s = nullptr;
-    if (int rc = horizon_prepare(first, n, view_stride, &c, &s)) return rc;
+    if (int rc = query_prepare(first, n, &c, &s)) return rc;
+    if (view_stride < c->sub.query.W) return fail(TOPO_ERR_INVALID, kStrideError);
     if (int rc = horizon_launch(*c, first, n, (HorizonPoint*)out_dev, view_stride, s)) return rc;
     if (s != stream_) c->pending = true;      // a context's own stream: the next join (and whatever rewrites the frame) waits for the query too
+    return TOPO_OK;
+}
+
+// ---- ground -------------------------------------------------------------------------------------------------------------------
+
+static_assert(sizeof(GroundPoint) == sizeof(topo_ground_point) && sizeof(topo_ground_point) == 64, "ground record layout");
+static_assert(sizeof(GroundQuery) == sizeof(topo_ground_query) && sizeof(topo_ground_query) == 16, "ground query layout");
+
+// The parameters of a ground kernel over c's latest submission, on s: the shared tables, the tile table (the submission's: the tile
+// set has not changed since) and the submission's views, which its first ground query uploads from the host copy the submission kept.
+int TerrainRenderer::ground_params(FrameCtx& c, hipStream_t s, GroundParams& p) {
+    if (int rc = query_tables(s)) return rc;
+    const size_t trig_doubles = tiles_.size() * ground_table_doubles(tile_w_, tile_h_);
+    if (ground_trig_gen_ != tile_gen_) {
+        // once per tile set: nothing that could still read the old tables is left running, and the new ones are complete before a
+        // query can be queued on any other stream
+        if (int rc = wait_all()) return rc;
+        if (int rc = ensure(s, d_ground_trig_, (trig_doubles + 2) * sizeof(double))) return rc;
+        launch_ground_tables(d_tiles_.as<const TileDev>(), (uint32_t)tiles_.size(), d_ground_trig_.as<double>(), tile_w_, tile_h_, s);
+        TOPO_HIP_TRY(hipGetLastError());
+        TOPO_HIP_TRY(hipStreamSynchronize(s));
+        ground_trig_gen_ = tile_gen_;
+    }
+    if (!c.sub.views_on_device) {
+        const size_t bytes = c.sub.views.size() * sizeof(GroundView);
+        if (int rc = ensure(s, c.d_ground_views, bytes)) return rc;
+        TOPO_HIP_TRY(hipMemcpyAsync(c.d_ground_views.p, c.sub.views.data(), bytes, hipMemcpyHostToDevice, s));
+        c.sub.views_on_device = true;
+    }
+    p.q = c.sub.query;
+    p.q.check = d_hz_check_.as<uint32_t>();
+    p.q.tile_ll = d_hz_ll_.as<const int32_t>();
+    p.q.first_view = 0;
+    p.q.n_views = c.sub.n_views;
+    p.tiles = d_tiles_.as<const TileDev>();
+    p.views = c.d_ground_views.as<const GroundView>();
+    p.trig = d_ground_trig_.as<const double>();
+    p.trig_doubles = trig_doubles;
+    p.tile_w = tile_w_;
+    p.tile_h = tile_h_;
+    p.sub_views = c.sub.n_views;
+    return TOPO_OK;
+}
+
+// Host read: every query is checked against the submission's shape first; waits for the submission and the query.
+int TerrainRenderer::ground_read(uint32_t n, const topo_ground_query* queries, topo_ground_point* out) {
+    if (n == 0 || !queries || !out) return fail(TOPO_ERR_INVALID, "null/empty argument");
+    FrameCtx* c = nullptr;
+    hipStream_t s = nullptr;
+    if (int rc = query_prepare(0, 1, &c, &s)) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (queries[i].view >= c->sub.n_views || queries[i].x >= c->sub.query.W || queries[i].y >= c->sub.query.H)
+            return fail(TOPO_ERR_INVALID, "a query names a view or pixel outside the latest submission");
+    if (int rc = ensure(s, d_ground_q_, (size_t)n * sizeof(GroundQuery))) return rc;
+    if (int rc = ensure(s, d_ground_out_, (size_t)n * sizeof(GroundPoint))) return rc;
+    GroundParams p{};
+    if (int rc = ground_params(*c, s, p)) return rc;
+    TOPO_HIP_TRY(hipMemcpyAsync(d_ground_q_.p, queries, (size_t)n * sizeof(GroundQuery), hipMemcpyHostToDevice, s));
+    launch_ground(p, d_ground_q_.as<const GroundQuery>(), d_ground_out_.as<GroundPoint>(), n, s);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipMemcpyAsync(out, d_ground_out_.p, (size_t)n * sizeof(GroundPoint), hipMemcpyDeviceToHost, s));
+    return query_finish_read(*c, s, "ground points");
+}
+
+// Device variants: queued behind the submission on its stream.  The list's queries are in device memory, so the kernel checks them:
+// one outside the submission answers kind -1; an incomplete frame writes kind -2 (list) or NaN (map).
+int TerrainRenderer::ground_device(uint32_t n, const topo_ground_query* queries_dev, topo_ground_point* out_dev) {
+    if (n == 0 || !queries_dev || !out_dev) return fail(TOPO_ERR_INVALID, "null/empty argument");
+    if ((uintptr_t)out_dev % 16 != 0 || (uintptr_t)queries_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "queries_dev and out_dev must be 16-byte aligned");
+    FrameCtx* c = nullptr;
+    hipStream_t s = nullptr;
+    if (int rc = query_prepare(0, 1, &c, &s)) return rc;
+    GroundParams p{};
+    if (int rc = ground_params(*c, s, p)) return rc;
+    launch_ground(p, (const GroundQuery*)queries_dev, (GroundPoint*)out_dev, n, s);
+    TOPO_HIP_TRY(hipGetLastError());
+    if (s != stream_) c->pending = true;      // (as topo_horizon_device)
+    return TOPO_OK;
+}
+
+int TerrainRenderer::ground_map_device(uint32_t first, uint32_t n, float* out_dev, size_t view_stride, size_t pitch) {
+    if (!out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)out_dev % 16 != 0 || view_stride % 16 != 0 || pitch % 16 != 0) return fail(TOPO_ERR_INVALID, "out_dev, the view stride and the pitch must be multiples of 16 bytes");
+    FrameCtx* c = nullptr;
+    hipStream_t s = nullptr;
+    if (int rc = query_prepare(first, n, &c, &s)) return rc;
+    if (pitch < (size_t)c->sub.query.W * 16) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
+    if (n > 1 && view_stride < pitch * (c->sub.query.H - 1) + (size_t)c->sub.query.W * 16) return fail(TOPO_ERR_INVALID, "view stride smaller than a view");
+    GroundParams p{};
+    if (int rc = ground_params(*c, s, p)) return rc;
+    p.q.first_view = first;
+    p.q.n_views = n;
+    launch_ground_map(p, out_dev, view_stride, pitch, s);
+    TOPO_HIP_TRY(hipGetLastError());
+    if (s != stream_) c->pending = true;
     return TOPO_OK;
 }
 
@@ -1232,7 +1348,7 @@ int TerrainRenderer::frame_status(uint32_t out[4]) {
     // (folds the finished frames into last_status_; an overflow is reported through out[0] here, and stays pending as the error
     // of the next call that waits for frames)
     overflow_pending_ |= fold_idle();
-    if (int rc = horizon_fold_check()) return rc;
+    if (int rc = query_fold_check()) return rc;
     for (int i = 0; i < 4; ++i) out[i] = last_status_[i];
     last_status_[0] = last_status_[1] = last_status_[2] = last_status_[3] = 0;
     return TOPO_OK;

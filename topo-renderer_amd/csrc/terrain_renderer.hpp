@@ -158,6 +158,11 @@ class TerrainRenderer {
     int horizon_read(uint32_t first_view, uint32_t n_views, topo_horizon_point* out, size_t view_stride);
     int horizon_device(uint32_t first_view, uint32_t n_views, topo_horizon_point* out_dev, size_t view_stride);
 
+    // ground: the terrain point under pixels of the latest submission's views (topo_ground_*)
+    int ground_read(uint32_t n, const topo_ground_query* queries, topo_ground_point* out);
+    int ground_device(uint32_t n, const topo_ground_query* queries_dev, topo_ground_point* out_dev);
+    int ground_map_device(uint32_t first_view, uint32_t n_views, float* out_dev, size_t view_stride_bytes, size_t pitch_bytes);
+
     const char* last_error() const { return err_.c_str(); }
 
    private:
@@ -238,12 +243,15 @@ class TerrainRenderer {
         DeviceBuffer d_vis, d_dirty;      // d_dirty: one mark per 64 visibility keys (kernels_common.h: struct Vis)
         DeviceBuffer d_work, d_work2, d_far, d_big, d_rare, d_counters;
         DeviceBuffer d_pre_rgba, d_pre_depth;      // the pixelise branch: the render-target image k_post_pixelize samples, and a depth image when the caller wants none
-        // the context's latest submission as the horizon query reads it (its keys and marks are d_vis / d_dirty until the next one)
+        // the context's latest submission as the queries read it (its keys and marks are d_vis / d_dirty until the next one)
         struct Submission {
             uint32_t n_views = 0;
             uint64_t tile_gen = 0;                  // tile_gen_ when it was rendered
             HorizonParams query{};                  // a query's parameters, as far as the submission sets them (its keys, marks, counter set, shape)
+            std::vector<GroundView> views;          // its views' camera_proj and eye, whoever generated them (the ground query; ViewDev has no eye)
+            bool views_on_device = false;           // d_ground_views holds them (uploaded by the submission's first ground query)
         } sub;
+        DeviceBuffer d_ground_views;
     };
     static constexpr int kMaxPipeline = 4;
     FrameCtx ctx_[kMaxPipeline];
@@ -270,7 +278,7 @@ class TerrainRenderer {
     CullList cull_pairs(const topo_uniforms* views, const FrameParams& p);
     int queue_frame(FrameCtx& c, hipStream_t s, FrameParams& p, const ViewPack* pack_in_cull, const CullList& cull, bool far_phase, const OutputParams& out,
                     const ResolveSlot* slots, uint32_t n_slots, const std::function<int(uint32_t, hipStream_t)>* after_slot);
-    void record_submission(FrameCtx& c, const FrameParams& p);
+    void record_submission(FrameCtx& c, const FrameParams& p, const topo_uniforms* views);
     int frame_durations(const FrameCtx::TimedFrame& f, float out[7]);
 
     DeviceBuffer d_tiles_, d_views_, d_edge_jobs_, d_corner_jobs_, d_out_rgba_, d_out_depth_;
@@ -305,7 +313,7 @@ class TerrainRenderer {
     bool vs_on_ = false, vs_ever_ = false;
     DeviceBuffer d_vs_table_;      // rank -> the tile's mask, rebuilt with the tile table
     DeviceBuffer d_vs_stats_;      // kViewshedStatSlots x 4 counters of k_viewshed
-    // horizon: the frame context of the latest submission (-1: none, or one that failed half-way), and the tile set's generation
+    // horizon, ground: the frame context of the latest submission (-1: none, or one that failed half-way), and the tile set's generation
     // (add_terrain / unload_terrain bump it: a submission rendered with another tile order can no longer be decoded).  The rank ->
     // (lat, lon) table and the host read's device buffer are made by the first query.
     int latest_ctx_ = -1;
@@ -313,10 +321,20 @@ class TerrainRenderer {
     std::vector<int32_t> hz_ll_;                                 // the table's host copy (the source of its upload)
     uint64_t hz_ll_gen_ = ~0ull;
     DeviceBuffer d_hz_ll_, d_hz_out_;
-    DeviceBuffer d_hz_check_;             // TOPO_BOUNDS_CHECK build: k_horizon's bounds record, folded into topo_frame_status
-    int horizon_prepare(uint32_t first_view, uint32_t n_views, size_t view_stride, FrameCtx** c, hipStream_t* s);
+    DeviceBuffer d_hz_check_;             // TOPO_BOUNDS_CHECK build: the queries' bounds record, folded into topo_frame_status
+    DeviceBuffer d_ground_q_, d_ground_out_;      // the ground host read's queries and records
+    // the tiles' f64 sin / cos tables (one entry per column and per row of every tile, draw order: topo_ground.h), made by the first
+    // ground query after the tile set changed -- 38 KB per 1200 x 1200 tile -- and the tile set they were made for
+    DeviceBuffer d_ground_trig_;
+    uint64_t ground_trig_gen_ = ~0ull;
+    // what the horizon and ground queries share: the latest submission if views [first, first + n) of it can be answered, the tables
+    // a query kernel reads, the end of a host read (wait, fold the submission's status), the bounds record of the check build
+    int query_prepare(uint32_t first_view, uint32_t n_views, FrameCtx** c, hipStream_t* s);
+    int query_tables(hipStream_t s);
+    int query_finish_read(FrameCtx& c, hipStream_t s, const char* what);
+    int query_fold_check();
     int horizon_launch(FrameCtx& c, uint32_t first_view, uint32_t n_views, HorizonPoint* out, size_t view_stride, hipStream_t s);
-    int horizon_fold_check();
+    int ground_params(FrameCtx& c, hipStream_t s, GroundParams& p);
 
     std::string err_;
 };

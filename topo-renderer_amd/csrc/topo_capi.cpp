@@ -380,6 +380,21 @@ int topo_horizon_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, to
     TOPO_CALL(ctx->r->horizon_device(first_view, n_views, out_dev, view_stride));
 }
 
+int topo_ground_read(topo_ctx* ctx, uint32_t n, const topo_ground_query* queries, topo_ground_point* out) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->ground_read(n, queries, out));
+}
+
+int topo_ground_device(topo_ctx* ctx, uint32_t n, const topo_ground_query* queries_dev, topo_ground_point* out_dev) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->ground_device(n, queries_dev, out_dev));
+}
+
+int topo_ground_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, float* out_dev, size_t view_stride_bytes, size_t pitch_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->ground_map_device(first_view, n_views, out_dev, view_stride_bytes, pitch_bytes));
+}
+
 void topo_pixel_angles(const topo_uniforms* view, uint32_t width, uint32_t height, uint32_t n, const float* xy, double* az_el_out) {
     if (!view || !az_el_out || (n && !xy) || width == 0 || height == 0) return;
     topo::pixel_angles(view, width, height, n, xy, az_el_out);

@@ -5,6 +5,7 @@
 #include <hip/hip_ext.h>
 
 #include "topo_pipeline.h"
+#include "topo_ground.h"
 
 namespace topo {
 
@@ -181,6 +182,31 @@ struct HorizonParams {
     FastDiv div_tris, div_hm1;
 };
 void launch_horizon(const HorizonParams& p, hipStream_t s);
+
+// ground (topo_ground_*), behind a finished submission: the terrain point under a pixel, from its key's triangle, the tile's DEM
+// and the view's camera_proj in f64 (topo_ground.h).  Reads what k_horizon reads plus the tile table and the DEMs; writes only `out`.
+struct GroundPoint {       // = topo_ground_point (64 bytes)
+    double lon_deg, lat_deg;
+    float height_m, range_m, depth;
+    int32_t kind;
+    int32_t tile_lat, tile_lon;
+    uint32_t cell_x, cell_y, tri, fan;
+    float w1, w2;
+};
+struct GroundQuery { uint32_t view, x, y, reserved; };      // = topo_ground_query
+struct GroundParams {
+    HorizonParams q;              // the submission as a query sees it (out / view_stride unused; first_view, n_views: the map's views)
+    const TileDev* tiles;         // the tile table in the submission's draw order
+    const GroundView* views;      // sub_views entries: every view of the submission
+    const double* trig;           // the tiles' f64 (cos, sin) tables of their columns' longitudes and rows' latitudes (topo_ground.h), draw order
+    size_t trig_doubles;          // their size: n_tiles * ground_table_doubles(tile_w, tile_h)
+    uint32_t tile_w, tile_h;
+    uint32_t sub_views;
+};
+void launch_ground_tables(const TileDev* tiles, uint32_t n_tiles, double* trig, uint32_t w, uint32_t h, hipStream_t s);
+void launch_ground(const GroundParams& p, const GroundQuery* queries, GroundPoint* out, uint32_t n, hipStream_t s);
+// float4 (lon, lat, height, range) per pixel of views [p.q.first_view, + p.q.n_views): view i at out + i * view_stride, rows pitch apart (bytes)
+void launch_ground_map(const GroundParams& p, float* out, size_t view_stride, size_t pitch, hipStream_t s);
 
 // overlay pass (line_shader.wgsl over the post pass's image): keys = W*H overlay keys, (re-)initialised when keys_fresh
 void launch_overlay(const OverlayVertex* verts, const uint32_t* idx, uint32_t n_tris, uint32_t n_verts, float width, int32_t W, int32_t H, uint64_t* keys,

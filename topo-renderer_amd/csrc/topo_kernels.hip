@@ -5,7 +5,7 @@
 //   kernels_load.h      load phase (once per add_terrain): block tables, sin/cos tables, cull bounds, normals
 //   kernels_frame.h     frame phase: view constants, clear, cull, occlusion filter, the three raster kernels
 //   kernels_resolve.h   k_resolve: shading of each pixel's winner + the post pass
-//   kernels_query.h     viewshed and horizon, over a finished frame's visibility buffer
+//   kernels_query.h     viewshed, horizon and ground points, over a finished frame's visibility buffer
 //   kernels_overlay.h   pixelise post pass, line / glyph overlays, visible peaks
 //   kernels_tiff.h      GeoTIFF rows, unit-test probes
 //
@@ -244,6 +244,24 @@ void launch_horizon(const HorizonParams& p, hipStream_t s) {
     const uint64_t waves = (uint64_t)((p.W + 63) / 64) * p.n_views;      // one per (view, 64-column group)
     if (waves == 0) return;
     hipLaunchKernelGGL(k_horizon, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p);
+}
+
+void launch_ground_tables(const TileDev* tiles, uint32_t n_tiles, double* trig, uint32_t w, uint32_t h, hipStream_t s) {
+    if (n_tiles == 0) return;
+    hipLaunchKernelGGL(k_ground_tables, dim3((w + h + 255) / 256, n_tiles), dim3(256), 0, s, tiles, trig, w, h);
+}
+
+void launch_ground(const GroundParams& p, const GroundQuery* queries, GroundPoint* out, uint32_t n, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_ground, dim3((n + 255) / 256), dim3(256), 0, s, p, queries, out, n);
+}
+
+void launch_ground_map(const GroundParams& p, float* out, size_t view_stride, size_t pitch, hipStream_t s) {
+    const uint64_t view_keys = (uint64_t)p.q.W * p.q.H, k0 = p.q.first_view * view_keys, k1 = k0 + p.q.n_views * view_keys;
+    if (k1 == k0) return;
+    const uint64_t waves = ((k1 + 63) >> 6) - (k0 >> 6);      // one per 64-key segment the views touch; past 2^20 workgroups they stride
+    const uint64_t blocks = (waves + 3) / 4;
+    hipLaunchKernelGGL(k_ground_map, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0, s, p, (uint8_t*)out, view_stride, pitch);
 }
 
 // the overlay key image of a W x H target, (re-)initialised where the caller's keys are fresh
