@@ -387,6 +387,59 @@ int topo_ground_device(topo_ctx* ctx, uint32_t n, const topo_ground_query* queri
  * the ground at |lon| >= 128 degrees (half that below 128, and so on); the list calls give f64.  Asynchronous, as topo_ground_device. */
 int topo_ground_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, float* out_dev, size_t view_stride_bytes, size_t pitch_bytes);
 
+/* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
+ * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
+ * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --
+ * into one image whose columns are linear in azimuth (clockwise from true north, topo_pixel_angles' frame at the views' common eye:
+ * up = eye / |eye|, east = z x up, north = up x east) and whose rows are linear in elevation (TOPO_UNWRAP_EQUIRECTANGULAR) or in
+ * tan(elevation) (TOPO_UNWRAP_CYLINDRICAL, the classic printed panorama).
+ *
+ * Mapping.  Output pixel (c, r) looks along d = cos(el_r) (sin(az_c) east + cos(az_c) north) + sin(el_r) up, with
+ * az_c = az0 + (c + 0.5) az_span / out_w and el_r = el_top - (r + 0.5) (el_top - el_bottom) / out_h (cylindrical: tan(el_r) linear
+ * between tan(el_top) and tan(el_bottom)).  View k sees d at clip coordinates cx, cy, cw = rows 0, 1, 3 of its camera_proj applied to
+ * (d, 0) -- all views must have the same camera_pos, bit for bit, and only the direction part of camera_proj is read -- i.e. at
+ * px = (cx / cw + 1) src_w / 2, py = (1 - cy / cw) src_h / 2; it CONTAINS the pixel iff cw > 0, 0 <= px < src_w, 0 <= py < src_h.
+ * All of this is f64 (the f32 matrices widened and taken as exact).
+ * Seam rule.  The source view is the containing view with the largest cw -- the one whose axis is nearest -- and on a tie the one
+ * with the lowest index.  (At pitch 0 the sectors of topo_panorama_uniforms tile the sphere band exactly once; at other pitches
+ * they overlap slightly and leave gaps.)
+ * Filters.  TOPO_UNWRAP_NEAREST: source texel (floor px, floor py).  TOPO_UNWRAP_BILINEAR, colour only: the four texels around
+ * (px - 0.5, py - 0.5) of the SAME view with 8-bit weights, tap coordinates clamped to the view (a seam is clamped, never crossed);
+ * on the *Srgb formats the channels are decoded, blended in linear light (f32, fixed order) and encoded again; alpha blends as a
+ * plain unorm.  Depth and the source map are nearest with either filter: a depth blended across a silhouette is no depth.
+ * Fill.  A pixel no view contains gets rgba 0 0 0 0, depth a quiet NaN and source -1.
+ *
+ * Outputs (each nullable, at least one; pointers and pitches multiples of 16 bytes; the bytes between out_w and the pitch are left
+ * alone): RGBA8 in the context's format (needs rgba_src_dev), f32 depth (needs depth_src_dev), and an int32 SOURCE MAP
+ * (view * src_h + sy) * src_w + sx of the nearest texel, with which any other per-pixel layer of the views (topo_ground_map_device's
+ * float4, a mask) is carried across by a plain gather; it needs n_views * src_h * src_w < 2^31.  The sources are caller-owned
+ * device memory laid out as topo_render_views_device writes them (view k at + k * view_stride, rows pitch bytes apart; a
+ * topo_render_panorama strip: view_stride = sector_h * pitch); 1 <= n_views <= 64.
+ * Asynchronous on the context's stream (topo_set_stream), in order behind whatever was queued there, as topo_visible_peaks_device;
+ * with a pipeline depth > 1 call topo_join first, the frames run on streams of their own.  After topo_render_panorama every rank
+ * holds the whole strip and the context's stream has waited for the last exchange, so any rank can unwrap.
+ * Errors: TOPO_ERR_INVALID for null or misaligned arguments, zero sizes, parameters out of range, views with different eyes and a
+ * source map beyond 2^31 texels. */
+#define TOPO_UNWRAP_EQUIRECTANGULAR 0u
+#define TOPO_UNWRAP_CYLINDRICAL 1u
+#define TOPO_UNWRAP_NEAREST 0u
+#define TOPO_UNWRAP_BILINEAR 1u
+typedef struct topo_unwrap_params {
+    uint32_t projection, filter, out_w, out_h;
+    double az0_deg, az_span_deg;        /* left edge of column 0, clockwise from north; span in (0, 360] */
+    double el_top_deg, el_bottom_deg;   /* top edge of row 0, bottom edge of the last row; -90 < bottom < top < 90 */
+} topo_unwrap_params;
+int topo_unwrap_device(topo_ctx* ctx, const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views,
+                       uint32_t src_w, uint32_t src_h,
+                       const uint8_t* rgba_src_dev, size_t rgba_view_stride, size_t rgba_pitch,
+                       const float* depth_src_dev, size_t depth_view_stride, size_t depth_pitch,
+                       uint8_t* rgba_out_dev, size_t rgba_out_pitch, float* depth_out_dev, size_t depth_out_pitch,
+                       int32_t* src_out_dev, size_t src_out_pitch);
+/* Host, no GPU: output-pixel coordinates (x, y) = xy_out[2i], [2i+1] of the azimuth / elevation pairs az_el[2i], [2i+1] (degrees: what
+ * topo_pixel_angles returns), so that a label placed in a sector lands on the unwrapped image.  Column c's centre is x = c + 0.5,
+ * row r's centre y = r + 0.5; an azimuth outside a partial span gives x >= out_w.  Invalid parameters write nothing. */
+void topo_unwrap_xy(const topo_unwrap_params* params, uint32_t n, const double* az_el, double* xy_out);
+
 /* ---- host-side helpers mirroring the reference's CPU code ---------------------------------------------- */
 
 /* Uniforms::new(&camera, bounds) with Camera{eye, yaw, pitch, fov_y, NEAR, FAR, view_mode, sun_angle{theta,phi}}:

@@ -182,6 +182,19 @@ impl TerrainRenderer {
         check(self.ctx, unsafe { sys::topo_ground_read(self.ctx, q.len() as u32, q.as_ptr(), out.as_mut_ptr()) })?;
         Ok(out)
     }
+
+    /// Unwrap (new): the densely packed strip `render_panorama` wrote (`strip_dev` / `depth_dev`, sectors of `sector`) as ONE
+    /// `params.out_w` x `params.out_h` azimuth / elevation image: colour into `rgba_out_dev`, depth into `depth_out_dev`, rows
+    /// `4 * out_w` bytes apart (device memory, 16-byte aligned; `out_w` a multiple of 4).  `views`: the sectors' uniforms
+    /// (`sys::topo_panorama_uniforms`).  Asynchronous on the context's stream, behind the panorama.
+    pub fn unwrap_panorama(&mut self, params: &sys::topo_unwrap_params, views: &[sys::topo_uniforms], sector: (u32, u32), strip_dev: *const u8,
+                           depth_dev: *const f32, rgba_out_dev: *mut u8, depth_out_dev: *mut f32) -> Result<(), TopoError> {
+        let (row, out_row) = (4 * sector.0 as usize, 4 * params.out_w as usize);
+        check(self.ctx, unsafe {
+            sys::topo_unwrap_device(self.ctx, params, views.len() as u32, views.as_ptr(), sector.0, sector.1, strip_dev, row * sector.1 as usize, row,
+                                    depth_dev, row * sector.1 as usize, row, rgba_out_dev, out_row, depth_out_dev, out_row, ptr::null_mut(), 0)
+        })
+    }
 }
 
 impl Drop for TerrainRenderer {

@@ -44,6 +44,11 @@ GROUND_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<
                          ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("fan", "<u4"),
                          ("w1", "<f4"), ("w2", "<f4")])
 GROUND_QUERY_DTYPE = np.dtype([("view", "<u4"), ("x", "<u4"), ("y", "<u4"), ("_reserved", "<u4")])
+UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
+UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
+# topo_unwrap_params, 48 bytes
+UNWRAP_PARAMS_DTYPE = np.dtype([("projection", "<u4"), ("filter", "<u4"), ("out_w", "<u4"), ("out_h", "<u4"), ("az0_deg", "<f8"), ("az_span_deg", "<f8"),
+                                ("el_top_deg", "<f8"), ("el_bottom_deg", "<f8")])
 
 
 class TopoError(RuntimeError):
@@ -162,6 +167,8 @@ def lib():
             "topo_ground_read": (C.c_int, [vp, u32, vp, vp]),
             "topo_ground_device": (C.c_int, [vp, u32, vp, vp]),
             "topo_ground_map_device": (C.c_int, [vp, u32, u32, vp, sz, sz]),
+            "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
+            "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -303,6 +310,26 @@ def pixel_angles(view_uniforms, width: int, height: int, xy) -> np.ndarray:
     pts = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
     out = np.zeros((len(pts), 2), np.float64)
     lib().topo_pixel_angles(_p(u), width, height, len(pts), _p(pts), _p(out))
+    return out
+
+
+def unwrap_params(out_w: int, out_h: int, el_top_deg: float, el_bottom_deg: float, az0_deg: float = 0.0, az_span_deg: float = 360.0,
+                  projection: int = UNWRAP_EQUIRECTANGULAR, filter: int = UNWRAP_NEAREST) -> np.ndarray:
+    """A topo_unwrap_params record: an out_w x out_h image over [az0, az0 + span) degrees clockwise from north and
+    [el_bottom, el_top] degrees of elevation, rows linear in the elevation (equirectangular) or in its tangent (cylindrical)."""
+    p = np.zeros(1, UNWRAP_PARAMS_DTYPE)
+    p["projection"], p["filter"], p["out_w"], p["out_h"] = projection, filter, out_w, out_h
+    p["az0_deg"], p["az_span_deg"], p["el_top_deg"], p["el_bottom_deg"] = az0_deg, az_span_deg, el_top_deg, el_bottom_deg
+    return p
+
+
+def unwrap_xy(params, az_el) -> np.ndarray:
+    """topo_unwrap_xy: (n, 2) f64 output-pixel coordinates of (n, 2) azimuth / elevation pairs in degrees (what pixel_angles
+    returns); NaN for parameters the library refuses."""
+    p = np.ascontiguousarray(params, dtype=UNWRAP_PARAMS_DTYPE).reshape(-1)[:1]
+    a = np.ascontiguousarray(az_el, dtype=np.float64).reshape(-1, 2)
+    out = np.full((len(a), 2), np.nan, np.float64)
+    lib().topo_unwrap_xy(_p(p), len(a), _p(a), _p(out))
     return out
 
 
@@ -713,6 +740,25 @@ class TerrainRenderer:
         pitch = 16 * w if pitch_bytes is None else pitch_bytes
         stride = pitch * h if view_stride_bytes is None else view_stride_bytes
         self._check(lib().topo_ground_map_device(self._h, first_view, n, C.c_void_p(out_ptr), stride, pitch))
+
+    # unwrap: finished views that share an eye as one azimuth / elevation image (include/topo_hip.h)
+    def unwrap_device(self, params, uniforms_list, src_w: int, src_h: int, rgba_src_ptr: int = 0, rgba_view_stride: int = None, rgba_pitch: int = None,
+                      depth_src_ptr: int = 0, depth_view_stride: int = None, depth_pitch: int = None, rgba_out_ptr: int = 0, rgba_out_pitch: int = None,
+                      depth_out_ptr: int = 0, depth_out_pitch: int = None, src_out_ptr: int = 0, src_out_pitch: int = None):
+        """topo_unwrap_device: the views (uniforms_list: their 160-byte uniforms) at the device pointers *_src_ptr (defaults: densely
+        packed, as render_views_device / render_panorama write them) resampled by `params` (unwrap_params) into the outputs given
+        (0: not wanted; default pitch 4 * out_w); asynchronous on the context's stream."""
+        p = np.ascontiguousarray(params, dtype=UNWRAP_PARAMS_DTYPE).reshape(-1)[:1]
+        us = np.ascontiguousarray(np.stack([np.ascontiguousarray(u).view(np.uint8).reshape(160) for u in uniforms_list]))
+        row, out_row = 4 * src_w, 4 * int(p["out_w"][0])
+        ptr = lambda v: C.c_void_p(v) if v else None
+        dflt = lambda v, d: d if v is None else v
+        rp, dp = dflt(rgba_pitch, row), dflt(depth_pitch, row)
+        self._check(lib().topo_unwrap_device(self._h, _p(p), len(us), _p(us), src_w, src_h,
+                                             ptr(rgba_src_ptr), dflt(rgba_view_stride, rp * src_h), rp,
+                                             ptr(depth_src_ptr), dflt(depth_view_stride, dp * src_h), dp,
+                                             ptr(rgba_out_ptr), dflt(rgba_out_pitch, out_row), ptr(depth_out_ptr), dflt(depth_out_pitch, out_row),
+                                             ptr(src_out_ptr), dflt(src_out_pitch, out_row)))
 
     def probe_div(self, kind: int, x: np.ndarray, y: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)

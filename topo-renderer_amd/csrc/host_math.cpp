@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "topo_math.h"
+#include "topo_unwrap.h"
 
 namespace topo {
 
@@ -51,6 +52,22 @@ void geometry_transform(float h, float lon_deg, float lat_deg, float out[3]) {
     out[2] = r * sinf(lat);
 }
 
+// The local frame at an eye (geometry_transform's axes: x to (0 N, 0 E), z to the north pole): up = the eye's geocentric radius,
+// east = z x up normalised (at a pole: +y), north = up x east.  What topo_pixel_angles and the unwrap tables measure azimuth and
+// elevation in.
+void local_frame(const float eye[3], double east[3], double north[3], double up[3]) {
+    const double ex = eye[0], ey = eye[1], ez = eye[2];
+    const double el = std::sqrt(ex * ex + ey * ey + ez * ez);
+    up[0] = ex / el; up[1] = ey / el; up[2] = ez / el;
+    const double eh = std::hypot(up[0], up[1]);
+    east[0] = eh > 0.0 ? -up[1] / eh : 0.0;
+    east[1] = eh > 0.0 ? up[0] / eh : 1.0;
+    east[2] = 0.0;
+    north[0] = up[1] * east[2] - up[2] * east[1];
+    north[1] = up[2] * east[0] - up[0] * east[2];
+    north[2] = up[0] * east[1] - up[1] * east[0];
+}
+
 // topo_pixel_angles, in f64: the ray through pixel-space point (x, y) is the line between the points the inverse of camera_proj maps
 // it to on the near (NDC z 0) and the far (z 1) plane -- no f32 eye enters the direction -- seen in the local east / north / up
 // frame at the eye (up = the eye's geocentric radius; geometry_transform's axes: x to (0 N, 0 E), z to the north pole).
@@ -79,12 +96,8 @@ void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n,
         for (int r = 0; r < 4; ++r) p[r] = inv[r][4] * nx + inv[r][5] * ny + inv[r][6] * nz + inv[r][7];
         for (int k = 0; k < 3; ++k) out[k] = p[k] / p[3];
     };
-    const double ex = view->camera_pos[0], ey = view->camera_pos[1], ez = view->camera_pos[2];
-    const double el = std::sqrt(ex * ex + ey * ey + ez * ez);
-    const double up[3] = {ex / el, ey / el, ez / el};
-    const double eh = std::hypot(up[0], up[1]);
-    const double east[3] = {eh > 0.0 ? -up[1] / eh : 0.0, eh > 0.0 ? up[0] / eh : 1.0, 0.0};      // z x up (at a pole: +y)
-    const double north[3] = {up[1] * east[2] - up[2] * east[1], up[2] * east[0] - up[0] * east[2], up[0] * east[1] - up[1] * east[0]};
+    double east[3], north[3], up[3];
+    local_frame(view->camera_pos, east, north, up);
     const double kDeg = 180.0 / 3.14159265358979323846;
     for (uint32_t i = 0; i < n; ++i) {
         const double nx = 2.0 * xy[2 * i] / w - 1.0, ny = 1.0 - 2.0 * xy[2 * i + 1] / h;
@@ -99,6 +112,53 @@ void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n,
         if (az < 0.0) az += 360.0;
         az_el[2 * i] = az;
         az_el[2 * i + 1] = std::atan2(du, std::hypot(de, dn)) * kDeg;
+    }
+}
+
+// ---- unwrap (topo_unwrap_*): parameter checks, the f64 tables of k_unwrap (topo_unwrap.h), the inverse mapping ----------------------
+const char* unwrap_params_error(const topo_unwrap_params* p) {
+    if (!p) return "null parameters";
+    if (p->projection > TOPO_UNWRAP_CYLINDRICAL || p->filter > TOPO_UNWRAP_BILINEAR) return "unknown projection or filter";
+    if (p->out_w == 0 || p->out_h == 0) return "output size must be non-zero";
+    if (!(p->az_span_deg > 0.0 && p->az_span_deg <= 360.0) || !std::isfinite(p->az0_deg)) return "az_span_deg must be in (0, 360] and az0_deg finite";
+    if (!(p->el_bottom_deg > -90.0 && p->el_bottom_deg < p->el_top_deg && p->el_top_deg < 90.0)) return "elevations must satisfy -90 < bottom < top < 90";
+    return nullptr;
+}
+
+const char* unwrap_views_error(uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h) {
+    if (!views || n_views == 0 || n_views > kUnwrapMaxViews) return "1 .. 64 views";
+    if (src_w == 0 || src_h == 0) return "source size must be non-zero";
+    for (uint32_t k = 1; k < n_views; ++k)
+        if (memcmp(views[k].camera_pos, views[0].camera_pos, 3 * sizeof(float)) != 0) return "the views must share one eye (camera_pos bitwise equal)";
+    return nullptr;
+}
+
+void unwrap_tables(const topo_unwrap_params* p, uint32_t n_views, const topo_uniforms* views, std::vector<double>& out) {
+    out.assign(unwrap_table_doubles(n_views, p->out_w, p->out_h), 0.0);
+    double east[3], north[3], up[3];
+    local_frame(views[0].camera_pos, east, north, up);
+    for (int k = 0; k < 3; ++k) out[k] = up[k];
+    static const int kRows[3] = {0, 1, 3};
+    for (uint32_t v = 0; v < n_views; ++v)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) out[kUnwrapViewsAt + (size_t)kUnwrapViewDoubles * v + 3 * r + c] = (double)views[v].camera_proj[4 * c + kRows[r]];
+    double* cols = out.data() + unwrap_cols_at(n_views);
+    for (uint32_t c = 0; c < p->out_w; ++c) unwrap_column(p->az0_deg, p->az_span_deg, p->out_w, c, east, north, cols + 3 * (size_t)c);
+    double* rows = out.data() + unwrap_rows_at(n_views, p->out_w);
+    for (uint32_t r = 0; r < p->out_h; ++r)
+        unwrap_row_entry(p->projection == TOPO_UNWRAP_CYLINDRICAL, p->el_top_deg, p->el_bottom_deg, p->out_h, r, rows[2 * (size_t)r], rows[2 * (size_t)r + 1]);
+}
+
+// The inverse of the tables' mapping: column c's centre has x = c + 0.5, row r's centre y = r + 0.5.
+void unwrap_xy(const topo_unwrap_params* p, uint32_t n, const double* az_el, double* xy) {
+    const bool cyl = p->projection == TOPO_UNWRAP_CYLINDRICAL;
+    const double tt = std::tan(p->el_top_deg * kUnwrapRad), tb = std::tan(p->el_bottom_deg * kUnwrapRad);
+    for (uint32_t i = 0; i < n; ++i) {
+        double a = std::fmod(az_el[2 * i] - p->az0_deg, 360.0);
+        if (a < 0.0) a += 360.0;
+        const double el = az_el[2 * i + 1];
+        xy[2 * i] = a / p->az_span_deg * (double)p->out_w;
+        xy[2 * i + 1] = (cyl ? (tt - std::tan(el * kUnwrapRad)) / (tt - tb) : (p->el_top_deg - el) / (p->el_top_deg - p->el_bottom_deg)) * (double)p->out_h;
     }
 }
 

@@ -16,6 +16,14 @@ void panorama_uniforms(const float eye[3], float yaw0, float pitch, uint32_t sec
                        int32_t view_mode, uint32_t n_sectors, topo_uniforms* out);
 void geometry_transform(float h, float lon_deg, float lat_deg, float out[3]);
 void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n, const float* xy, double* az_el);
+// up = eye / |eye|, east = z x up normalised (at a pole: +y), north = up x east: the frame of topo_pixel_angles and topo_unwrap_*
+void local_frame(const float eye[3], double east[3], double north[3], double up[3]);
+// unwrap (topo_unwrap_*): why the parameters / the views cannot be unwrapped (null: they can); the f64 tables k_unwrap reads
+// (topo_unwrap.h has their layout); output-pixel coordinates of azimuth / elevation pairs
+const char* unwrap_params_error(const topo_unwrap_params* p);
+const char* unwrap_views_error(uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h);
+void unwrap_tables(const topo_unwrap_params* p, uint32_t n_views, const topo_uniforms* views, std::vector<double>& out);
+void unwrap_xy(const topo_unwrap_params* p, uint32_t n, const double* az_el, double* xy_out);
 void terrain_rotation(float model_lon_deg, float model_lat_deg, float rot3x3_colmajor[9]);
 uint32_t locations_range(float latitude, float longitude, float range_dist, int32_t* out_lat_lon, uint32_t cap);
 void change_location_plan(float latitude, float longitude, float range_dist, const int32_t* loaded, uint32_t n_loaded,

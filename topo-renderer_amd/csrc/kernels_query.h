@@ -3,10 +3,13 @@
 //   k_viewshed   behind the frame's last k_resolve: the DEM cells that own a pixel, OR-ed into per-tile bit masks
 //   k_horizon    per view and column, the topmost pixel that shows terrain, decoded to its tile and cell
 //   k_ground     per queried pixel, the terrain point under it (f64: topo_ground.h); k_ground_map: the same for every pixel of whole views
+// and the one query over finished IMAGES:
+//   k_unwrap     a strip of perspective views resampled into one azimuth / elevation image (f64: topo_unwrap.h)
 #pragma once
 
 #include "kernels_common.h"
 #include "topo_ground.h"
+#include "topo_unwrap.h"
 
 namespace topo {
 namespace {
@@ -318,6 +321,130 @@ __global__ __launch_bounds__(256) void k_ground_map(GroundParams P, uint8_t* __r
         uint8_t* const dst = out + (size_t)(v - P.q.first_view) * view_stride + (size_t)y * pitch + (size_t)x * 16;
         __builtin_nontemporal_store(val, reinterpret_cast<u32x4_t*>(dst));
     }
+}
+
+// ---- unwrap (topo_unwrap_*) ---------------------------------------------------------------------------------------------------
+// Views that share an eye, resampled into one image whose columns are linear in azimuth and whose rows are linear in elevation (or
+// its tangent): topo_unwrap.h has the mapping, the seam rule and the tables.  A workgroup takes 256 columns of four rows, a wave one
+// of the rows, a lane four consecutive pixels of it: the row's (cos, sin), up and the views' matrices are wave-uniform and come over
+// the scalar path (the tables were written by an earlier copy: constant address space), the four columns' h vectors are six 16-byte
+// loads, and each output is one 16-byte non-temporal store per lane (nothing here reads them again); a ragged last group of a row
+// stores its pixels one by one.  Neighbouring output pixels read neighbouring source texels, row by row of the source.
+// The views' cw rows are applied to all four pixels view by view; the winner's rows 0 and 1 are then fetched once per view that
+// won a pixel of the wave (one or two of them: a wave spans at most 256 columns), still as scalars.  Only a pixel its nearest-axis
+// view does not contain (beyond the vertical field of view, a gap of a pitched panorama) takes unwrap_scan.
+template <bool kBilinear>
+__global__ __launch_bounds__(256) void k_unwrap(UnwrapParams P) {
+    [[maybe_unused]] __shared__ float s_thresh[256], s_decode[256];
+    if constexpr (kBilinear) {
+        if (P.srgb) {
+            s_thresh[threadIdx.x] = bits_f(TOPO_SRGB_THRESH_BITS[threadIdx.x]);
+            s_decode[threadIdx.x] = bits_f(TOPO_SRGB_DECODE_BITS[threadIdx.x]);
+            __syncthreads();
+        }
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t by = blockIdx.x / P.blocks_x, bx = blockIdx.x - by * P.blocks_x;
+    const uint32_t r = wave_first(by * 4 + (threadIdx.x >> 6));
+    const uint32_t c0 = (bx * 64 + lane) * 4;
+    if (r >= P.out_h || c0 >= P.out_w) return;
+    const auto tab = const_space(P.tab);
+    const auto views = tab + kUnwrapViewsAt;
+    const size_t row_at = unwrap_rows_at(P.n_views, P.out_w) + 2 * (size_t)r;
+    const double ce = tab[row_at], se = tab[row_at + 1];
+    const double up[3] = {tab[0], tab[1], tab[2]};
+    // (c0 + 3 is inside the padded column table: the host sizes it to a multiple of four columns)
+    const double2* const hc = reinterpret_cast<const double2*>(P.tab + unwrap_cols_at(P.n_views) + 3 * (size_t)c0);
+    double2 hv[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) hv[i] = hc[i];
+    const double hs[12] = {hv[0].x, hv[0].y, hv[1].x, hv[1].y, hv[2].x, hv[2].y, hv[3].x, hv[3].y, hv[4].x, hv[4].y, hv[5].x, hv[5].y};
+    double d[4][3], best[4];
+    uint32_t kb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        unwrap_dir(ce, se, hs + 3 * j, up, d[j]);
+        best[j] = unwrap_row(views + 6, d[j]);
+        kb[j] = 0;
+    }
+    for (uint32_t k = 1; k < P.n_views; ++k) {
+        const auto m = views + (size_t)kUnwrapViewDoubles * k + 6;
+        const double m0 = m[0], m1 = m[1], m2 = m[2];
+        const double row[3] = {m0, m1, m2};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double cw = unwrap_row(row, d[j]);
+            if (cw > best[j]) { best[j] = cw; kb[j] = k; }
+        }
+    }
+    UnwrapSource src[4];
+    bool found[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        src[j] = UnwrapSource{(int32_t)kb[j], 0.0, 0.0};
+        found[j] = false;
+    }
+    // the winners' rows 0 and 1: once per view that won a pixel of the wave
+    for (uint32_t k = 0; k < P.n_views; ++k) {
+        bool mine[4];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            mine[j] = kb[j] == k;
+            any |= mine[j];
+        }
+        if (!__ballot(any)) continue;
+        const auto m = views + (size_t)kUnwrapViewDoubles * k;
+        const double mm[6] = {m[0], m[1], m[2], m[3], m[4], m[5]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (mine[j]) found[j] = unwrap_project(mm, d[j], best[j], P.src_w, P.src_h, src[j].px, src[j].py);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (!found[j]) src[j] = unwrap_scan(views, P.n_views, P.src_w, P.src_h, d[j]);
+
+    u32x4_t rgba = {0u, 0u, 0u, 0u}, depth = {kUnwrapNoDepthBits, kUnwrapNoDepthBits, kUnwrapNoDepthBits, kUnwrapNoDepthBits};
+    u32x4_t smap = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (src[j].view < 0) continue;
+        const uint32_t v = (uint32_t)src[j].view, sx = (uint32_t)floor(src[j].px), sy = (uint32_t)floor(src[j].py);
+        // (the product build trusts unwrap_project's containment test; the check build tests what it yields)
+        if (!TOPO_CHK(P.check, v < P.n_views && sx < P.src_w && sy < P.src_h, 19u, ((uint64_t)v << 48) | ((uint64_t)sy << 24) | sx)) continue;
+        smap[j] = (uint32_t)unwrap_source_index(v, sx, sy, P.src_w, P.src_h);
+        if (P.depth_out) depth[j] = *reinterpret_cast<const uint32_t*>(P.depth_src + (size_t)v * P.depth_view_stride + (size_t)sy * P.depth_pitch + (size_t)sx * 4);
+        if (!P.rgba_out) continue;
+        const uint8_t* const img = P.rgba_src + (size_t)v * P.rgba_view_stride;
+        if constexpr (kBilinear) {
+            const UnwrapTaps t = unwrap_taps(src[j].px, src[j].py, P.src_w, P.src_h);
+            if (!TOPO_CHK(P.check, t.x[0] < P.src_w && t.x[1] < P.src_w && t.y[0] < P.src_h && t.y[1] < P.src_h && t.fx < 256u && t.fy < 256u, 19u,
+                          ((uint64_t)t.y[1] << 32) | t.x[1]))
+                continue;
+            const uint8_t* const r0 = img + (size_t)t.y[0] * P.rgba_pitch, * const r1 = img + (size_t)t.y[1] * P.rgba_pitch;
+            const uint32_t t00 = *reinterpret_cast<const uint32_t*>(r0 + (size_t)t.x[0] * 4), t10 = *reinterpret_cast<const uint32_t*>(r0 + (size_t)t.x[1] * 4);
+            const uint32_t t01 = *reinterpret_cast<const uint32_t*>(r1 + (size_t)t.x[0] * 4), t11 = *reinterpret_cast<const uint32_t*>(r1 + (size_t)t.x[1] * 4);
+            rgba[j] = unwrap_blend(t00, t10, t01, t11, t.fx, t.fy, P.srgb != 0u, s_thresh, s_decode);
+        } else {
+            rgba[j] = *reinterpret_cast<const uint32_t*>(img + (size_t)sy * P.rgba_pitch + (size_t)sx * 4);
+        }
+    }
+    if (!TOPO_CHK(P.check, r < P.out_h && c0 < P.out_w, 19u, ((uint64_t)r << 32) | c0)) return;
+    const bool whole = c0 + 4 <= P.out_w;
+    auto put = [&](uint8_t* base, size_t pitch, const u32x4_t& val) {
+        if (!base) return;
+        uint8_t* const dst = base + (size_t)r * pitch + (size_t)c0 * 4;
+        if (whole) {
+            __builtin_nontemporal_store(val, reinterpret_cast<u32x4_t*>(dst));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 3; ++j)      // (a ragged group holds one to three pixels)
+                if (c0 + j < P.out_w) reinterpret_cast<uint32_t*>(dst)[j] = val[j];
+        }
+    };
+    put(P.rgba_out, P.rgba_out_pitch, rgba);
+    put(P.depth_out, P.depth_out_pitch, depth);
+    put(P.src_out, P.src_out_pitch, smap);
 }
 
 }  // namespace

@@ -919,11 +919,17 @@ int TerrainRenderer::query_tables(hipStream_t s) {
         if (!hz_ll_.empty()) TOPO_HIP_TRY(hipMemcpyAsync(d_hz_ll_.p, hz_ll_.data(), hz_ll_.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
         hz_ll_gen_ = tile_gen_;
     }
+    return ensure_query_check(s);
+}
+
+int TerrainRenderer::ensure_query_check(hipStream_t s) {
 #ifdef TOPO_BOUNDS_CHECK
     if (!d_hz_check_.p) {
         if (int rc = ensure(s, d_hz_check_, kStatusWords * sizeof(uint32_t))) return rc;
         TOPO_HIP_TRY(hipMemsetAsync(d_hz_check_.p, 0, kStatusWords * sizeof(uint32_t), s));
     }
+#else
+    (void)s;
 #endif
     return TOPO_OK;
 }
@@ -1091,6 +1097,72 @@ int TerrainRenderer::ground_map_device(uint32_t first, uint32_t n, float* out_de
     launch_ground_map(p, out_dev, view_stride, pitch, s);
     TOPO_HIP_TRY(hipGetLastError());
     if (s != stream_) c->pending = true;
+    return TOPO_OK;
+}
+
+// ---- unwrap -------------------------------------------------------------------------------------------------------------------
+
+// Queued on stream_, in order, like topo_visible_peaks_device: the sources are the caller's, whatever wrote them.  The tables are
+// rebuilt (host, f64) and uploaded only when the parameters, the views' matrices or the eye differ from the last call's.
+int TerrainRenderer::unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h,
+                                   const OutputParams& src, const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch) {
+    if (const char* why = unwrap_params_error(params)) return fail(TOPO_ERR_INVALID, why);
+    if (const char* why = unwrap_views_error(n_views, views, src_w, src_h)) return fail(TOPO_ERR_INVALID, why);
+    if (!out.rgba && !out.depth && !src_out_dev) return fail(TOPO_ERR_INVALID, "at least one output must be given");
+    if ((out.rgba && !src.rgba) || (out.depth && !src.depth)) return fail(TOPO_ERR_INVALID, "an output needs its source");
+    const size_t row = (size_t)params->out_w * 4, src_row = (size_t)src_w * 4;
+    auto bad_out = [&](const void* p, size_t pitch) { return p && ((uintptr_t)p % 16 != 0 || pitch % 16 != 0 || pitch < row); };
+    if (bad_out(out.rgba, out.rgba_pitch) || bad_out(out.depth, out.depth_pitch) || bad_out(src_out_dev, src_out_pitch))
+        return fail(TOPO_ERR_INVALID, "output pointers and pitches must be multiples of 16 bytes, a pitch at least a row");
+    auto bad_src = [&](const void* p, size_t stride, size_t pitch) {
+        return p && ((uintptr_t)p % 4 != 0 || pitch % 4 != 0 || stride % 4 != 0 || pitch < src_row || (n_views > 1 && stride < pitch * (src_h - 1) + src_row));
+    };
+    if ((out.rgba && bad_src(src.rgba, src.rgba_view_stride, src.rgba_pitch)) || (out.depth && bad_src(src.depth, src.depth_view_stride, src.depth_pitch)))
+        return fail(TOPO_ERR_INVALID, "source pointers, pitches and view strides must be multiples of 4 bytes, a pitch at least a row, a stride at least a view");
+    if (src_out_dev && (uint64_t)n_views * src_h * src_w >= (1ull << 31)) return fail(TOPO_ERR_INVALID, "the source map needs n_views * src_h * src_w < 2^31");
+    if ((((uint64_t)params->out_w + 255) / 256) * (((uint64_t)params->out_h + 3) / 4) > 0x7FFFFFFFull) return fail(TOPO_ERR_INVALID, "output too large");
+    if (int rc = bind_device()) return rc;
+
+    std::vector<uint8_t> key(sizeof *params + sizeof(uint32_t) + 3 * sizeof(float) + (size_t)n_views * 16 * sizeof(float));
+    uint8_t* k = key.data();
+    memcpy(k, params, sizeof *params); k += sizeof *params;
+    memcpy(k, &n_views, sizeof n_views); k += sizeof n_views;
+    memcpy(k, views[0].camera_pos, 3 * sizeof(float)); k += 3 * sizeof(float);
+    for (uint32_t v = 0; v < n_views; ++v, k += 16 * sizeof(float)) memcpy(k, views[v].camera_proj, 16 * sizeof(float));
+    const size_t tab_bytes = unwrap_table_doubles(n_views, params->out_w, params->out_h) * sizeof(double);
+    if (key != unwrap_key_ || !d_unwrap_tab_.p) {
+        // an earlier unwrap may still read the old tables, an earlier upload the old host copy: both are on stream_
+        TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+        unwrap_key_.clear();
+        unwrap_tables(params, n_views, views, unwrap_tab_);
+        if (int rc = ensure(stream_, d_unwrap_tab_, tab_bytes)) return rc;
+        TOPO_HIP_TRY(hipMemcpyAsync(d_unwrap_tab_.p, unwrap_tab_.data(), tab_bytes, hipMemcpyHostToDevice, stream_));
+        unwrap_key_ = std::move(key);
+    }
+    if (int rc = ensure_query_check(stream_)) return rc;
+    UnwrapParams p{};
+    p.tab = d_unwrap_tab_.as<const double>();
+    p.rgba_src = out.rgba ? src.rgba : nullptr;
+    p.rgba_view_stride = src.rgba_view_stride;
+    p.rgba_pitch = src.rgba_pitch;
+    p.depth_src = out.depth ? reinterpret_cast<const uint8_t*>(src.depth) : nullptr;
+    p.depth_view_stride = src.depth_view_stride;
+    p.depth_pitch = src.depth_pitch;
+    p.rgba_out = out.rgba;
+    p.rgba_out_pitch = out.rgba_pitch;
+    p.depth_out = reinterpret_cast<uint8_t*>(out.depth);
+    p.depth_out_pitch = out.depth_pitch;
+    p.src_out = reinterpret_cast<uint8_t*>(src_out_dev);
+    p.src_out_pitch = src_out_pitch;
+    p.check = d_hz_check_.as<uint32_t>();
+    p.n_views = n_views;
+    p.src_w = src_w;
+    p.src_h = src_h;
+    p.out_w = params->out_w;
+    p.out_h = params->out_h;
+    p.srgb = format_ == TOPO_FORMAT_RGBA8_UNORM_SRGB || format_ == TOPO_FORMAT_BGRA8_UNORM_SRGB;
+    launch_unwrap(p, params->filter == TOPO_UNWRAP_BILINEAR, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
 }
 

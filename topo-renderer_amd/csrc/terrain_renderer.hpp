@@ -163,6 +163,10 @@ class TerrainRenderer {
     int ground_device(uint32_t n, const topo_ground_query* queries_dev, topo_ground_point* out_dev);
     int ground_map_device(uint32_t first_view, uint32_t n_views, float* out_dev, size_t view_stride_bytes, size_t pitch_bytes);
 
+    // unwrap: finished views that share an eye as one azimuth / elevation image (topo_unwrap_device)
+    int unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h, const OutputParams& src,
+                      const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch);
+
     const char* last_error() const { return err_.c_str(); }
 
    private:
@@ -330,11 +334,18 @@ class TerrainRenderer {
     // what the horizon and ground queries share: the latest submission if views [first, first + n) of it can be answered, the tables
     // a query kernel reads, the end of a host read (wait, fold the submission's status), the bounds record of the check build
     int query_prepare(uint32_t first_view, uint32_t n_views, FrameCtx** c, hipStream_t* s);
+    int ensure_query_check(hipStream_t s);      // the check build's bounds record of the query kernels (the product build: nothing)
     int query_tables(hipStream_t s);
     int query_finish_read(FrameCtx& c, hipStream_t s, const char* what);
     int query_fold_check();
     int horizon_launch(FrameCtx& c, uint32_t first_view, uint32_t n_views, HorizonPoint* out, size_t view_stride, hipStream_t s);
     int ground_params(FrameCtx& c, hipStream_t s, GroundParams& p);
+
+    // unwrap: the device copy of k_unwrap's f64 tables (topo_unwrap.h), kept for the parameter set they were built from -- the call's
+    // parameters, the views' direction blocks and the eye (unwrap_key_) -- and their host copy, the source of the upload
+    DeviceBuffer d_unwrap_tab_;
+    std::vector<double> unwrap_tab_;
+    std::vector<uint8_t> unwrap_key_;
 
     std::string err_;
 };

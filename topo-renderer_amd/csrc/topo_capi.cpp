@@ -395,6 +395,30 @@ int topo_ground_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views,
     TOPO_CALL(ctx->r->ground_map_device(first_view, n_views, out_dev, view_stride_bytes, pitch_bytes));
 }
 
+int topo_unwrap_device(topo_ctx* ctx, const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h,
+                       const uint8_t* rgba_src_dev, size_t rgba_view_stride, size_t rgba_pitch, const float* depth_src_dev, size_t depth_view_stride,
+                       size_t depth_pitch, uint8_t* rgba_out_dev, size_t rgba_out_pitch, float* depth_out_dev, size_t depth_out_pitch, int32_t* src_out_dev,
+                       size_t src_out_pitch) {
+    TOPO_GUARD(ctx);
+    topo::OutputParams src{}, out{};
+    src.rgba = const_cast<uint8_t*>(rgba_src_dev);      // (read only: OutputParams is the shape the images have)
+    src.rgba_view_stride = rgba_view_stride;
+    src.rgba_pitch = rgba_pitch;
+    src.depth = const_cast<float*>(depth_src_dev);
+    src.depth_view_stride = depth_view_stride;
+    src.depth_pitch = depth_pitch;
+    out.rgba = rgba_out_dev;
+    out.rgba_pitch = rgba_out_pitch;
+    out.depth = depth_out_dev;
+    out.depth_pitch = depth_out_pitch;
+    TOPO_CALL(ctx->r->unwrap_device(params, n_views, views, src_w, src_h, src, out, src_out_dev, src_out_pitch));
+}
+
+void topo_unwrap_xy(const topo_unwrap_params* params, uint32_t n, const double* az_el, double* xy_out) {
+    if (topo::unwrap_params_error(params) || (n && (!az_el || !xy_out))) return;
+    topo::unwrap_xy(params, n, az_el, xy_out);
+}
+
 void topo_pixel_angles(const topo_uniforms* view, uint32_t width, uint32_t height, uint32_t n, const float* xy, double* az_el_out) {
     if (!view || !az_el_out || (n && !xy) || width == 0 || height == 0) return;
     topo::pixel_angles(view, width, height, n, xy, az_el_out);

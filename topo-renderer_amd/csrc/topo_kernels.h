@@ -6,6 +6,7 @@
 
 #include "topo_pipeline.h"
 #include "topo_ground.h"
+#include "topo_unwrap.h"
 
 namespace topo {
 
@@ -207,6 +208,28 @@ void launch_ground_tables(const TileDev* tiles, uint32_t n_tiles, double* trig, 
 void launch_ground(const GroundParams& p, const GroundQuery* queries, GroundPoint* out, uint32_t n, hipStream_t s);
 // float4 (lon, lat, height, range) per pixel of views [p.q.first_view, + p.q.n_views): view i at out + i * view_stride, rows pitch apart (bytes)
 void launch_ground_map(const GroundParams& p, float* out, size_t view_stride, size_t pitch, hipStream_t s);
+
+// unwrap (topo_unwrap_*): n_views views of src_w x src_h that share an eye, resampled into one out_w x out_h azimuth / elevation
+// image (topo_unwrap.h).  Reads the tables and the source images; writes only the outputs given (each nullable; rgba_out needs
+// rgba_src, depth_out needs depth_src).
+struct UnwrapParams {
+    const double* tab;            // the f64 tables: unwrap_table_doubles(n_views, out_w, out_h) doubles (host_math.hpp: unwrap_tables)
+    const uint8_t* rgba_src;      // view k at + k * rgba_view_stride, rows rgba_pitch apart (bytes)
+    size_t rgba_view_stride, rgba_pitch;
+    const uint8_t* depth_src;
+    size_t depth_view_stride, depth_pitch;
+    uint8_t* rgba_out;            // rows *_out_pitch apart (bytes; pointers and pitches multiples of 16)
+    size_t rgba_out_pitch;
+    uint8_t* depth_out;
+    size_t depth_out_pitch;
+    uint8_t* src_out;             // int32 source map
+    size_t src_out_pitch;
+    uint32_t* check;              // TOPO_BOUNDS_CHECK build: the queries' status record; else unused
+    uint32_t n_views, src_w, src_h, out_w, out_h;
+    uint32_t blocks_x;            // workgroups per four output rows: ceil(out_w / 256) (set by the launcher)
+    uint32_t srgb;                // 1: *Srgb format (bilinear blends in linear light)
+};
+void launch_unwrap(const UnwrapParams& p, bool bilinear, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // overlay pass (line_shader.wgsl over the post pass's image): keys = W*H overlay keys, (re-)initialised when keys_fresh
 void launch_overlay(const OverlayVertex* verts, const uint32_t* idx, uint32_t n_tris, uint32_t n_verts, float width, int32_t W, int32_t H, uint64_t* keys,

@@ -5,7 +5,7 @@
 //   kernels_load.h      load phase (once per add_terrain): block tables, sin/cos tables, cull bounds, normals
 //   kernels_frame.h     frame phase: view constants, clear, cull, occlusion filter, the three raster kernels
 //   kernels_resolve.h   k_resolve: shading of each pixel's winner + the post pass
-//   kernels_query.h     viewshed, horizon and ground points, over a finished frame's visibility buffer
+//   kernels_query.h     viewshed, horizon and ground points, over a finished frame's visibility buffer; the unwrap of finished images
 //   kernels_overlay.h   pixelise post pass, line / glyph overlays, visible peaks
 //   kernels_tiff.h      GeoTIFF rows, unit-test probes
 //
@@ -262,6 +262,15 @@ void launch_ground_map(const GroundParams& p, float* out, size_t view_stride, si
     const uint64_t waves = ((k1 + 63) >> 6) - (k0 >> 6);      // one per 64-key segment the views touch; past 2^20 workgroups they stride
     const uint64_t blocks = (waves + 3) / 4;
     hipLaunchKernelGGL(k_ground_map, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(256), 0, s, p, (uint8_t*)out, view_stride, pitch);
+}
+
+void launch_unwrap(const UnwrapParams& p, bool bilinear, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    UnwrapParams q = p;
+    q.blocks_x = (p.out_w + 255) / 256;      // 256 columns x 4 rows per workgroup
+    const uint64_t blocks = (uint64_t)q.blocks_x * ((p.out_h + 3) / 4);
+    if (blocks == 0 || blocks > 0x7FFFFFFFull) return;      // (the host has refused such sizes)
+    if (bilinear) launch_timed(k_unwrap<true>, dim3((unsigned)blocks), dim3(256), s, start, stop, q);
+    else launch_timed(k_unwrap<false>, dim3((unsigned)blocks), dim3(256), s, start, stop, q);
 }
 
 // the overlay key image of a W x H target, (re-)initialised where the caller's keys are fresh
