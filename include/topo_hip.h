@@ -387,6 +387,58 @@ int topo_ground_device(topo_ctx* ctx, uint32_t n, const topo_ground_query* queri
  * the ground at |lon| >= 128 degrees (half that below 128, and so on); the list calls give f64.  Asynchronous, as topo_ground_device. */
 int topo_ground_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, float* out_dev, size_t view_stride_bytes, size_t pitch_bytes);
 
+/* ---- rays: line of sight over the resident tiles -------------------------------------------------------------------------------
+ * "Can the summit at B be seen from the hut at A?"  A ray p(t) = origin + t * dir (f64 ECEF metres, the frame of
+ * topo_geometry_transform; dir need not be unit: with dir = B - A, t in [0, 1] is the segment from A to B) against every triangle of
+ * every resident tile -- the triangles the renderer draws: the vertices of the ground queries (the f32 tile transform and height
+ * widened, f64 from there on), the index-buffer topology, both faces.  A triangle with a non-finite vertex height does not exist;
+ * finite sentinel heights are geometry, as in the frame.  The test is Moeller-Trumbore in f64 on vertices translated by the origin:
+ * hit iff u >= 0, v >= 0, u + v <= 1, t_min <= t <= t_max and t finite.  The hit reported is the one with the smallest t; on equal t
+ * the tile that comes first in draw order, then the lower triangle index.  front = 1 when the ray meets the side the renderer
+ * draws (N . dir < 0 with N = (v1 - v0) x (v2 - v0)).  A ray with a non-finite origin or direction component, a zero dir or
+ * !(t_min <= t_max) is TOPO_RAY_INVALID; infinite bounds are allowed.  An endpoint that lies ON the terrain touches its own triangle
+ * at t = 0 (or 1) within rounding: for "is B visible from A" lift the endpoints off the ground or keep t_min / t_max short of them.
+ * The calls read the resident tiles only and need no submission; they run on the context's stream (topo_set_stream) behind whatever
+ * was queued there, and write nothing but their outputs.  With no tiles every valid ray misses; n = 0 is a no-op.
+ * TOPO_ERR_INVALID for null or misaligned pointers. */
+typedef struct topo_ray { double origin[3]; double dir[3]; double t_min, t_max; } topo_ray;      /* 64 bytes */
+typedef struct topo_ray_hit {            /* 64 bytes; written as 16-byte stores */
+    double t;                            /* hit point = origin + t * dir */
+    double lon_deg, lat_deg;             /* of the hit point, as topo_ground_point defines them */
+    float height_m;                      /* |p| - R0, the f64 value rounded once */
+    int32_t kind;                        /* TOPO_RAY_*; every other field is 0 unless TOPO_RAY_HIT */
+    int32_t tile_lat_deg, tile_lon_deg;  /* tile of the triangle hit */
+    uint32_t cell_x, cell_y;             /* its cell: viewshed / horizon / ground numbering */
+    uint32_t tri, front;                 /* tri = triangle & 1 (index-buffer order within the cell) */
+    float w1, w2;                        /* Moeller-Trumbore u, v: the weights of the triangle's second and third vertex */
+} topo_ray_hit;
+#define TOPO_RAY_HIT 1
+#define TOPO_RAY_MISS 0
+#define TOPO_RAY_INVALID (-1)
+/* Host memory, n rays -> n records; waits. */
+int topo_raycast_read(topo_ctx* ctx, uint32_t n, const topo_ray* rays, topo_ray_hit* out);
+/* Device memory (both 16-byte aligned); asynchronous on the context's stream. */
+int topo_raycast_device(topo_ctx* ctx, uint32_t n, const topo_ray* rays_dev, topo_ray_hit* out_dev);
+/* The first application: a lit / shadowed layer for views [first_view, first_view + n_views) of the latest submission (as the
+ * horizon and ground calls define it; their errors, stream order and handling of an overflowed submission), one byte per pixel:
+ * view i at out_dev + i * view_stride_bytes, rows pitch_bytes apart (device memory; pitch >= width, bytes between width and the
+ * pitch are left alone).  sun_dir points TOWARDS the sun (topo_uniforms.sun_direction widened, or topo_sun_direction) and is
+ * normalised in f64; zero or non-finite: TOPO_ERR_INVALID.  Per pixel: the ground point exactly as topo_ground_map_device finds it,
+ * its three barycentric weights clamped to >= 0 and renormalised so that it lies on the pixel's own triangle T0 (a piece of a
+ * near-clipped triangle answers with its original triangle); TOPO_SUN_AWAY if N(T0) . sun <= 0; otherwise the ray from that point
+ * along sun against every triangle except T0, a hit counting for 1e-3 m < t <= 1e6 m: any hit TOPO_SUN_SHADOW, none TOPO_SUN_LIT.
+ * The frame path shades with sun_direction but casts no shadows; this layer is what it leaves out.  Asynchronous. */
+#define TOPO_SUN_NONE 0     /* no terrain point: sky, degenerate, incomplete submission */
+#define TOPO_SUN_LIT 1
+#define TOPO_SUN_AWAY 2     /* the pixel's own triangle faces away from the sun: N . sun <= 0 */
+#define TOPO_SUN_SHADOW 3   /* faces the sun, other terrain is in the way */
+int topo_sunlit_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, const double sun_dir[3], uint8_t* out_dev, size_t view_stride_bytes,
+                           size_t pitch_bytes);
+/* Host helper, f64, no GPU: the unit ECEF direction at azimuth az_deg (clockwise from true north) and elevation el_deg over the
+ * horizontal plane of the point at (lon_deg, lat_deg), in the east / north / up frame of topo_pixel_angles and topo_unwrap_device
+ * (up = the geocentric radius).  The direction towards the sun for a ray from the ground, for one. */
+void topo_sun_direction(double lon_deg, double lat_deg, double az_deg, double el_deg, double dir_out[3]);
+
 /* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
  * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
  * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --

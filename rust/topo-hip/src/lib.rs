@@ -195,6 +195,43 @@ impl TerrainRenderer {
                                     depth_dev, row * sector.1 as usize, row, rgba_out_dev, out_row, depth_out_dev, out_row, ptr::null_mut(), 0)
         })
     }
+
+    /// Rays (new): for each ray `origin + t * dir` (f64 ECEF metres, `t` in `[t_min, t_max]` in units of `|dir|`) the first terrain
+    /// it meets among the resident tiles -- `kind` 1 hit, 0 miss, -1 invalid ray; `t`, the hit point's longitude / latitude / height,
+    /// the triangle's tile and cell, `front` = the side the renderer draws.  Needs no submission; waits.
+    pub fn raycast(&mut self, rays: &[sys::topo_ray]) -> Result<Vec<sys::topo_ray_hit>, TopoError> {
+        let n = u32::try_from(rays.len()).expect("topo_raycast_read takes at most u32::MAX rays");
+        let mut out = vec![sys::topo_ray_hit::default(); rays.len()];
+        check(self.ctx, unsafe { sys::topo_raycast_read(self.ctx, n, rays.as_ptr(), out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+
+    /// Line of sight (new): whether the segment from `a` to `b` (ECEF metres) is free of terrain -- one ray with `dir = b - a` and
+    /// `t` in `[margin / |b - a|, 1 - margin / |b - a|]`: the first and last `margin_m` metres do not count.  An endpoint that lies ON
+    /// the terrain (a hut, a summit) touches its own triangle at `t` = 0 or 1 within rounding, so either lift the endpoints off the
+    /// ground (an eye height, a mast) or give a margin; with `margin_m` 0 the interval is the closed `[0, 1]`.
+    pub fn line_of_sight(&mut self, a: [f64; 3], b: [f64; 3], margin_m: f64) -> Result<bool, TopoError> {
+        let dir = [b[0] - a[0], b[1] - a[1], b[2] - a[2]];
+        let m = margin_m / (dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]).sqrt();
+        let ray = sys::topo_ray { origin: a, dir, t_min: m, t_max: 1.0 - m };
+        Ok(self.raycast(&[ray])?[0].kind == sys::TOPO_RAY_MISS)
+    }
+
+    /// Sunlit layer (new): one byte per pixel (`sys::TOPO_SUN_*`) of views `[first_view, first_view + n_views)` of the latest
+    /// submission under a sun in direction `sun_dir` (towards the sun; see `sun_direction`), densely packed rows of `width` bytes
+    /// into `out_dev` (device memory).  Asynchronous, behind the submission.
+    pub fn sunlit_map(&mut self, first_view: u32, n_views: u32, sun_dir: [f64; 3], out_dev: *mut u8) -> Result<(), TopoError> {
+        let (mut n, mut w, mut h) = (0u32, 0u32, 0u32);
+        check(self.ctx, unsafe { sys::topo_horizon_shape(self.ctx, &mut n, &mut w, &mut h) })?;
+        check(self.ctx, unsafe { sys::topo_sunlit_map_device(self.ctx, first_view, n_views, sun_dir.as_ptr(), out_dev, w as usize * h as usize, w as usize) })
+    }
+}
+
+/// The unit ECEF direction at azimuth `az_deg` (clockwise from true north) and elevation `el_deg` at `(lon_deg, lat_deg)`: host, f64.
+pub fn sun_direction(lon_deg: f64, lat_deg: f64, az_deg: f64, el_deg: f64) -> [f64; 3] {
+    let mut out = [0f64; 3];
+    unsafe { sys::topo_sun_direction(lon_deg, lat_deg, az_deg, el_deg, out.as_mut_ptr()) };
+    out
 }
 
 impl Drop for TerrainRenderer {

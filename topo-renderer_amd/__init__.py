@@ -44,6 +44,12 @@ GROUND_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<
                          ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("fan", "<u4"),
                          ("w1", "<f4"), ("w2", "<f4")])
 GROUND_QUERY_DTYPE = np.dtype([("view", "<u4"), ("x", "<u4"), ("y", "<u4"), ("_reserved", "<u4")])
+RAY_HIT, RAY_MISS, RAY_INVALID = 1, 0, -1
+SUN_NONE, SUN_LIT, SUN_AWAY, SUN_SHADOW = 0, 1, 2, 3
+# topo_ray and topo_ray_hit, 64 bytes each
+RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("dir", "<f8", 3), ("t_min", "<f8"), ("t_max", "<f8")])
+RAY_HIT_DTYPE = np.dtype([("t", "<f8"), ("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f4"), ("kind", "<i4"), ("tile_lat_deg", "<i4"),
+                          ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("front", "<u4"), ("w1", "<f4"), ("w2", "<f4")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
 # topo_unwrap_params, 48 bytes
@@ -167,6 +173,10 @@ def lib():
             "topo_ground_read": (C.c_int, [vp, u32, vp, vp]),
             "topo_ground_device": (C.c_int, [vp, u32, vp, vp]),
             "topo_ground_map_device": (C.c_int, [vp, u32, u32, vp, sz, sz]),
+            "topo_raycast_read": (C.c_int, [vp, u32, vp, vp]),
+            "topo_raycast_device": (C.c_int, [vp, u32, vp, vp]),
+            "topo_sunlit_map_device": (C.c_int, [vp, u32, u32, vp, vp, sz, sz]),
+            "topo_sun_direction": (None, [C.c_double, C.c_double, C.c_double, C.c_double, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
         }
@@ -298,6 +308,23 @@ def ground_queries(queries) -> np.ndarray:
     q = q.reshape(-1, 3)
     out = np.zeros(len(q), GROUND_QUERY_DTYPE)
     out["view"], out["x"], out["y"] = q[:, 0], q[:, 1], q[:, 2]
+    return out
+
+
+def rays(origin, direction, t_min=0.0, t_max=np.inf) -> np.ndarray:
+    """RAY_DTYPE records (topo_ray) from origins and directions (f64 ECEF metres, (3,) or (n, 3), broadcast against each other) and
+    bounds on t (scalars or (n,)); dir need not be unit: dir = B - A with t in [0, 1] is the segment from A to B."""
+    o, d = np.broadcast_arrays(np.atleast_2d(np.asarray(origin, np.float64)), np.atleast_2d(np.asarray(direction, np.float64)))
+    out = np.zeros(len(o), RAY_DTYPE)
+    out["origin"], out["dir"], out["t_min"], out["t_max"] = o, d, t_min, t_max
+    return out
+
+
+def sun_direction(lon_deg: float, lat_deg: float, az_deg: float, el_deg: float) -> np.ndarray:
+    """topo_sun_direction: the unit f64 ECEF direction at azimuth az_deg (clockwise from true north) and elevation el_deg at the
+    point (lon_deg, lat_deg), in the east / north / up frame of pixel_angles and unwrap_device.  Host only."""
+    out = np.zeros(3, np.float64)
+    lib().topo_sun_direction(lon_deg, lat_deg, az_deg, el_deg, _p(out))
     return out
 
 
@@ -740,6 +767,30 @@ class TerrainRenderer:
         pitch = 16 * w if pitch_bytes is None else pitch_bytes
         stride = pitch * h if view_stride_bytes is None else view_stride_bytes
         self._check(lib().topo_ground_map_device(self._h, first_view, n, C.c_void_p(out_ptr), stride, pitch))
+
+    # rays against the resident tiles (include/topo_hip.h); no submission needed
+    def raycast(self, ray_records) -> np.ndarray:
+        """topo_raycast_read: RAY_DTYPE records (see rays()) -> RAY_HIT_DTYPE records; waits."""
+        r = np.ascontiguousarray(ray_records, dtype=RAY_DTYPE).reshape(-1)
+        out = np.zeros(len(r), RAY_HIT_DTYPE)
+        self._check(lib().topo_raycast_read(self._h, len(r), _p(r) if len(r) else None, _p(out) if len(r) else None))
+        return out
+
+    def raycast_device(self, rays_ptr: int, out_ptr: int, n: int):
+        """topo_raycast_device: n topo_ray at rays_ptr -> n topo_ray_hit at out_ptr (device memory, 16-byte aligned), queued on
+        the context's stream."""
+        self._check(lib().topo_raycast_device(self._h, n, C.c_void_p(rays_ptr) if rays_ptr else None, C.c_void_p(out_ptr) if out_ptr else None))
+
+    def sunlit_map_device(self, sun_dir, out_ptr: int, first_view: int = 0, n_views: int = None, view_stride_bytes: int = None, pitch_bytes: int = None):
+        """topo_sunlit_map_device: one byte (SUN_NONE / SUN_LIT / SUN_AWAY / SUN_SHADOW) for every pixel of the views of the latest
+        submission under a sun in direction sun_dir (f64, towards the sun; see sun_direction); view i at out_ptr + i *
+        view_stride_bytes, rows pitch_bytes apart (defaults: densely packed)."""
+        total, w, h = self.horizon_shape()
+        n = total - first_view if n_views is None else n_views
+        pitch = w if pitch_bytes is None else pitch_bytes
+        stride = pitch * h if view_stride_bytes is None else view_stride_bytes
+        sun = np.ascontiguousarray(sun_dir, dtype=np.float64).reshape(3)
+        self._check(lib().topo_sunlit_map_device(self._h, first_view, n, _p(sun), C.c_void_p(out_ptr) if out_ptr else None, stride, pitch))
 
     # unwrap: finished views that share an eye as one azimuth / elevation image (include/topo_hip.h)
     def unwrap_device(self, params, uniforms_list, src_w: int, src_h: int, rgba_src_ptr: int = 0, rgba_view_stride: int = None, rgba_pitch: int = None,

@@ -68,6 +68,18 @@ void local_frame(const float eye[3], double east[3], double north[3], double up[
     north[2] = up[0] * east[1] - up[1] * east[0];
 }
 
+// topo_sun_direction: local_frame's axes at (lon, lat) -- up = (cos lat cos lon, cos lat sin lon, sin lat), east = (-sin lon, cos lon, 0),
+// north = up x east -- and the direction cos el (sin az east + cos az north) + sin el up.
+void sun_direction(double lon_deg, double lat_deg, double az_deg, double el_deg, double out[3]) {
+    const double kRad = 3.14159265358979323846 / 180.0;
+    const double lo = lon_deg * kRad, la = lat_deg * kRad, az = az_deg * kRad, el = el_deg * kRad;
+    const double up[3] = {std::cos(la) * std::cos(lo), std::cos(la) * std::sin(lo), std::sin(la)};
+    const double east[3] = {-std::sin(lo), std::cos(lo), 0.0};
+    const double north[3] = {up[1] * east[2] - up[2] * east[1], up[2] * east[0] - up[0] * east[2], up[0] * east[1] - up[1] * east[0]};
+    const double ce = std::cos(el), se = std::sin(el), ca = std::cos(az), sa = std::sin(az);
+    for (int k = 0; k < 3; ++k) out[k] = ce * (sa * east[k] + ca * north[k]) + se * up[k];
+}
+
 // topo_pixel_angles, in f64: the ray through pixel-space point (x, y) is the line between the points the inverse of camera_proj maps
 // it to on the near (NDC z 0) and the far (z 1) plane -- no f32 eye enters the direction -- seen in the local east / north / up
 // frame at the eye (up = the eye's geocentric radius; geometry_transform's axes: x to (0 N, 0 E), z to the north pole).

@@ -18,6 +18,8 @@ void geometry_transform(float h, float lon_deg, float lat_deg, float out[3]);
 void pixel_angles(const topo_uniforms* view, uint32_t w, uint32_t h, uint32_t n, const float* xy, double* az_el);
 // up = eye / |eye|, east = z x up normalised (at a pole: +y), north = up x east: the frame of topo_pixel_angles and topo_unwrap_*
 void local_frame(const float eye[3], double east[3], double north[3], double up[3]);
+// topo_sun_direction: the unit direction at azimuth / elevation (degrees) in that frame at the point (lon, lat) (degrees), f64
+void sun_direction(double lon_deg, double lat_deg, double az_deg, double el_deg, double out[3]);
 // unwrap (topo_unwrap_*): why the parameters / the views cannot be unwrapped (null: they can); the f64 tables k_unwrap reads
 // (topo_unwrap.h has their layout); output-pixel coordinates of azimuth / elevation pairs
 const char* unwrap_params_error(const topo_unwrap_params* p);

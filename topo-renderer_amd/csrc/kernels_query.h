@@ -8,6 +8,7 @@
 #pragma once
 
 #include "kernels_common.h"
+#include "kernels_ground.h"
 #include "topo_ground.h"
 #include "topo_unwrap.h"
 
@@ -196,50 +197,8 @@ __global__ __launch_bounds__(256) void k_horizon(HorizonParams P) {
 // their longitude and latitude from the tiles' f64 tables (k_ground_tables); ground_solve (topo_ground.h, f64 throughout) finds the
 // point of the triangle's plane that the view maps to the pixel centre.  Launched by the query on the submission's stream, behind it;
 // the kernels read the keys, the marks, the status word, the tile table, the DEMs and the tables and write only their output.  Both
-// kernels answer a pixel through ground_answer: with -ffp-contract=off the list and the map agree bit for bit.
-struct GroundAnswer {
-    int32_t kind;
-    int32_t lat, lon;
-    GroundTri t;
-    GroundResult r;
-};
-
-// The per-triangle part of an answer: the key's low word decoded, the tile, and the ECEF positions of the three vertices.  false
-// (a.kind = degenerate) where the id names nothing of the tile set.
-__device__ __forceinline__ bool ground_triangle(const GroundParams& P, uint32_t id, GroundAnswer& a, double p[3][3]) {
-    a.kind = kGroundDegenerate;
-    a.t = ground_decode(id, P.q.tris_per_tile, P.q.hm1);
-    // (the rank and the vertex texels are tested in the product build too: what they index are tables and the DEM)
-    if (!(TOPO_CHK(P.q.check, a.t.rank < P.q.n_tiles, 18u, id) && a.t.rank < P.q.n_tiles)) return false;
-    a.lat = P.q.tile_ll[2 * (size_t)a.t.rank];
-    a.lon = P.q.tile_ll[2 * (size_t)a.t.rank + 1];
-    const TileDev& t = P.tiles[a.t.rank];
-    uint32_t vx[3], vy[3];
-    triangle_vertices(a.t.tri, P.q.hm1, vx, vy);
-    const size_t tab = (size_t)a.t.rank * ground_table_doubles(P.tile_w, P.tile_h);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const bool inside = vx[i] < P.tile_w && vy[i] < P.tile_h;
-        if (!(TOPO_CHK(P.q.check, inside, 18u, ((uint64_t)vy[i] << 32) | vx[i]) && inside)) return false;
-        const size_t lo = tab + 2 * (size_t)vx[i], la = tab + 2 * ((size_t)P.tile_w + vy[i]);
-        if (!TOPO_CHK(P.q.check, la + 1 < P.trig_doubles, 18u, la)) return false;
-        const double2 clo_slo = *reinterpret_cast<const double2*>(P.trig + lo), cla_sla = *reinterpret_cast<const double2*>(P.trig + la);
-        ground_vertex_from(TOPO_GLOBAL_F32(t.heights)[(size_t)vy[i] * P.tile_w + vx[i]], clo_slo.x, clo_slo.y, cla_sla.x, cla_sla.y, p[i]);
-    }
-    return true;
-}
-
-__device__ __forceinline__ GroundAnswer ground_answer(const GroundParams& P, uint64_t key, uint32_t view, uint32_t x, uint32_t y) {
-    GroundAnswer a{};
-    const uint32_t id = (uint32_t)key;
-    if (id == kNoTri) return a;      // kind 0: sky
-    double p[3][3];
-    if (!ground_triangle(P, id, a, p)) return a;
-    a.r = ground_solve(p, P.views[view], ground_ndc_x(x, P.q.W), ground_ndc_y(y, P.q.H));
-    if (a.r.ok) a.kind = kGroundTerrain;
-    return a;
-}
-
+// kernels answer a pixel through ground_answer (kernels_ground.h: device helpers, no kernel, shared with kernels_rays.h): with
+// -ffp-contract=off the list and the map agree bit for bit.
 // The tiles' f64 (cos, sin) tables (ground_table_doubles each, draw order): a lane per column or row, once per tile set.
 __global__ __launch_bounds__(256) void k_ground_tables(const TileDev* __restrict__ tiles, double* __restrict__ trig, uint32_t w, uint32_t h) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;

@@ -1010,21 +1010,38 @@ int TerrainRenderer::horizon_device(uint32_t first, uint32_t n, topo_horizon_poi
 static_assert(sizeof(GroundPoint) == sizeof(topo_ground_point) && sizeof(topo_ground_point) == 64, "ground record layout");
 static_assert(sizeof(GroundQuery) == sizeof(topo_ground_query) && sizeof(topo_ground_query) == 16, "ground query layout");
 
+// The tiles' f64 (cos, sin) tables and, for the rays, their spheres: once per tile set.
+int TerrainRenderer::ground_tables(hipStream_t s) {
+    if (ground_trig_gen_ == tile_gen_) return TOPO_OK;
+    // nothing that could still read the old tables is left running, and the new ones are complete before a query can be queued
+    // on any other stream
+    if (int rc = wait_all()) return rc;
+    // The rays need no frame, so the device tile table (and the viewshed's rank -> mask table that travels with it) may still be
+    // the one from before an unload: whoever needs it first refreshes it, here as in render_frame.  On the ground queries' path
+    // this is a no-op: query_prepare has refused a submission whose tile set changed, and a frame uploaded the table before it.
+    if (int rc = upload_tile_table()) return rc;
+    const size_t trig_doubles = tiles_.size() * ground_table_doubles(tile_w_, tile_h_);
+    if (int rc = ensure(s, d_ground_trig_, (trig_doubles + 2) * sizeof(double))) return rc;
+    launch_ground_tables(d_tiles_.as<const TileDev>(), (uint32_t)tiles_.size(), d_ground_trig_.as<double>(), tile_w_, tile_h_, s);
+    TOPO_HIP_TRY(hipGetLastError());
+    std::vector<double> spheres;
+    for (const auto& kv : tiles_) {      // draw order
+        spheres.insert(spheres.end(), kv.second.centres, kv.second.centres + 4);
+        spheres.push_back(kv.second.block_radius);
+    }
+    if (int rc = ensure(s, d_los_spheres_, (spheres.size() + 2) * sizeof(double))) return rc;
+    if (!spheres.empty()) TOPO_HIP_TRY(hipMemcpyAsync(d_los_spheres_.p, spheres.data(), spheres.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    TOPO_HIP_TRY(hipStreamSynchronize(s));
+    ground_trig_gen_ = tile_gen_;
+    return TOPO_OK;
+}
+
 // The parameters of a ground kernel over c's latest submission, on s: the shared tables, the tile table (the submission's: the tile
 // set has not changed since) and the submission's views, which its first ground query uploads from the host copy the submission kept.
 int TerrainRenderer::ground_params(FrameCtx& c, hipStream_t s, GroundParams& p) {
     if (int rc = query_tables(s)) return rc;
     const size_t trig_doubles = tiles_.size() * ground_table_doubles(tile_w_, tile_h_);
-    if (ground_trig_gen_ != tile_gen_) {
-        // once per tile set: nothing that could still read the old tables is left running, and the new ones are complete before a
-        // query can be queued on any other stream
-        if (int rc = wait_all()) return rc;
-        if (int rc = ensure(s, d_ground_trig_, (trig_doubles + 2) * sizeof(double))) return rc;
-        launch_ground_tables(d_tiles_.as<const TileDev>(), (uint32_t)tiles_.size(), d_ground_trig_.as<double>(), tile_w_, tile_h_, s);
-        TOPO_HIP_TRY(hipGetLastError());
-        TOPO_HIP_TRY(hipStreamSynchronize(s));
-        ground_trig_gen_ = tile_gen_;
-    }
+    if (int rc = ground_tables(s)) return rc;
     if (!c.sub.views_on_device) {
         const size_t bytes = c.sub.views.size() * sizeof(GroundView);
         if (int rc = ensure(s, c.d_ground_views, bytes)) return rc;
@@ -1095,6 +1112,88 @@ int TerrainRenderer::ground_map_device(uint32_t first, uint32_t n, float* out_de
     p.q.first_view = first;
     p.q.n_views = n;
     launch_ground_map(p, out_dev, view_stride, pitch, s);
+    TOPO_HIP_TRY(hipGetLastError());
+    if (s != stream_) c->pending = true;
+    return TOPO_OK;
+}
+
+// ---- rays ---------------------------------------------------------------------------------------------------------------------
+
+static_assert(sizeof(LosRay) == sizeof(topo_ray) && sizeof(topo_ray) == 64, "ray layout");
+static_assert(sizeof(RayHit) == sizeof(topo_ray_hit) && sizeof(topo_ray_hit) == 64, "ray record layout");
+
+// The parameters of k_raycast over the resident tiles, on s: the tile table, the rank -> (lat, lon) table, the f64 tables and the
+// spheres, each rebuilt after the tile set changed.
+int TerrainRenderer::ray_params(hipStream_t s, RayParams& p) {
+    if (int rc = bind_device()) return rc;
+    if (int rc = query_tables(s)) return rc;
+    if (int rc = ground_tables(s)) return rc;      // (refreshes the tile table with them: a tile set changes both or neither)
+    const uint32_t n_tiles = (uint32_t)tiles_.size();
+    p.s.tiles = d_tiles_.as<const TileDev>();
+    p.s.trig = d_ground_trig_.as<const double>();
+    p.s.spheres = d_los_spheres_.as<const double>();
+    p.s.trig_doubles = n_tiles * ground_table_doubles(tile_w_, tile_h_);
+    p.s.n_tiles = n_tiles;
+    p.s.tile_w = tile_w_;
+    p.s.tile_h = tile_h_;
+    p.s.bx_count = n_tiles ? (tile_w_ - 1 + kBCX - 1) / kBCX : 0;
+    p.s.by_count = n_tiles ? (tile_h_ - 1 + kBCY - 1) / kBCY : 0;
+    p.tile_ll = d_hz_ll_.as<const int32_t>();
+    p.check = d_hz_check_.as<uint32_t>();
+    return TOPO_OK;
+}
+
+// Host read: the rays go in and the records come out through one pinned staging buffer; waits for the stream.
+int TerrainRenderer::raycast_read(uint32_t n, const topo_ray* rays, topo_ray_hit* out) {
+    if (n == 0) return TOPO_OK;
+    if (!rays || !out) return fail(TOPO_ERR_INVALID, "null argument");
+    RayParams p{};
+    if (int rc = ray_params(stream_, p)) return rc;
+    const size_t bytes = (size_t)n * sizeof(LosRay);
+    if (int rc = ensure(stream_, d_ray_in_, bytes)) return rc;
+    if (int rc = ensure(stream_, d_ray_out_, bytes)) return rc;
+    if (bytes > h_ray_stage_.cap) TOPO_HIP_TRY(hipStreamSynchronize(stream_));      // (nothing in flight reads the old staging block)
+    if (int rc = ensure_pinned(h_ray_stage_, bytes)) return rc;
+    std::memcpy(h_ray_stage_.p, rays, bytes);
+    TOPO_HIP_TRY(hipMemcpyAsync(d_ray_in_.p, h_ray_stage_.p, bytes, hipMemcpyHostToDevice, stream_));
+    launch_raycast(p, d_ray_in_.as<const LosRay>(), d_ray_out_.as<RayHit>(), n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipMemcpyAsync(h_ray_stage_.p, d_ray_out_.p, bytes, hipMemcpyDeviceToHost, stream_));
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    std::memcpy(out, h_ray_stage_.p, bytes);
+    return query_fold_check();
+}
+
+// Device variant: queued on stream_, in order.
+int TerrainRenderer::raycast_device(uint32_t n, const topo_ray* rays_dev, topo_ray_hit* out_dev) {
+    if (n == 0) return TOPO_OK;
+    if (!rays_dev || !out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)rays_dev % 16 != 0 || (uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "rays_dev and out_dev must be 16-byte aligned");
+    RayParams p{};
+    if (int rc = ray_params(stream_, p)) return rc;
+    launch_raycast(p, (const LosRay*)rays_dev, (RayHit*)out_dev, n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// The sunlit layer of views [first, first + n) of the latest submission: topo_ground_map_device's rules, one byte per pixel.
+int TerrainRenderer::sunlit_map_device(uint32_t first, uint32_t n, const double sun_dir[3], uint8_t* out_dev, size_t view_stride, size_t pitch) {
+    if (!out_dev || !sun_dir) return fail(TOPO_ERR_INVALID, "null argument");
+    const double len = std::sqrt(sun_dir[0] * sun_dir[0] + sun_dir[1] * sun_dir[1] + sun_dir[2] * sun_dir[2]);
+    if (!(len > 0.0) || !std::isfinite(len)) return fail(TOPO_ERR_INVALID, "sun_dir must be finite and non-zero");
+    const double sun[3] = {sun_dir[0] / len, sun_dir[1] / len, sun_dir[2] / len};
+    FrameCtx* c = nullptr;
+    hipStream_t s = nullptr;
+    if (int rc = query_prepare(first, n, &c, &s)) return rc;
+    if (pitch < (size_t)c->sub.query.W) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
+    if (n > 1 && view_stride < pitch * (c->sub.query.H - 1) + (size_t)c->sub.query.W) return fail(TOPO_ERR_INVALID, "view stride smaller than a view");
+    GroundParams p{};
+    if (int rc = ground_params(*c, s, p)) return rc;
+    p.q.first_view = first;
+    p.q.n_views = n;
+    RayParams rp{};
+    if (int rc = ray_params(s, rp)) return rc;      // (the tables are the ground query's: nothing is rebuilt here)
+    launch_sunlit_map(p, rp.s, sun, out_dev, view_stride, pitch, s);
     TOPO_HIP_TRY(hipGetLastError());
     if (s != stream_) c->pending = true;
     return TOPO_OK;

@@ -163,6 +163,12 @@ class TerrainRenderer {
     int ground_device(uint32_t n, const topo_ground_query* queries_dev, topo_ground_point* out_dev);
     int ground_map_device(uint32_t first_view, uint32_t n_views, float* out_dev, size_t view_stride_bytes, size_t pitch_bytes);
 
+    // rays against the resident tiles (topo_raycast_*): no submission needed
+    int raycast_read(uint32_t n, const topo_ray* rays, topo_ray_hit* out);
+    int raycast_device(uint32_t n, const topo_ray* rays_dev, topo_ray_hit* out_dev);
+    // ... and the sunlit layer of the latest submission's views, beside the ground map (topo_sunlit_map_device)
+    int sunlit_map_device(uint32_t first_view, uint32_t n_views, const double sun_dir[3], uint8_t* out_dev, size_t view_stride_bytes, size_t pitch_bytes);
+
     // unwrap: finished views that share an eye as one azimuth / elevation image (topo_unwrap_device)
     int unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h, const OutputParams& src,
                       const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch);
@@ -340,6 +346,12 @@ class TerrainRenderer {
     int query_fold_check();
     int horizon_launch(FrameCtx& c, uint32_t first_view, uint32_t n_views, HorizonPoint* out, size_t view_stride, hipStream_t s);
     int ground_params(FrameCtx& c, hipStream_t s, GroundParams& p);
+    int ground_tables(hipStream_t s);           // the tiles' f64 tables (and spheres) of the current tile set, rebuilt after it changed
+    // rays: the device copy of the tiles' spheres (kLosSphereDoubles each, draw order; made with d_ground_trig_), the host read's
+    // pinned staging (rays in, records out) and its device buffers
+    DeviceBuffer d_los_spheres_, d_ray_in_, d_ray_out_;
+    PinnedBuffer h_ray_stage_;
+    int ray_params(hipStream_t s, RayParams& p);
 
     // unwrap: the device copy of k_unwrap's f64 tables (topo_unwrap.h), kept for the parameter set they were built from -- the call's
     // parameters, the views' direction blocks and the eye (unwrap_key_) -- and their host copy, the source of the upload

@@ -395,6 +395,27 @@ int topo_ground_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views,
     TOPO_CALL(ctx->r->ground_map_device(first_view, n_views, out_dev, view_stride_bytes, pitch_bytes));
 }
 
+int topo_raycast_read(topo_ctx* ctx, uint32_t n, const topo_ray* rays, topo_ray_hit* out) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->raycast_read(n, rays, out));
+}
+
+int topo_raycast_device(topo_ctx* ctx, uint32_t n, const topo_ray* rays_dev, topo_ray_hit* out_dev) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->raycast_device(n, rays_dev, out_dev));
+}
+
+int topo_sunlit_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views, const double sun_dir[3], uint8_t* out_dev, size_t view_stride_bytes,
+                           size_t pitch_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->sunlit_map_device(first_view, n_views, sun_dir, out_dev, view_stride_bytes, pitch_bytes));
+}
+
+void topo_sun_direction(double lon_deg, double lat_deg, double az_deg, double el_deg, double dir_out[3]) {
+    if (!dir_out) return;
+    topo::sun_direction(lon_deg, lat_deg, az_deg, el_deg, dir_out);
+}
+
 int topo_unwrap_device(topo_ctx* ctx, const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h,
                        const uint8_t* rgba_src_dev, size_t rgba_view_stride, size_t rgba_pitch, const float* depth_src_dev, size_t depth_view_stride,
                        size_t depth_pitch, uint8_t* rgba_out_dev, size_t rgba_out_pitch, float* depth_out_dev, size_t depth_out_pitch, int32_t* src_out_dev,

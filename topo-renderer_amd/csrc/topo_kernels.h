@@ -7,6 +7,7 @@
 #include "topo_pipeline.h"
 #include "topo_ground.h"
 #include "topo_unwrap.h"
+#include "topo_los.h"
 
 namespace topo {
 
@@ -208,6 +209,27 @@ void launch_ground_tables(const TileDev* tiles, uint32_t n_tiles, double* trig, 
 void launch_ground(const GroundParams& p, const GroundQuery* queries, GroundPoint* out, uint32_t n, hipStream_t s);
 // float4 (lon, lat, height, range) per pixel of views [p.q.first_view, + p.q.n_views): view i at out + i * view_stride, rows pitch apart (bytes)
 void launch_ground_map(const GroundParams& p, float* out, size_t view_stride, size_t pitch, hipStream_t s);
+
+// rays (topo_raycast_*): n rays against the resident tiles (topo_los.h); needs no submission.  Reads the tile table, the DEMs and the
+// block tables, the tiles' f64 tables and spheres; writes only `out`.
+static_assert(kLosBCX == kBCX && kLosBCY == kBCY, "topo_los.h walks the raster blocks");
+struct RayHit {            // = topo_ray_hit (64 bytes)
+    double t, lon_deg, lat_deg;
+    float height_m;
+    int32_t kind;
+    int32_t tile_lat, tile_lon;
+    uint32_t cell_x, cell_y, tri, front;
+    float w1, w2;
+};
+struct RayParams {
+    LosScene s;
+    const int32_t* tile_ll;       // rank -> (lat, lon), n_tiles pairs
+    uint32_t* check;              // TOPO_BOUNDS_CHECK build: the queries' status record; else unused
+};
+void launch_raycast(const RayParams& p, const LosRay* rays, RayHit* out, uint32_t n, hipStream_t s);      // (a wave per ray; -DTOPO_RAYCAST_LANE: a lane per ray)
+// one byte (kSun*: topo_los.h) per pixel of views [g.q.first_view, + g.q.n_views) of a finished submission under a sun in direction
+// `sun` (unit): view i at out + i * view_stride, rows pitch apart (bytes)
+void launch_sunlit_map(const GroundParams& g, const LosScene& scene, const double sun[3], uint8_t* out, size_t view_stride, size_t pitch, hipStream_t s);
 
 // unwrap (topo_unwrap_*): n_views views of src_w x src_h that share an eye, resampled into one out_w x out_h azimuth / elevation
 // image (topo_unwrap.h).  Reads the tables and the source images; writes only the outputs given (each nullable; rgba_out needs
