@@ -162,6 +162,205 @@ CASES = {"ridges_ne": lambda: _ridges_case("ridges_ne"), "ridges_sw": lambda: _r
          "void_nan": _void_case, "void_pinf": _void_inf_case}
 
 
+# ---- off the 45N 15E quadrant: across the equator, the prime meridian, the antimeridian and the pole -----------------------------------
+def geo_relief(lat, lon):
+    from test_ray_check_cpu import relief
+    return relief(lat, lon)
+
+
+def placed_tiles(locs, n, height_fn=geo_relief):
+    """(tiles in draw order, their (lat, lon)) of square n-vertex tiles at explicit locations (Scene cannot name tile -180)."""
+    x = np.arange(n, dtype=np.float64) / n
+    order = LR.geo_order(locs)
+    return [(np.ascontiguousarray(height_fn((la + 1 - x)[:, None], (lo + x)[None, :]), dtype=np.float32),) + tuple(T.synth.tile_transform(la, lo, n, n))
+            for la, lo in order], order
+
+
+def _geo_rays(lat0, lat1, lon0, lon1, seed, meridians=None, k=14):
+    """The standard set over the box [lat0, lat1] x [lon0, lon1] (longitudes may run past 180: ecef takes them as they come): low rays
+    both ways along parallels and along meridians between the relief's lowest (100 m) and highest (2900 m) point, slanted rays from
+    above, zenith rays (misses) and rays whose t_max ends above the ground (misses)."""
+    rng = np.random.default_rng(seed)
+    R = []
+    lats = lat0 + (lat1 - lat0) * (np.arange(k) + 0.5) / k
+    lons = lon0 + (lon1 - lon0) * (np.arange(k) + 0.5) / k if meridians is None else np.asarray(meridians, np.float64)
+    dlat = 0.05 if lat1 + 0.05 < 90.0 and lat0 - 0.05 > -90.0 else 0.0
+    for hgt in (600.0, 1500.0, 2400.0):
+        a, b = ecef(lon0 - 0.1, lats, hgt), ecef(lon1 + 0.1, lats + 0.007, hgt)
+        R += [make_rays(a, b - a, 0.0, 1.0), make_rays(b, a - b, 0.0, 1.0)]
+        a, b = ecef(lons, lat1 + dlat, hgt), ecef(lons + 0.013, lat0 - dlat, hgt)
+        R += [make_rays(a, b - a, 0.0, 1.0), make_rays(b, a - b, 0.0, 1.0)]
+    return np.concatenate(R + _overhead_rays(lat0, lat1, lon0, lon1, rng))
+
+
+def _overhead_rays(lat0, lat1, lon0, lon1, rng):
+    glon, glat = np.meshgrid(lon0 + (lon1 - lon0) * (np.arange(9) + 0.37) / 9.5, lat0 + (lat1 - lat0) * (np.arange(8) + 0.41) / 8.5)
+    glon, glat = glon.reshape(-1), glat.reshape(-1)
+    n = len(glon)
+    top = ecef(glon, glat, 9000.0)
+    aim = ecef(glon + rng.uniform(-0.2, 0.2, n), np.clip(glat + rng.uniform(-0.2, 0.2, n), -89.99, 89.99), 0.0)
+    return [make_rays(top, aim - top, 0.0, 4.0),                               # slanted from above, non-unit
+            make_rays(top[::2], up_at(glon[::2], glat[::2]), 0.0, 1.0e6),      # zenith: miss
+            make_rays(top[1::2], aim[1::2] - top[1::2], 0.0, 0.4)]             # ends 5000 m up: miss
+
+
+def _antimeridian_case(lat):
+    """Two 48-vertex tiles either side of the antimeridian: parallels from 178.9E to 178.9W and back, meridians from 179.5E to 179.5W
+    (none on the meridian itself: a hit there may report +180 or -180)."""
+    tiles, order = placed_tiles([(lat, 179), (lat, -180)], 48)
+    meridians = np.concatenate([179.53 + 0.1 * np.arange(5), 180.03 + 0.1 * np.arange(5)])
+    rays = _geo_rays(float(lat), lat + 1.0, 179.0, 181.0, 21 + abs(lat), meridians)
+    return tiles, order, rays, LR.cast(LR.Mesh(tiles), rays)
+
+
+def _origin_case():
+    tiles, order = placed_tiles([(0, 0), (-1, 0), (0, -1), (-1, -1)], 32)
+    rays = _geo_rays(-1.0, 1.0, -1.0, 1.0, 23)
+    return tiles, order, rays, LR.cast(LR.Mesh(tiles), rays)
+
+
+def _high_latitude_case(lat, lon):
+    tiles, order = placed_tiles([(lat, lon), (lat, lon + 1)], 48)
+    rays = _geo_rays(float(lat), lat + 1.0, float(lon), lon + 2.0, 25 + abs(lat))
+    return tiles, order, rays, LR.cast(LR.Mesh(tiles), rays)
+
+
+def _polar_case():
+    """Four 32-vertex tiles whose row 0 is the north pole, two on either side of it: rays from 88.9N over the pole to 88.9N on the
+    opposite longitude and back (2.5 to 4 km up at their ends: the chord dips 1.2 km towards the pole), rays along parallels between
+    89N and 89.98N, rays past the pole whose latitude peaks over the tiles (the t_e term of los_cell_range), and the slanted, zenith and short rays of the standard set over either pair."""
+    tiles, order = placed_tiles([(89, 20), (89, 21), (89, -160), (89, -159)], 32)
+    k = 16
+    lons = 20.0 + 2.0 * (np.arange(k) + 0.5) / k
+    R = []
+    for hgt in (2500.0, 3000.0, 3500.0, 4000.0):
+        a, b = ecef(lons, 88.9, hgt), ecef(lons - 180.0 + 0.013, 88.9, hgt)
+        R += [make_rays(a, b - a, 0.0, 1.0), make_rays(b, a - b, 0.0, 1.0)]
+    lats = 89.0 + 0.98 * (np.arange(k) + 0.5) / k
+    for west in (20.0, -160.0):
+        for hgt in (900.0, 1500.0, 2100.0):
+            a, b = ecef(west - 0.1, lats, hgt), ecef(west + 2.1, lats + 0.003, hgt)
+            R += [make_rays(a, b - a, 0.0, 1.0), make_rays(b, a - b, 0.0, 1.0)]
+    # past the pole, 9 to 100 km from it, square to the meridian of the closest point C: the latitude peaks inside every interval
+    colat = np.repeat(0.08 + 0.82 * (np.arange(8) + 0.5) / 8, 4)
+    lonc = np.tile([20.5, 21.5, -159.5, -158.5], 8)
+    east = np.stack([-np.sin(np.radians(lonc)), np.cos(np.radians(lonc)), 0.0 * lonc], axis=-1)
+    for hgt in (1100.0, 1700.0):
+        c, up = ecef(lonc, 90.0 - colat, hgt), up_at(lonc, 90.0 - colat)
+        a, b = c - 60000.0 * east + 900.0 * up, c + 60000.0 * east - 700.0 * up
+        R += [make_rays(a, b - a, 0.0, 1.0), make_rays(b, a - b, 0.0, 1.0)]
+    for west, seed in ((20.0, 31), (-160.0, 32)):
+        R += _overhead_rays(89.0, 89.98, west, west + 2.0, np.random.default_rng(seed))
+    rays = np.concatenate(R)
+    return tiles, order, rays, LR.cast(LR.Mesh(tiles), rays)
+
+
+# ---- tiles of more than 64 raster blocks: the wave-per-ray kernel takes the blocks of a tile 64 at a time ----------------------------------
+BATCH = 64      # blocks per batch of k_raycast
+BLOCK_CX, BLOCK_CY = 60, 15      # cells of a raster block
+BATCH_TILES = {"tall": (61, 964), "grid": (301, 250)}      # (w, h) vertices: 1 x 65 blocks (the 65th of 3 cell rows); 5 x 17 blocks (the last row partial)
+_BLOCKS_BASE = 1320      # the rays of _blocks_case before its short / beyond copies
+
+
+def blocks_heights(lat, lon, w, h):
+    """The relief of _blocks_case sampled at w x h vertices of the tile (lat, lon)."""
+    la, lo = (lat + 1 - np.arange(h) / h)[:, None], (lon + np.arange(w) / w)[None, :]
+    return (1500.0 + 1200.0 * np.sin(np.radians(2300.0 * lo)) * np.cos(np.radians(1700.0 * la)) + 400.0 * np.sin(np.radians(7000.0 * (lo + la)))).astype(np.float32)
+
+
+def block_of(cell_x, cell_y, w):
+    """The raster block of a cell, numbered as k_raycast numbers them."""
+    return (np.asarray(cell_y, np.int64) // BLOCK_CY) * (-(-(w - 1) // BLOCK_CX)) + np.asarray(cell_x, np.int64) // BLOCK_CX
+
+
+def _surface(hts, lat, lon, la, lo):
+    """The height of the nearest vertex of the tile at (la, lo)."""
+    h, w = hts.shape
+    j = np.clip(np.rint((lat + 1 - np.asarray(la)) * h), 0, h - 1).astype(int)
+    i = np.clip(np.rint((np.asarray(lo) - lon) * w), 0, w - 1).astype(int)
+    return hts[j, i].astype(np.float64)
+
+
+def aimed_rays(hts, lat, lon, k, seed):
+    """Rays into the last block row of the tile: slanted from above, and along the meridian from the south (from 0.01 degrees outside
+    the tile, descending 300 to 900 m to a point 40 m under the surface of the row, and on across the whole tile) and from the north
+    (from 0.15 degrees inside the tile, descending 1500 m).  -> (rays, the indices of the meridional ones)."""
+    rng = np.random.default_rng(seed)
+    h, w = hts.shape
+    rows = ((h - 2) // BLOCK_CY) * BLOCK_CY                                  # the first cell row of the last block row
+    la = lat + 1 - rng.uniform(rows + 0.3, h - 1.3, 3 * k) / h
+    lo = lon + rng.uniform(0.02, (w - 1.5) / w, 3 * k)
+    tgt = ecef(lo, la, _surface(hts, lat, lon, la, lo) - 40.0)
+    top = ecef(lo[:k] + rng.uniform(-0.05, 0.05, k), la[:k] + rng.uniform(0.0, 0.05, k), 9000.0)
+    south = ecef(lo[k:2 * k] - 0.001, lat - 0.01, _surface(hts, lat, lon, la[k:2 * k], lo[k:2 * k]) + rng.uniform(300.0, 900.0, k))
+    north = ecef(lo[2 * k:] - 0.004, la[2 * k:] + 0.15, _surface(hts, lat, lon, la[2 * k:], lo[2 * k:]) + 1500.0)
+    span = 1.1 / (la[k:2 * k] - (lat - 0.01))                                # t at which the ray from the south leaves the tile in the north
+    rays = np.concatenate([make_rays(top, tgt[:k] - top, 0.0, 2.0), make_rays(south, tgt[k:2 * k] - south, 0.0, span),
+                           make_rays(north, tgt[2 * k:] - north, 0.0, 3.0)])
+    return rays, np.arange(k, 3 * k)
+
+
+def batch_rays(hts, lat, lon, stride, k, seed):
+    """The rays of _blocks_case (the same degree), every stride-th and its 30 meridional rays at 2600 m, the full-length meridional
+    ones among them; then the aimed rays.  -> (rays, the indices of the meridional ones)."""
+    base = case("blocks")[2]
+    assert len(base) > _BLOCKS_BASE
+    idx = np.union1d(np.arange(0, _BLOCKS_BASE, stride), np.arange(660, 690))
+    first = 480                                                                 # per height: 30 meridional, 30 + 30 along the parallel
+    merid = np.nonzero((idx >= first) & (idx < first + 360) & ((idx - first) % 90 < 30))[0]
+    aimed, am = aimed_rays(hts, lat, lon, k, seed)
+    return np.concatenate([base[idx], aimed]), np.concatenate([merid, len(idx) + am])
+
+
+_MERIDIONAL = {}
+
+
+def batch_scene(name):
+    """(tiles, order, rays, the indices of the meridional rays) of a batch case, before any reference is computed."""
+    lat, lon = 46, 7
+    w, h = BATCH_TILES[name]
+    hts = blocks_heights(lat, lon, w, h)
+    tiles, order = [(hts,) + tuple(T.synth.tile_transform(lat, lon, w, h))], [(lat, lon)]
+    rays, merid = batch_rays(hts, lat, lon, *{"tall": (15, 35, 41), "grid": (15, 30, 42)}[name])
+    return tiles, order, rays, merid
+
+
+def _batch_case(name):
+    tiles, order, rays, merid = batch_scene(name)
+    mesh = LR.Mesh(tiles)
+    first = LR.cast(mesh, rays)
+    hit = np.nonzero(first["kind"] == LR.HIT)[0][::10]                       # _blocks_case's short and beyond copies
+    short, beyond = rays[hit].copy(), rays[hit].copy()
+    short["t_max"] = first["t"][hit] * 0.999
+    beyond["t_min"] = first["t"][hit] * 1.001
+    extra = np.concatenate([short, beyond])
+    _MERIDIONAL[name] = merid
+    return tiles, order, np.concatenate([rays, extra]), np.concatenate([first, LR.cast(mesh, extra)])
+
+
+def meridional(name):
+    """The indices of the meridional rays of a batch case."""
+    case(name)
+    return _MERIDIONAL[name]
+
+
+def blocks_under(rays, lat, lon, w, h, samples=4000):
+    """Per ray, whether its ground track over [t_min, t_max] passes over a block of index < 64, and over one of index >= 64."""
+    t = rays["t_min"][:, None] + (rays["t_max"] - rays["t_min"])[:, None] * (np.arange(samples) + 0.5)[None, :] / samples
+    p = rays["origin"][:, None, :] + t[..., None] * rays["dir"][:, None, :]
+    la = np.degrees(np.arcsin(p[..., 2] / np.linalg.norm(p, axis=-1)))
+    lo = np.degrees(np.arctan2(p[..., 1], p[..., 0]))
+    cx, cy = np.floor((lo - lon) * w), np.floor((lat + 1 - la) * h)
+    inside = (cx >= 0) & (cx < w - 1) & (cy >= 0) & (cy < h - 1)
+    blk = block_of(np.clip(cx, 0, w - 2), np.clip(cy, 0, h - 2), w)
+    return (inside & (blk < BATCH)).any(axis=1), (inside & (blk >= BATCH)).any(axis=1)
+
+
+CASES.update({"antimeridian": lambda: _antimeridian_case(10), "antimeridian_south": lambda: _antimeridian_case(-11), "origin": _origin_case,
+              "north84": lambda: _high_latitude_case(84, 20), "south85": lambda: _high_latitude_case(-85, -40), "polar": _polar_case,
+              "tall": lambda: _batch_case("tall"), "grid": lambda: _batch_case("grid")})
+
+
 def case(name):
     """(tiles, order, rays, reference records), computed once."""
     if name not in _CACHE:

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import geo_scenes as GS
 import ground_ref as GR
 from oracle import ray_check as RC
 from scenes import Scene
@@ -24,6 +25,9 @@ CASES = {name: (dict(tile=c[0], n_lat=c[1], n_lon=c[2], lat0=c[3], lon0=c[4], ey
          for name, c in zip(("ne_2x2", "down_1x1", "sw_3x3"), SCENES)}
 CASES["giants"] = (dict(tile=96, n_lat=2, n_lon=2, eye_dh=100.0), 200, 150, 120.0, 60.0, 90.0)      # near-clipped giants
 CASES["low_eye"] = (dict(tile=96, n_lat=2, n_lon=2, eye_dh=50.0), 256, 128, 40.0, 10.0, 70.0)
+for _name in GS.NAMES:      # off the 45N 15E quadrant: the scene of the pose's eye itself, one pose each and both eyes at the antimeridian
+    for _k, (_eye, _yaw, _pitch, _fov) in enumerate(GS.placement(_name).poses[:2 if _name == "antimeridian" else 1]):
+        CASES[_name + ("_west" if _k else "")] = (_eye, GS.W, GS.H, _yaw, _pitch, _fov)
 _DONE = {}
 
 
@@ -31,7 +35,7 @@ def case(orc, name):
     """(scene, uniforms, oracle depth, oracle winners, reference) of a case, computed once."""
     if name not in _DONE:
         kw, W, H, yaw, pitch, fov = CASES[name]
-        sc = Scene(**kw)
+        sc = kw if isinstance(kw, Scene) else Scene(**kw)
         o = orc.OracleRenderer(W, H)
         sc.load(o)
         u = sc.uniforms(W, H, yaw, pitch, fov, 1)

@@ -40,6 +40,46 @@ def test_blocks_case_covers_its_kinds():
     assert (np.abs(d - 1.0) > 0.1).sum() >= 100, "non-unit directions"
 
 
+@pytest.mark.parametrize("name", sorted(LC.BATCH_TILES))
+def test_batch_cases_cross_the_batch_boundary(name):
+    """k_raycast takes the raster blocks of a tile 64 at a time.  The reference's hits of the tall and grid cases lie on both sides of
+    block 64, and meridional rays cross from one batch into the other before and after their first hit: a t_max that shrank in one
+    batch is applied in the next."""
+    tiles, order, rays, ref = LC.case(name)
+    w, h = LC.BATCH_TILES[name]
+    assert tiles[0][0].shape == (h, w)
+    hit = ref["kind"] == LR.HIT
+    cell = ref["tri"] >> 1
+    blk = LC.block_of(cell // (h - 1), cell % (h - 1), w)
+    n_blocks = -(-(w - 1) // LC.BLOCK_CX) * -(-(h - 1) // LC.BLOCK_CY)
+    assert LC.BATCH < n_blocks <= 2 * LC.BATCH and blk[hit].max() < n_blocks
+    high, low = int((hit & (blk >= LC.BATCH)).sum()), int((hit & (blk < LC.BATCH)).sum())
+    m = LC.meridional(name)
+    over_first, over_second = LC.blocks_under(rays[m], order[0][0], order[0][1], w, h)
+    second_then_first = int((hit[m] & (blk[m] >= LC.BATCH) & over_first).sum())
+    first_then_second = int((hit[m] & (blk[m] < LC.BATCH) & over_second).sum())
+    print(f"{name}: {high} hits in blocks >= 64, {low} below; of {len(m)} meridional rays {second_then_first} hit first in the second batch and "
+          f"cross the first, {first_then_second} the reverse; {int((hit & (blk == n_blocks - 1)).sum())} hits in the last block")
+    assert high >= 20 and low >= 20
+    assert second_then_first >= 10 and first_then_second >= 10
+    assert ((rays["t_min"] > 0) & hit).sum() >= 5 and (np.abs(np.linalg.norm(rays["dir"], axis=1) - 1.0) > 0.1).sum() >= 100
+
+
+def test_geographic_cases_hit_every_tile():
+    """The cases across the equator and the prime meridian, the antimeridian and the pole have hits in each of their tiles, at
+    least 15 % hits and 15 % misses, and the rays over the pole hit on either side of it."""
+    for name in ("antimeridian", "antimeridian_south", "origin", "north84", "south85", "polar"):
+        tiles, order, rays, ref = LC.case(name)
+        hit = ref["kind"] == LR.HIT
+        assert hit.mean() >= 0.15 and (ref["kind"] == LR.MISS).mean() >= 0.15, (name, float(hit.mean()))
+        assert {int(r) for r in ref["rank"][hit]} == set(range(len(order))), name
+    tiles, order, rays, ref = LC.case("polar")
+    over = ref[:128]      # the rays over the pole come first
+    east = np.array([order[r][1] > 0 for r in over["rank"]]) & (over["kind"] == LR.HIT)
+    west = np.array([order[r][1] < 0 for r in over["rank"]]) & (over["kind"] == LR.HIT)
+    assert east.sum() >= 20 and west.sum() >= 20, (int(east.sum()), int(west.sum()))
+
+
 def test_long_case_passes_through_the_gaps():
     tiles, order, rays, ref = LC.case("long")
     assert (ref["kind"][-20:] == LR.MISS).all(), "a ray straight down a gap between two tiles passes"

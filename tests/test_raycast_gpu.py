@@ -326,13 +326,19 @@ def test_sunlit_errors(topo):
 
 
 def _checked_run(T):
-    """The blocks and ridges cases (and a void case), then a sunlit map of an odd-sized frame -> hash of every output, status."""
+    """The blocks and ridges cases (and a void case), the tall and polar cases, then a sunlit map of an odd-sized frame -> hash of
+    every output, status."""
     h = hashlib.sha256()
     status = 0
     for name in ("blocks", "ridges_sw", "void_pinf"):
         tiles, order, rays, _ = LC.case(name)
         g = _renderer(T, tiles, order)
         h.update(g.raycast(LC.with_invalid(rays)[0]).tobytes())
+        status |= g.frame_status()["status"]
+        g.close()
+    for tiles, order, rays in (LC.batch_scene("tall")[:3], LC.case("polar")[:3]):      # the second batch of 64 blocks; tiles whose row 0 is the pole
+        g = _renderer(T, tiles, order)
+        h.update(g.raycast(rays).tobytes())
         status |= g.frame_status()["status"]
         g.close()
     import torch
