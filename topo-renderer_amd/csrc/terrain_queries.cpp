@@ -1,0 +1,463 @@
+// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, unwrap), the tile-set
+// tables they read and their handle on the latest submission.  The frame path is terrain_renderer.cpp (see terrain_renderer.hpp).
+#include "terrain_renderer.hpp"
+
+#include <cmath>
+#include <cstring>
+
+namespace topo {
+
+static_assert(sizeof(HorizonPoint) == sizeof(topo_horizon_point) && sizeof(topo_horizon_point) == 32, "horizon record layout");
+static_assert(sizeof(GroundPoint) == sizeof(topo_ground_point) && sizeof(topo_ground_point) == 64, "ground record layout");
+static_assert(sizeof(GroundQuery) == sizeof(topo_ground_query) && sizeof(topo_ground_query) == 16, "ground query layout");
+static_assert(sizeof(LosRay) == sizeof(topo_ray) && sizeof(topo_ray) == 64, "ray layout");
+static_assert(sizeof(RayHit) == sizeof(topo_ray_hit) && sizeof(topo_ray_hit) == 64, "ray record layout");
+static_assert(kTileSphereDoubles == kLosSphereDoubles, "the cull prefilter and the rays read the same spheres: one gather, one layout");
+
+// ---- viewshed ----------------------------------------------------------------------------------------------------------------
+
+int TerrainRenderer::alloc_mask(Tile& t) {
+    DeviceBuffer m;      // (the tile gets it once it is zeroed)
+    if (int rc = ensure(stream_, m, mask_bytes())) return rc;
+    TOPO_HIP_TRY(hipMemsetAsync(m.p, 0, mask_bytes(), stream_));      // (frames on other streams are ordered after stream_)
+    t.mask = std::move(m);
+    return TOPO_OK;
+}
+
+// The masks are allocated when accumulation is first turned on (for the tiles loaded then; later tiles get theirs in add_terrain) and
+// kept until the tile goes; turning accumulation off only stops the launches.
+int TerrainRenderer::viewshed_enable(bool on) {
+    if (int rc = bind_device()) return rc;
+    if (on && !vs_ever_) {
+        if (int rc = join()) return rc;
+        const size_t stats = (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long);
+        if (!d_vs_stats_.p) {
+            if (int rc = ensure(stream_, d_vs_stats_, stats)) return rc;
+            TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_.p, 0, stats, stream_));
+        }
+        for (auto& kv : tiles_)
+            if (!kv.second.mask.p)
+                if (int rc = alloc_mask(kv.second)) return rc;
+        vs_ever_ = true;
+        table_dirty_ = true;      // the next submission uploads the rank -> mask table with the tile table
+    }
+    vs_on_ = on;
+    return TOPO_OK;
+}
+
+int TerrainRenderer::viewshed_reset() {
+    if (int rc = bind_device()) return rc;
+    if (!vs_ever_) return TOPO_OK;
+    if (int rc = join()) return rc;      // frames in flight on the contexts' own streams; later ones are ordered after stream_
+    for (auto& kv : tiles_) TOPO_HIP_TRY(hipMemsetAsync(kv.second.mask.p, 0, mask_bytes(), stream_));
+    TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_.p, 0, (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long), stream_));
+    return TOPO_OK;
+}
+
+int TerrainRenderer::viewshed_read(int32_t lat, int32_t lon, uint8_t* mask_out, size_t pitch, uint64_t* n_visible) {
+    if (!mask_out) return fail(TOPO_ERR_INVALID, "mask_out is null");
+    Tile* t = find(lat, lon);
+    if (!t) return fail(TOPO_ERR_NOT_FOUND, "no such tile");
+    if (!vs_ever_) return fail(TOPO_ERR_INVALID, "viewshed accumulation was never enabled");
+    const uint32_t wm1 = tile_w_ - 1, hm1 = tile_h_ - 1;
+    if (pitch < wm1) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
+    if (int rc = wait_all()) return rc;
+    std::vector<uint32_t> words(mask_bytes() / 4);
+    TOPO_HIP_TRY(hipMemcpy(words.data(), t->mask.p, mask_bytes(), hipMemcpyDeviceToHost));
+    uint64_t count = 0;
+    for (uint32_t x = 0, bit = 0; x < wm1; ++x)      // bit = x (h-1) + y: the cell of the draw id's triangle (triangle_vertices)
+        for (uint32_t y = 0; y < hm1; ++y, ++bit) {
+            const uint8_t v = (uint8_t)((words[bit >> 5] >> (bit & 31u)) & 1u);
+            mask_out[(size_t)y * pitch + x] = v;
+            count += v;
+        }
+    if (n_visible) *n_visible = count;
+    return TOPO_OK;
+}
+
+int TerrainRenderer::viewshed_stats(uint64_t out[3]) {
+    if (!out) return fail(TOPO_ERR_INVALID, "null argument");
+    out[0] = out[1] = out[2] = 0;
+    if (!vs_ever_) return TOPO_OK;
+    if (int rc = wait_all()) return rc;
+    std::vector<unsigned long long> s((size_t)kViewshedStatSlots * 4);
+    TOPO_HIP_TRY(hipMemcpy(s.data(), d_vs_stats_.p, s.size() * sizeof(s[0]), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < s.size(); i += 4)
+        for (int k = 0; k < 3; ++k) out[k] += s[i + k];
+    return TOPO_OK;
+}
+
+// ---- what the queries share: the tile-set tables, the bounds record, the latest submission -------------------------------------
+
+// The tiles' spheres, gathered once per tile set.  Host memory only -- no HIP call, no wait: the cull prefilter asks on every submission.
+const std::vector<double>& TerrainRenderer::tile_spheres() {
+    if (tables_.spheres_gen == tile_gen_) return tables_.spheres;
+    tables_.spheres.clear();
+    for (const auto& kv : tiles_) {      // draw order
+        tables_.spheres.insert(tables_.spheres.end(), kv.second.centres, kv.second.centres + 4);
+        tables_.spheres.push_back(kv.second.block_radius);
+    }
+    tables_.spheres_gen = tile_gen_;
+    return tables_.spheres;
+}
+
+// The tables a query kernel on s reads besides the submission's own, up to `level`; every query calls this once.  A level is rebuilt
+// after the tile set changed, once every earlier query has finished (add_terrain / unload_terrain join the frames, a query on a context's
+// own stream marks it pending); with current tables nothing waits.  rank -> (lat, lon) is the current tile order: query_begin checked it.
+int TerrainRenderer::prepare_tables(TableLevel level, hipStream_t s) {
+    if (tables_.decode_gen != tile_gen_) {
+        if (int rc = wait_all()) return rc;
+        tables_.ll.clear();
+        for (const auto& kv : tiles_) tables_.ll.insert(tables_.ll.end(), {kv.second.lat, kv.second.lon});      // draw order
+        if (int rc = ensure(stream_, tables_.d_ll, (tables_.ll.size() + 2) * sizeof(int32_t))) return rc;
+        if (!tables_.ll.empty()) TOPO_HIP_TRY(hipMemcpyAsync(tables_.d_ll.p, tables_.ll.data(), tables_.ll.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        tables_.decode_gen = tile_gen_;
+    }
+    if (int rc = ensure_query_check(s)) return rc;
+    if (level == kDecodeTables || tables_.geometry_gen == tile_gen_) return TOPO_OK;
+    // The tiles' f64 (cos, sin) tables and, for the rays, their spheres.  Nothing that could still read the old tables is left
+    // running, and the new ones are complete before a query can be queued on any other stream.
+    if (int rc = wait_all()) return rc;
+    // The rays need no frame, so the device tile table (and the viewshed's rank -> mask table that travels with it) may still be
+    // the one from before an unload: whoever needs it first refreshes it, here as in render_frame.  On the ground queries' path
+    // this is a no-op: query_begin has refused a submission whose tile set changed, and a frame uploaded the table before it.
+    if (int rc = upload_tile_table()) return rc;
+    tables_.trig_doubles = tiles_.size() * ground_table_doubles(tile_w_, tile_h_);
+    if (int rc = ensure(s, tables_.d_trig, (tables_.trig_doubles + 2) * sizeof(double))) return rc;
+    launch_ground_tables(d_tiles_.as<const TileDev>(), (uint32_t)tiles_.size(), tables_.d_trig.as<double>(), tile_w_, tile_h_, s);
+    TOPO_HIP_TRY(hipGetLastError());
+    const std::vector<double>& spheres = tile_spheres();
+    if (int rc = ensure(s, tables_.d_spheres, (spheres.size() + 2) * sizeof(double))) return rc;
+    if (!spheres.empty()) TOPO_HIP_TRY(hipMemcpyAsync(tables_.d_spheres.p, spheres.data(), spheres.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    TOPO_HIP_TRY(hipStreamSynchronize(s));
+    tables_.geometry_gen = tile_gen_;
+    return TOPO_OK;
+}
+
+int TerrainRenderer::ensure_query_check([[maybe_unused]] hipStream_t s) {
+#ifdef TOPO_BOUNDS_CHECK
+    if (!query_.d_check.p) {
+        if (int rc = ensure(s, query_.d_check, kStatusWords * sizeof(uint32_t))) return rc;
+        TOPO_HIP_TRY(hipMemsetAsync(query_.d_check.p, 0, kStatusWords * sizeof(uint32_t), s));
+    }
+#endif
+    return TOPO_OK;
+}
+
+// The bounds-checking build: what the query kernels recorded, into the status topo_frame_status reports (the queries have finished).
+int TerrainRenderer::query_fold_check() {
+#ifdef TOPO_BOUNDS_CHECK
+    if (!query_.d_check.p) return TOPO_OK;
+    uint32_t w[kStatusWords];
+    TOPO_HIP_TRY(hipMemcpy(w, query_.d_check.p, sizeof w, hipMemcpyDeviceToHost));
+    if (w[kCtrStatus] & kStatusBounds) {
+        record_bounds(w);
+        TOPO_HIP_TRY(hipMemset(query_.d_check.p, 0, sizeof w));
+    }
+#endif
+    return TOPO_OK;
+}
+
+// The latest submission, if views [first, first + n) of it can be answered (tiles added, replaced or unloaded since have taken its draw
+// order with them), and the stream a query is queued on, behind it (last_stream null: a wait covered it, the stream may be gone).
+int TerrainRenderer::query_begin(uint32_t first, uint32_t n, LatestSubmission& q) {
+    if (latest_ctx_ < 0) return fail(TOPO_ERR_INVALID, "no submission to query");
+    FrameCtx& c = ctx_[latest_ctx_];
+    if (c.sub.tile_gen != tile_gen_) return fail(TOPO_ERR_INVALID, "tiles were added or unloaded since the latest submission: its draw order is gone");
+    if (n == 0 || first >= c.sub.n_views || n > c.sub.n_views - first) return fail(TOPO_ERR_INVALID, "views outside the latest submission");
+    if (int rc = bind_device()) return rc;
+    q = LatestSubmission{&c, c.last_stream ? c.last_stream : stream_, c.sub.query.W, c.sub.query.H, c.sub.n_views};
+    return TOPO_OK;
+}
+
+// The end of a device variant: the query has just been launched on q.s.  On a context's own stream the next join (and whatever
+// rewrites the frame: the context's next submission) waits for the query too -- it is still reading the submission's keys.
+int TerrainRenderer::query_queued(const LatestSubmission& q) {
+    TOPO_HIP_TRY(hipGetLastError());
+    if (q.s != stream_) q.c->pending = true;
+    return TOPO_OK;
+}
+
+// The end of a host read: waits for the submission and the query queued behind it on q.s.  The submission's status is folded as
+// topo_render folds its own frame: the frames of its context in front of it go to the next topo_join (their overflow stays pending
+// there), and its own overflow is this call's error -- the query of an incomplete frame -- and is not reported again by the next
+// topo_join.
+int TerrainRenderer::query_finish_read(const LatestSubmission& q, const char* what) {
+    TOPO_HIP_TRY(hipStreamSynchronize(q.s));      // (the stream of the context's latest frame: all its frames are done)
+    q.c->pending = false;
+    const bool overflow = fold_latest(*q.c, false);
+    if (int rc = query_fold_check()) return rc;
+    if (overflow) return fail(TOPO_ERR_CAPACITY, std::string("rare-triangle queue overflowed: the latest submission is incomplete, and so is its ") + what);
+    return TOPO_OK;
+}
+
+// A caller's n views of W x H texels of texel_bytes, rows `pitch` and views `view_stride` bytes apart: null, or what is wrong with it.
+// (An entry point that wants them aligned says so before query_begin: a bad pointer is refused with or without a submission.)
+static const char* view_image_error(uint32_t n, uint32_t W, uint32_t H, size_t texel_bytes, size_t view_stride, size_t pitch) {
+    const size_t row = (size_t)W * texel_bytes;
+    if (pitch < row) return "pitch smaller than a row";
+    if (n > 1 && view_stride < pitch * (H - 1) + row) return "view stride smaller than a view";
+    return nullptr;
+}
+
+// ---- horizon ------------------------------------------------------------------------------------------------------------------
+
+int TerrainRenderer::horizon_shape(uint32_t* n_views, uint32_t* w, uint32_t* h) {
+    if (!n_views || !w || !h) return fail(TOPO_ERR_INVALID, "null argument");
+    if (latest_ctx_ < 0) return fail(TOPO_ERR_INVALID, "no submission to query");
+    const FrameCtx::Submission& s = ctx_[latest_ctx_].sub;      // (its shape outlives the tile set it was rendered from)
+    *n_views = s.n_views;
+    *w = s.query.W;
+    *h = s.query.H;
+    return TOPO_OK;
+}
+
+// k_horizon over views [first, first + n) of q into `out` (device), on q.s.  The decode table is all a horizon builds.
+int TerrainRenderer::horizon_launch(const LatestSubmission& q, uint32_t first, uint32_t n, HorizonPoint* out, size_t view_stride) {
+    if (int rc = prepare_tables(kDecodeTables, q.s)) return rc;
+    HorizonParams p = q.c->sub.query;
+    p.check = query_.d_check.as<uint32_t>();
+    p.tile_ll = tables_.d_ll.as<const int32_t>();
+    p.out = out;
+    p.view_stride = view_stride;
+    p.first_view = first;
+    p.n_views = n;
+    launch_horizon(p, q.s);
+    return TOPO_OK;
+}
+
+static const char* const kStrideError = "view stride smaller than a view's width";
+
+// Host read: waits for the submission and the query.
+int TerrainRenderer::horizon_read(uint32_t first, uint32_t n, topo_horizon_point* out, size_t view_stride) {
+    if (!out) return fail(TOPO_ERR_INVALID, "null argument");
+    LatestSubmission q{};
+    if (int rc = query_begin(first, n, q)) return rc;
+    if (view_stride < q.W) return fail(TOPO_ERR_INVALID, kStrideError);
+    const size_t row = (size_t)q.W * sizeof(HorizonPoint);
+    if (int rc = ensure(q.s, query_.d_horizon_out, row * n)) return rc;
+    if (int rc = horizon_launch(q, first, n, query_.d_horizon_out.as<HorizonPoint>(), q.W)) return rc;
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipMemcpy2DAsync(out, view_stride * sizeof(topo_horizon_point), query_.d_horizon_out.p, row, row, n, hipMemcpyDeviceToHost, q.s));
+    return query_finish_read(q, "horizon");
+}
+
+// Device variant: queued behind the submission on its stream; an incomplete frame writes row TOPO_HORIZON_INCOMPLETE.
+int TerrainRenderer::horizon_device(uint32_t first, uint32_t n, topo_horizon_point* out_dev, size_t view_stride) {
+    if (!out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "out_dev must be 16-byte aligned");
+    LatestSubmission q{};
+    if (int rc = query_begin(first, n, q)) return rc;
+    if (view_stride < q.W) return fail(TOPO_ERR_INVALID, kStrideError);
+    if (int rc = horizon_launch(q, first, n, (HorizonPoint*)out_dev, view_stride)) return rc;
+    return query_queued(q);
+}
+
+// ---- ground -------------------------------------------------------------------------------------------------------------------
+
+// What a ground kernel over q reads: the geometry tables, and the submission's views, uploaded by its first ground query.
+int TerrainRenderer::ground_prepare(const LatestSubmission& q) {
+    if (int rc = prepare_tables(kGeometryTables, q.s)) return rc;
+    if (FrameCtx& c = *q.c; !c.sub.views_on_device) {
+        const size_t bytes = c.sub.views.size() * sizeof(GroundView);
+        if (int rc = ensure(q.s, c.d_ground_views, bytes)) return rc;
+        TOPO_HIP_TRY(hipMemcpyAsync(c.d_ground_views.p, c.sub.views.data(), bytes, hipMemcpyHostToDevice, q.s));
+        c.sub.views_on_device = true;
+    }
+    return TOPO_OK;
+}
+
+// A ground kernel's parameters over views [first, first + n) of q, from what ground_prepare left (the tile table is the submission's).
+GroundParams TerrainRenderer::ground_params(const LatestSubmission& q, uint32_t first, uint32_t n) const {
+    GroundParams p{};
+    p.q = q.c->sub.query;
+    p.q.check = query_.d_check.as<uint32_t>();
+    p.q.tile_ll = tables_.d_ll.as<const int32_t>();
+    p.q.first_view = first;
+    p.q.n_views = n;
+    p.tiles = d_tiles_.as<const TileDev>();
+    p.views = q.c->d_ground_views.as<const GroundView>();
+    p.trig = tables_.d_trig.as<const double>();
+    p.trig_doubles = tables_.trig_doubles;
+    p.tile_w = tile_w_;
+    p.tile_h = tile_h_;
+    p.sub_views = q.n_views;
+    return p;
+}
+
+// Host read: every query is checked against the submission's shape first; waits for the submission and the query.
+int TerrainRenderer::ground_read(uint32_t n, const topo_ground_query* queries, topo_ground_point* out) {
+    if (n == 0 || !queries || !out) return fail(TOPO_ERR_INVALID, "null/empty argument");
+    LatestSubmission q{};
+    if (int rc = query_begin(0, 1, q)) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (queries[i].view >= q.n_views || queries[i].x >= q.W || queries[i].y >= q.H)
+            return fail(TOPO_ERR_INVALID, "a query names a view or pixel outside the latest submission");
+    if (int rc = ensure(q.s, query_.d_ground_q, (size_t)n * sizeof(GroundQuery))) return rc;
+    if (int rc = ensure(q.s, query_.d_ground_out, (size_t)n * sizeof(GroundPoint))) return rc;
+    if (int rc = ground_prepare(q)) return rc;
+    TOPO_HIP_TRY(hipMemcpyAsync(query_.d_ground_q.p, queries, (size_t)n * sizeof(GroundQuery), hipMemcpyHostToDevice, q.s));
+    launch_ground(ground_params(q, 0, q.n_views), query_.d_ground_q.as<const GroundQuery>(), query_.d_ground_out.as<GroundPoint>(), n, q.s);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipMemcpyAsync(out, query_.d_ground_out.p, (size_t)n * sizeof(GroundPoint), hipMemcpyDeviceToHost, q.s));
+    return query_finish_read(q, "ground points");
+}
+
+// Device variants: queued behind the submission on its stream.  The list's queries are in device memory, so the kernel checks them:
+// one outside the submission answers kind -1; an incomplete frame writes kind -2 (list) or NaN (map).
+int TerrainRenderer::ground_device(uint32_t n, const topo_ground_query* queries_dev, topo_ground_point* out_dev) {
+    if (n == 0 || !queries_dev || !out_dev) return fail(TOPO_ERR_INVALID, "null/empty argument");
+    if ((uintptr_t)out_dev % 16 != 0 || (uintptr_t)queries_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "queries_dev and out_dev must be 16-byte aligned");
+    LatestSubmission q{};
+    if (int rc = query_begin(0, 1, q)) return rc;
+    if (int rc = ground_prepare(q)) return rc;
+    launch_ground(ground_params(q, 0, q.n_views), (const GroundQuery*)queries_dev, (GroundPoint*)out_dev, n, q.s);
+    return query_queued(q);
+}
+
+int TerrainRenderer::ground_map_device(uint32_t first, uint32_t n, float* out_dev, size_t view_stride, size_t pitch) {
+    if (!out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)out_dev % 16 != 0 || view_stride % 16 != 0 || pitch % 16 != 0) return fail(TOPO_ERR_INVALID, "out_dev, the view stride and the pitch must be multiples of 16 bytes");
+    LatestSubmission q{};
+    if (int rc = query_begin(first, n, q)) return rc;
+    if (const char* why = view_image_error(n, q.W, q.H, 16, view_stride, pitch)) return fail(TOPO_ERR_INVALID, why);
+    if (int rc = ground_prepare(q)) return rc;
+    launch_ground_map(ground_params(q, first, n), out_dev, view_stride, pitch, q.s);
+    return query_queued(q);
+}
+
+// ---- rays ---------------------------------------------------------------------------------------------------------------------
+
+// The parameters of k_raycast over the resident tiles, from prepared geometry tables.
+RayParams TerrainRenderer::ray_params() const {
+    RayParams p{};
+    const uint32_t n_tiles = (uint32_t)tiles_.size();
+    p.s.tiles = d_tiles_.as<const TileDev>();
+    p.s.trig = tables_.d_trig.as<const double>();
+    p.s.spheres = tables_.d_spheres.as<const double>();
+    p.s.trig_doubles = tables_.trig_doubles;
+    p.s.n_tiles = n_tiles;
+    p.s.tile_w = tile_w_;
+    p.s.tile_h = tile_h_;
+    p.s.bx_count = n_tiles ? (tile_w_ - 1 + kBCX - 1) / kBCX : 0;
+    p.s.by_count = n_tiles ? (tile_h_ - 1 + kBCY - 1) / kBCY : 0;
+    p.tile_ll = tables_.d_ll.as<const int32_t>();
+    p.check = query_.d_check.as<uint32_t>();
+    return p;
+}
+
+// Host read: the rays go in and the records come out through one pinned staging buffer; waits for the stream.
+int TerrainRenderer::raycast_read(uint32_t n, const topo_ray* rays, topo_ray_hit* out) {
+    if (n == 0) return TOPO_OK;
+    if (!rays || !out) return fail(TOPO_ERR_INVALID, "null argument");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;      // (refreshes the tile table with them: a tile set changes both or neither)
+    const size_t bytes = (size_t)n * sizeof(LosRay);
+    if (int rc = ensure(stream_, query_.d_ray_in, bytes)) return rc;
+    if (int rc = ensure(stream_, query_.d_ray_out, bytes)) return rc;
+    if (bytes > query_.h_ray_stage.cap) TOPO_HIP_TRY(hipStreamSynchronize(stream_));      // (nothing in flight reads the old staging block)
+    if (int rc = ensure_pinned(query_.h_ray_stage, bytes)) return rc;
+    std::memcpy(query_.h_ray_stage.p, rays, bytes);
+    TOPO_HIP_TRY(hipMemcpyAsync(query_.d_ray_in.p, query_.h_ray_stage.p, bytes, hipMemcpyHostToDevice, stream_));
+    launch_raycast(ray_params(), query_.d_ray_in.as<const LosRay>(), query_.d_ray_out.as<RayHit>(), n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipMemcpyAsync(query_.h_ray_stage.p, query_.d_ray_out.p, bytes, hipMemcpyDeviceToHost, stream_));
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    std::memcpy(out, query_.h_ray_stage.p, bytes);
+    return query_fold_check();
+}
+
+// Device variant: queued on stream_, in order.
+int TerrainRenderer::raycast_device(uint32_t n, const topo_ray* rays_dev, topo_ray_hit* out_dev) {
+    if (n == 0) return TOPO_OK;
+    if (!rays_dev || !out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)rays_dev % 16 != 0 || (uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "rays_dev and out_dev must be 16-byte aligned");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    launch_raycast(ray_params(), (const LosRay*)rays_dev, (RayHit*)out_dev, n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// The sunlit layer of views [first, first + n) of the latest submission: topo_ground_map_device's rules, one byte per pixel.  The
+// rays' tables are the ground query's, prepared once: with current tables nothing waits in the middle of the stream.
+int TerrainRenderer::sunlit_map_device(uint32_t first, uint32_t n, const double sun_dir[3], uint8_t* out_dev, size_t view_stride, size_t pitch) {
+    if (!out_dev || !sun_dir) return fail(TOPO_ERR_INVALID, "null argument");
+    const double len = std::sqrt(sun_dir[0] * sun_dir[0] + sun_dir[1] * sun_dir[1] + sun_dir[2] * sun_dir[2]);
+    if (!(len > 0.0) || !std::isfinite(len)) return fail(TOPO_ERR_INVALID, "sun_dir must be finite and non-zero");
+    const double sun[3] = {sun_dir[0] / len, sun_dir[1] / len, sun_dir[2] / len};
+    LatestSubmission q{};
+    if (int rc = query_begin(first, n, q)) return rc;
+    if (const char* why = view_image_error(n, q.W, q.H, 1, view_stride, pitch)) return fail(TOPO_ERR_INVALID, why);
+    if (int rc = ground_prepare(q)) return rc;
+    launch_sunlit_map(ground_params(q, first, n), ray_params().s, sun, out_dev, view_stride, pitch, q.s);
+    return query_queued(q);
+}
+
+// ---- unwrap -------------------------------------------------------------------------------------------------------------------
+
+// Queued on stream_, in order, like topo_visible_peaks_device: the sources are the caller's, whatever wrote them.  The tables are
+// rebuilt (host, f64) and uploaded only when the parameters, the views' matrices or the eye differ from the last call's.
+int TerrainRenderer::unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h,
+                                   const OutputParams& src, const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch) {
+    if (const char* why = unwrap_params_error(params)) return fail(TOPO_ERR_INVALID, why);
+    if (const char* why = unwrap_views_error(n_views, views, src_w, src_h)) return fail(TOPO_ERR_INVALID, why);
+    if (!out.rgba && !out.depth && !src_out_dev) return fail(TOPO_ERR_INVALID, "at least one output must be given");
+    if ((out.rgba && !src.rgba) || (out.depth && !src.depth)) return fail(TOPO_ERR_INVALID, "an output needs its source");
+    const size_t row = (size_t)params->out_w * 4;
+    auto bad_out = [&](const void* p, size_t pitch) { return p && ((uintptr_t)p % 16 != 0 || pitch % 16 != 0 || pitch < row); };
+    if (bad_out(out.rgba, out.rgba_pitch) || bad_out(out.depth, out.depth_pitch) || bad_out(src_out_dev, src_out_pitch))
+        return fail(TOPO_ERR_INVALID, "output pointers and pitches must be multiples of 16 bytes, a pitch at least a row");
+    auto bad_src = [&](const void* p, size_t stride, size_t pitch) {
+        return p && ((uintptr_t)p % 4 != 0 || pitch % 4 != 0 || stride % 4 != 0 || view_image_error(n_views, src_w, src_h, 4, stride, pitch));
+    };
+    if ((out.rgba && bad_src(src.rgba, src.rgba_view_stride, src.rgba_pitch)) || (out.depth && bad_src(src.depth, src.depth_view_stride, src.depth_pitch)))
+        return fail(TOPO_ERR_INVALID, "source pointers, pitches and view strides must be multiples of 4 bytes, a pitch at least a row, a stride at least a view");
+    if (src_out_dev && (uint64_t)n_views * src_h * src_w >= (1ull << 31)) return fail(TOPO_ERR_INVALID, "the source map needs n_views * src_h * src_w < 2^31");
+    if ((((uint64_t)params->out_w + 255) / 256) * (((uint64_t)params->out_h + 3) / 4) > 0x7FFFFFFFull) return fail(TOPO_ERR_INVALID, "output too large");
+    if (int rc = bind_device()) return rc;
+
+    std::vector<uint8_t> key(sizeof *params + sizeof(uint32_t) + 3 * sizeof(float) + (size_t)n_views * 16 * sizeof(float));
+    uint8_t* k = key.data();
+    memcpy(k, params, sizeof *params); k += sizeof *params;
+    memcpy(k, &n_views, sizeof n_views); k += sizeof n_views;
+    memcpy(k, views[0].camera_pos, 3 * sizeof(float)); k += 3 * sizeof(float);
+    for (uint32_t v = 0; v < n_views; ++v, k += 16 * sizeof(float)) memcpy(k, views[v].camera_proj, 16 * sizeof(float));
+    const size_t tab_bytes = unwrap_table_doubles(n_views, params->out_w, params->out_h) * sizeof(double);
+    if (key != query_.unwrap_key || !query_.d_unwrap_tab.p) {
+        // an earlier unwrap may still read the old tables, an earlier upload the old host copy: both are on stream_
+        TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+        query_.unwrap_key.clear();
+        unwrap_tables(params, n_views, views, query_.unwrap_tab);
+        if (int rc = ensure(stream_, query_.d_unwrap_tab, tab_bytes)) return rc;
+        TOPO_HIP_TRY(hipMemcpyAsync(query_.d_unwrap_tab.p, query_.unwrap_tab.data(), tab_bytes, hipMemcpyHostToDevice, stream_));
+        query_.unwrap_key = std::move(key);
+    }
+    if (int rc = ensure_query_check(stream_)) return rc;
+    UnwrapParams p{};
+    p.tab = query_.d_unwrap_tab.as<const double>();
+    p.rgba_src = out.rgba ? src.rgba : nullptr;
+    p.rgba_view_stride = src.rgba_view_stride;
+    p.rgba_pitch = src.rgba_pitch;
+    p.depth_src = out.depth ? reinterpret_cast<const uint8_t*>(src.depth) : nullptr;
+    p.depth_view_stride = src.depth_view_stride;
+    p.depth_pitch = src.depth_pitch;
+    p.rgba_out = out.rgba;
+    p.rgba_out_pitch = out.rgba_pitch;
+    p.depth_out = reinterpret_cast<uint8_t*>(out.depth);
+    p.depth_out_pitch = out.depth_pitch;
+    p.src_out = reinterpret_cast<uint8_t*>(src_out_dev);
+    p.src_out_pitch = src_out_pitch;
+    p.check = query_.d_check.as<uint32_t>();
+    p.n_views = n_views;
+    p.src_w = src_w;
+    p.src_h = src_h;
+    p.out_w = params->out_w;
+    p.out_h = params->out_h;
+    p.srgb = format_ == TOPO_FORMAT_RGBA8_UNORM_SRGB || format_ == TOPO_FORMAT_BGRA8_UNORM_SRGB;
+    launch_unwrap(p, params->filter == TOPO_UNWRAP_BILINEAR, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+}  // namespace topo

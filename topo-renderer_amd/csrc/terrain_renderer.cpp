@@ -515,7 +515,6 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     bool pack_in_cull = false;
     if (int rc = stage_views(c, stream, views, p, pack, &pack_in_cull)) return rc;
     fill_params(c, p);
-    last_blocks_tested_ = p.work_cap;
     last_far_phase_ = p.split_m > 0.0f && !(switches().far_skip && far_phase_empty(views, n, tiles_, &p.split_m));
     const CullList cull = cull_pairs(views, p);
     if (int rc = queue_frame(c, stream, p, pack_in_cull ? &pack : nullptr, cull, last_far_phase_, out, slots, n_slots, after_slot)) return rc;
@@ -526,21 +525,13 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
 
 // The (view, tile) pairs the cull is launched over: those the host's prefilter keeps (host_math.hpp: tile_prefilter), when the
 // prefilter is on (TOPO_TILE_PREFILTER=0, topo_debug_set_tile_prefilter: off) and their list fits the launch's argument segment;
-// otherwise every pair, as the full grid (`codes` null).  The tiles' spheres are gathered once per tile set.
+// otherwise every pair, as the full grid (`codes` null).  The tiles' spheres are gathered once per tile set (tile_spheres).
 TerrainRenderer::CullList TerrainRenderer::cull_pairs(const topo_uniforms* views, const FrameParams& p) {
     const size_t all = (size_t)p.n_views * p.n_tiles;
     last_cull_pairs_[0] = last_cull_pairs_[1] = (uint32_t)all;
     CullList list{nullptr, 0};
     if (!tile_prefilter_ || all == 0 || all > 65536) return list;
-    if (tile_spheres_gen_ != tile_gen_) {
-        tile_spheres_.clear();
-        for (const auto& kv : tiles_) {
-            tile_spheres_.insert(tile_spheres_.end(), kv.second.centres, kv.second.centres + 4);
-            tile_spheres_.push_back(kv.second.block_radius);
-        }
-        tile_spheres_gen_ = tile_gen_;
-    }
-    const uint32_t kept = tile_prefilter(views, p.n_views, tile_spheres_.data(), p.n_tiles, cull_codes_, kMaxCullPairs);
+    const uint32_t kept = tile_prefilter(views, p.n_views, tile_spheres().data(), p.n_tiles, cull_codes_, kMaxCullPairs);
     if (kept > kMaxCullPairs) return list;
     last_cull_pairs_[0] = kept;
     list.codes = cull_codes_;
@@ -802,467 +793,6 @@ void TerrainRenderer::record_submission(FrameCtx& c, const FrameParams& p, const
     q.div_tris = p.div_tris;
     q.div_hm1 = p.div_hm1;
     latest_ctx_ = (int)(&c - ctx_);
-}
-
-// ---- viewshed ----------------------------------------------------------------------------------------------------------------
-
-int TerrainRenderer::alloc_mask(Tile& t) {
-    DeviceBuffer m;      // (the tile gets it once it is zeroed)
-    if (int rc = ensure(stream_, m, mask_bytes())) return rc;
-    TOPO_HIP_TRY(hipMemsetAsync(m.p, 0, mask_bytes(), stream_));      // (frames on other streams are ordered after stream_)
-    t.mask = std::move(m);
-    return TOPO_OK;
-}
-
-// The masks are allocated when accumulation is first turned on (for the tiles loaded then; later tiles get theirs in add_terrain) and
-// kept until the tile goes; turning accumulation off only stops the launches.
-int TerrainRenderer::viewshed_enable(bool on) {
-    if (int rc = bind_device()) return rc;
-    if (on && !vs_ever_) {
-        if (int rc = join()) return rc;
-        const size_t stats = (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long);
-        if (!d_vs_stats_.p) {
-            if (int rc = ensure(stream_, d_vs_stats_, stats)) return rc;
-            TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_.p, 0, stats, stream_));
-        }
-        for (auto& kv : tiles_)
-            if (!kv.second.mask.p)
-                if (int rc = alloc_mask(kv.second)) return rc;
-        vs_ever_ = true;
-        table_dirty_ = true;      // the next submission uploads the rank -> mask table with the tile table
-    }
-    vs_on_ = on;
-    return TOPO_OK;
-}
-
-int TerrainRenderer::viewshed_reset() {
-    if (int rc = bind_device()) return rc;
-    if (!vs_ever_) return TOPO_OK;
-    if (int rc = join()) return rc;      // frames in flight on the contexts' own streams; later ones are ordered after stream_
-    for (auto& kv : tiles_) TOPO_HIP_TRY(hipMemsetAsync(kv.second.mask.p, 0, mask_bytes(), stream_));
-    TOPO_HIP_TRY(hipMemsetAsync(d_vs_stats_.p, 0, (size_t)kViewshedStatSlots * 4 * sizeof(unsigned long long), stream_));
-    return TOPO_OK;
-}
-
-int TerrainRenderer::viewshed_read(int32_t lat, int32_t lon, uint8_t* mask_out, size_t pitch, uint64_t* n_visible) {
-    if (!mask_out) return fail(TOPO_ERR_INVALID, "mask_out is null");
-    Tile* t = find(lat, lon);
-    if (!t) return fail(TOPO_ERR_NOT_FOUND, "no such tile");
-    if (!vs_ever_) return fail(TOPO_ERR_INVALID, "viewshed accumulation was never enabled");
-    const uint32_t wm1 = tile_w_ - 1, hm1 = tile_h_ - 1;
-    if (pitch < wm1) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
-    if (int rc = wait_all()) return rc;
-    std::vector<uint32_t> words(mask_bytes() / 4);
-    TOPO_HIP_TRY(hipMemcpy(words.data(), t->mask.p, mask_bytes(), hipMemcpyDeviceToHost));
-    uint64_t count = 0;
-    for (uint32_t x = 0, bit = 0; x < wm1; ++x)      // bit = x (h-1) + y: the cell of the draw id's triangle (triangle_vertices)
-        for (uint32_t y = 0; y < hm1; ++y, ++bit) {
-            const uint8_t v = (uint8_t)((words[bit >> 5] >> (bit & 31u)) & 1u);
-            mask_out[(size_t)y * pitch + x] = v;
-            count += v;
-        }
-    if (n_visible) *n_visible = count;
-    return TOPO_OK;
-}
-
-int TerrainRenderer::viewshed_stats(uint64_t out[3]) {
-    if (!out) return fail(TOPO_ERR_INVALID, "null argument");
-    out[0] = out[1] = out[2] = 0;
-    if (!vs_ever_) return TOPO_OK;
-    if (int rc = wait_all()) return rc;
-    std::vector<unsigned long long> s((size_t)kViewshedStatSlots * 4);
-    TOPO_HIP_TRY(hipMemcpy(s.data(), d_vs_stats_.p, s.size() * sizeof(s[0]), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < s.size(); i += 4)
-        for (int k = 0; k < 3; ++k) out[k] += s[i + k];
-    return TOPO_OK;
-}
-
-// ---- horizon ------------------------------------------------------------------------------------------------------------------
-
-static_assert(sizeof(HorizonPoint) == sizeof(topo_horizon_point) && sizeof(topo_horizon_point) == 32, "horizon record layout");
-
-int TerrainRenderer::horizon_shape(uint32_t* n_views, uint32_t* w, uint32_t* h) {
-    if (!n_views || !w || !h) return fail(TOPO_ERR_INVALID, "null argument");
-    if (latest_ctx_ < 0) return fail(TOPO_ERR_INVALID, "no submission to query");
-    const FrameCtx::Submission& s = ctx_[latest_ctx_].sub;
-    *n_views = s.n_views;
-    *w = s.query.W;
-    *h = s.query.H;
-    return TOPO_OK;
-}
-
-// The latest submission, if views [first, first + n) of it can be answered: its context and the stream it was queued on (the one a
-// query is queued on, behind it).  Tiles added, replaced or unloaded since have taken its draw order with them.
-int TerrainRenderer::query_prepare(uint32_t first, uint32_t n, FrameCtx** out_c, hipStream_t* out_s) {
-    if (latest_ctx_ < 0) return fail(TOPO_ERR_INVALID, "no submission to query");
-    FrameCtx& c = ctx_[latest_ctx_];
-    if (c.sub.tile_gen != tile_gen_) return fail(TOPO_ERR_INVALID, "tiles were added or unloaded since the latest submission: its draw order is gone");
-    if (n == 0 || first >= c.sub.n_views || n > c.sub.n_views - first) return fail(TOPO_ERR_INVALID, "views outside the latest submission");
-    if (int rc = bind_device()) return rc;
-    *out_c = &c;
-    *out_s = c.last_stream ? c.last_stream : stream_;      // (null: a wait covered it and the stream may be gone; the frame is done)
-    return TOPO_OK;
-}
-
-// The tables a query kernel reads besides the submission's own.  The rank -> (lat, lon) table is the current tile order, which
-// query_prepare has checked to be the submission's; it is rebuilt after the tile set changed, once every earlier query has finished
-// (add_terrain / unload_terrain join the frames, and a query on a context's own stream marks it pending).  The check build's bounds record.
-int TerrainRenderer::query_tables(hipStream_t s) {
-    if (hz_ll_gen_ != tile_gen_) {
-        if (int rc = wait_all()) return rc;
-        hz_ll_.clear();
-        for (const auto& kv : tiles_) {      // draw order
-            hz_ll_.push_back(kv.second.lat);
-            hz_ll_.push_back(kv.second.lon);
-        }
-        if (int rc = ensure(stream_, d_hz_ll_, (hz_ll_.size() + 2) * sizeof(int32_t))) return rc;
-        if (!hz_ll_.empty()) TOPO_HIP_TRY(hipMemcpyAsync(d_hz_ll_.p, hz_ll_.data(), hz_ll_.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        hz_ll_gen_ = tile_gen_;
-    }
-    return ensure_query_check(s);
-}
-
-int TerrainRenderer::ensure_query_check(hipStream_t s) {
-#ifdef TOPO_BOUNDS_CHECK
-    if (!d_hz_check_.p) {
-        if (int rc = ensure(s, d_hz_check_, kStatusWords * sizeof(uint32_t))) return rc;
-        TOPO_HIP_TRY(hipMemsetAsync(d_hz_check_.p, 0, kStatusWords * sizeof(uint32_t), s));
-    }
-#else
-    (void)s;
-#endif
-    return TOPO_OK;
-}
-
-// k_horizon over views [first, first + n) of c's latest submission into `out` (device), on s.
-int TerrainRenderer::horizon_launch(FrameCtx& c, uint32_t first, uint32_t n, HorizonPoint* out, size_t view_stride, hipStream_t s) {
-    if (int rc = query_tables(s)) return rc;
-    HorizonParams p = c.sub.query;
-    p.check = d_hz_check_.as<uint32_t>();
-    p.tile_ll = d_hz_ll_.as<const int32_t>();
-    p.out = out;
-    p.view_stride = view_stride;
-    p.first_view = first;
-    p.n_views = n;
-    launch_horizon(p, s);
-    TOPO_HIP_TRY(hipGetLastError());
-    return TOPO_OK;
-}
-
-// The bounds-checking build: what the query kernels recorded, into the status topo_frame_status reports (the queries have finished).
-int TerrainRenderer::query_fold_check() {
-#ifdef TOPO_BOUNDS_CHECK
-    if (!d_hz_check_.p) return TOPO_OK;
-    uint32_t w[kStatusWords];
-    TOPO_HIP_TRY(hipMemcpy(w, d_hz_check_.p, sizeof w, hipMemcpyDeviceToHost));
-    if (w[kCtrStatus] & kStatusBounds) {
-        record_bounds(w);
-        TOPO_HIP_TRY(hipMemset(d_hz_check_.p, 0, sizeof w));
-    }
-#endif
-    return TOPO_OK;
-}
-
-// The end of a host read: waits for the submission and the query queued behind it on s.  The submission's status is folded as
-// topo_render folds its own frame: the frames of its context in front of it go to the next topo_join (their overflow stays pending
-// there), and its own overflow is this call's error -- the query of an incomplete frame -- and is not reported again by the next
-// topo_join.
-int TerrainRenderer::query_finish_read(FrameCtx& c, hipStream_t s, const char* what) {
-    TOPO_HIP_TRY(hipStreamSynchronize(s));      // (the stream of the context's latest frame: all its frames are done)
-    c.pending = false;
-    const bool overflow = fold_latest(c, false);
-    if (int rc = query_fold_check()) return rc;
-    if (overflow) return fail(TOPO_ERR_CAPACITY, std::string("rare-triangle queue overflowed: the latest submission is incomplete, and so is its ") + what);
-    return TOPO_OK;
-}
-
-static const char* const kStrideError = "view stride smaller than a view's width";
-
-// Host read: waits for the submission and the query.
-int TerrainRenderer::horizon_read(uint32_t first, uint32_t n, topo_horizon_point* out, size_t view_stride) {
-    if (!out) return fail(TOPO_ERR_INVALID, "null argument");
-    FrameCtx* c = nullptr;
-    hipStream_t s = nullptr;
-    if (int rc = query_prepare(first, n, &c, &s)) return rc;
-    if (view_stride < c->sub.query.W) return fail(TOPO_ERR_INVALID, kStrideError);
-    const size_t row = (size_t)c->sub.query.W * sizeof(HorizonPoint);
-    if (int rc = ensure(s, d_hz_out_, row * n)) return rc;
-    if (int rc = horizon_launch(*c, first, n, d_hz_out_.as<HorizonPoint>(), c->sub.query.W, s)) return rc;
-    TOPO_HIP_TRY(hipMemcpy2DAsync(out, view_stride * sizeof(topo_horizon_point), d_hz_out_.p, row, row, n, hipMemcpyDeviceToHost, s));
-    return query_finish_read(*c, s, "horizon");
-}
-
-// Device variant: queued behind the submission on its stream; an incomplete frame writes row TOPO_HORIZON_INCOMPLETE.
-int TerrainRenderer::horizon_device(uint32_t first, uint32_t n, topo_horizon_point* out_dev, size_t view_stride) {
-    if (!out_dev) return fail(TOPO_ERR_INVALID, "null argument");
-    if ((uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "out_dev must be 16-byte aligned");
-    FrameCtx* c = nullptr;
-    hipStream_t s = nullptr;
-    if (int rc = query_prepare(first, n, &c, &s)) return rc;
-    if (view_stride < c->sub.query.W) return fail(TOPO_ERR_INVALID, kStrideError);
-    if (int rc = horizon_launch(*c, first, n, (HorizonPoint*)out_dev, view_stride, s)) return rc;
-    if (s != stream_) c->pending = true;      // a context's own stream: the next join (and whatever rewrites the frame) waits for the query too
-    return TOPO_OK;
-}
-
-// ---- ground -------------------------------------------------------------------------------------------------------------------
-
-static_assert(sizeof(GroundPoint) == sizeof(topo_ground_point) && sizeof(topo_ground_point) == 64, "ground record layout");
-static_assert(sizeof(GroundQuery) == sizeof(topo_ground_query) && sizeof(topo_ground_query) == 16, "ground query layout");
-
-// The tiles' f64 (cos, sin) tables and, for the rays, their spheres: once per tile set.
-int TerrainRenderer::ground_tables(hipStream_t s) {
-    if (ground_trig_gen_ == tile_gen_) return TOPO_OK;
-    // nothing that could still read the old tables is left running, and the new ones are complete before a query can be queued
-    // on any other stream
-    if (int rc = wait_all()) return rc;
-    // The rays need no frame, so the device tile table (and the viewshed's rank -> mask table that travels with it) may still be
-    // the one from before an unload: whoever needs it first refreshes it, here as in render_frame.  On the ground queries' path
-    // this is a no-op: query_prepare has refused a submission whose tile set changed, and a frame uploaded the table before it.
-    if (int rc = upload_tile_table()) return rc;
-    const size_t trig_doubles = tiles_.size() * ground_table_doubles(tile_w_, tile_h_);
-    if (int rc = ensure(s, d_ground_trig_, (trig_doubles + 2) * sizeof(double))) return rc;
-    launch_ground_tables(d_tiles_.as<const TileDev>(), (uint32_t)tiles_.size(), d_ground_trig_.as<double>(), tile_w_, tile_h_, s);
-    TOPO_HIP_TRY(hipGetLastError());
-    std::vector<double> spheres;
-    for (const auto& kv : tiles_) {      // draw order
-        spheres.insert(spheres.end(), kv.second.centres, kv.second.centres + 4);
-        spheres.push_back(kv.second.block_radius);
-    }
-    if (int rc = ensure(s, d_los_spheres_, (spheres.size() + 2) * sizeof(double))) return rc;
-    if (!spheres.empty()) TOPO_HIP_TRY(hipMemcpyAsync(d_los_spheres_.p, spheres.data(), spheres.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    TOPO_HIP_TRY(hipStreamSynchronize(s));
-    ground_trig_gen_ = tile_gen_;
-    return TOPO_OK;
-}
-
-// The parameters of a ground kernel over c's latest submission, on s: the shared tables, the tile table (the submission's: the tile
-// set has not changed since) and the submission's views, which its first ground query uploads from the host copy the submission kept.
-int TerrainRenderer::ground_params(FrameCtx& c, hipStream_t s, GroundParams& p) {
-    if (int rc = query_tables(s)) return rc;
-    const size_t trig_doubles = tiles_.size() * ground_table_doubles(tile_w_, tile_h_);
-    if (int rc = ground_tables(s)) return rc;
-    if (!c.sub.views_on_device) {
-        const size_t bytes = c.sub.views.size() * sizeof(GroundView);
-        if (int rc = ensure(s, c.d_ground_views, bytes)) return rc;
-        TOPO_HIP_TRY(hipMemcpyAsync(c.d_ground_views.p, c.sub.views.data(), bytes, hipMemcpyHostToDevice, s));
-        c.sub.views_on_device = true;
-    }
-    p.q = c.sub.query;
-    p.q.check = d_hz_check_.as<uint32_t>();
-    p.q.tile_ll = d_hz_ll_.as<const int32_t>();
-    p.q.first_view = 0;
-    p.q.n_views = c.sub.n_views;
-    p.tiles = d_tiles_.as<const TileDev>();
-    p.views = c.d_ground_views.as<const GroundView>();
-    p.trig = d_ground_trig_.as<const double>();
-    p.trig_doubles = trig_doubles;
-    p.tile_w = tile_w_;
-    p.tile_h = tile_h_;
-    p.sub_views = c.sub.n_views;
-    return TOPO_OK;
-}
-
-// Host read: every query is checked against the submission's shape first; waits for the submission and the query.
-int TerrainRenderer::ground_read(uint32_t n, const topo_ground_query* queries, topo_ground_point* out) {
-    if (n == 0 || !queries || !out) return fail(TOPO_ERR_INVALID, "null/empty argument");
-    FrameCtx* c = nullptr;
-    hipStream_t s = nullptr;
-    if (int rc = query_prepare(0, 1, &c, &s)) return rc;
-    for (uint32_t i = 0; i < n; ++i)
-        if (queries[i].view >= c->sub.n_views || queries[i].x >= c->sub.query.W || queries[i].y >= c->sub.query.H)
-            return fail(TOPO_ERR_INVALID, "a query names a view or pixel outside the latest submission");
-    if (int rc = ensure(s, d_ground_q_, (size_t)n * sizeof(GroundQuery))) return rc;
-    if (int rc = ensure(s, d_ground_out_, (size_t)n * sizeof(GroundPoint))) return rc;
-    GroundParams p{};
-    if (int rc = ground_params(*c, s, p)) return rc;
-    TOPO_HIP_TRY(hipMemcpyAsync(d_ground_q_.p, queries, (size_t)n * sizeof(GroundQuery), hipMemcpyHostToDevice, s));
-    launch_ground(p, d_ground_q_.as<const GroundQuery>(), d_ground_out_.as<GroundPoint>(), n, s);
-    TOPO_HIP_TRY(hipGetLastError());
-    TOPO_HIP_TRY(hipMemcpyAsync(out, d_ground_out_.p, (size_t)n * sizeof(GroundPoint), hipMemcpyDeviceToHost, s));
-    return query_finish_read(*c, s, "ground points");
-}
-
-// Device variants: queued behind the submission on its stream.  The list's queries are in device memory, so the kernel checks them:
-// one outside the submission answers kind -1; an incomplete frame writes kind -2 (list) or NaN (map).
-int TerrainRenderer::ground_device(uint32_t n, const topo_ground_query* queries_dev, topo_ground_point* out_dev) {
-    if (n == 0 || !queries_dev || !out_dev) return fail(TOPO_ERR_INVALID, "null/empty argument");
-    if ((uintptr_t)out_dev % 16 != 0 || (uintptr_t)queries_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "queries_dev and out_dev must be 16-byte aligned");
-    FrameCtx* c = nullptr;
-    hipStream_t s = nullptr;
-    if (int rc = query_prepare(0, 1, &c, &s)) return rc;
-    GroundParams p{};
-    if (int rc = ground_params(*c, s, p)) return rc;
-    launch_ground(p, (const GroundQuery*)queries_dev, (GroundPoint*)out_dev, n, s);
-    TOPO_HIP_TRY(hipGetLastError());
-    if (s != stream_) c->pending = true;      // (as topo_horizon_device)
-    return TOPO_OK;
-}
-
-int TerrainRenderer::ground_map_device(uint32_t first, uint32_t n, float* out_dev, size_t view_stride, size_t pitch) {
-    if (!out_dev) return fail(TOPO_ERR_INVALID, "null argument");
-    if ((uintptr_t)out_dev % 16 != 0 || view_stride % 16 != 0 || pitch % 16 != 0) return fail(TOPO_ERR_INVALID, "out_dev, the view stride and the pitch must be multiples of 16 bytes");
-    FrameCtx* c = nullptr;
-    hipStream_t s = nullptr;
-    if (int rc = query_prepare(first, n, &c, &s)) return rc;
-    if (pitch < (size_t)c->sub.query.W * 16) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
-    if (n > 1 && view_stride < pitch * (c->sub.query.H - 1) + (size_t)c->sub.query.W * 16) return fail(TOPO_ERR_INVALID, "view stride smaller than a view");
-    GroundParams p{};
-    if (int rc = ground_params(*c, s, p)) return rc;
-    p.q.first_view = first;
-    p.q.n_views = n;
-    launch_ground_map(p, out_dev, view_stride, pitch, s);
-    TOPO_HIP_TRY(hipGetLastError());
-    if (s != stream_) c->pending = true;
-    return TOPO_OK;
-}
-
-// ---- rays ---------------------------------------------------------------------------------------------------------------------
-
-static_assert(sizeof(LosRay) == sizeof(topo_ray) && sizeof(topo_ray) == 64, "ray layout");
-static_assert(sizeof(RayHit) == sizeof(topo_ray_hit) && sizeof(topo_ray_hit) == 64, "ray record layout");
-
-// The parameters of k_raycast over the resident tiles, on s: the tile table, the rank -> (lat, lon) table, the f64 tables and the
-// spheres, each rebuilt after the tile set changed.
-int TerrainRenderer::ray_params(hipStream_t s, RayParams& p) {
-    if (int rc = bind_device()) return rc;
-    if (int rc = query_tables(s)) return rc;
-    if (int rc = ground_tables(s)) return rc;      // (refreshes the tile table with them: a tile set changes both or neither)
-    const uint32_t n_tiles = (uint32_t)tiles_.size();
-    p.s.tiles = d_tiles_.as<const TileDev>();
-    p.s.trig = d_ground_trig_.as<const double>();
-    p.s.spheres = d_los_spheres_.as<const double>();
-    p.s.trig_doubles = n_tiles * ground_table_doubles(tile_w_, tile_h_);
-    p.s.n_tiles = n_tiles;
-    p.s.tile_w = tile_w_;
-    p.s.tile_h = tile_h_;
-    p.s.bx_count = n_tiles ? (tile_w_ - 1 + kBCX - 1) / kBCX : 0;
-    p.s.by_count = n_tiles ? (tile_h_ - 1 + kBCY - 1) / kBCY : 0;
-    p.tile_ll = d_hz_ll_.as<const int32_t>();
-    p.check = d_hz_check_.as<uint32_t>();
-    return TOPO_OK;
-}
-
-// Host read: the rays go in and the records come out through one pinned staging buffer; waits for the stream.
-int TerrainRenderer::raycast_read(uint32_t n, const topo_ray* rays, topo_ray_hit* out) {
-    if (n == 0) return TOPO_OK;
-    if (!rays || !out) return fail(TOPO_ERR_INVALID, "null argument");
-    RayParams p{};
-    if (int rc = ray_params(stream_, p)) return rc;
-    const size_t bytes = (size_t)n * sizeof(LosRay);
-    if (int rc = ensure(stream_, d_ray_in_, bytes)) return rc;
-    if (int rc = ensure(stream_, d_ray_out_, bytes)) return rc;
-    if (bytes > h_ray_stage_.cap) TOPO_HIP_TRY(hipStreamSynchronize(stream_));      // (nothing in flight reads the old staging block)
-    if (int rc = ensure_pinned(h_ray_stage_, bytes)) return rc;
-    std::memcpy(h_ray_stage_.p, rays, bytes);
-    TOPO_HIP_TRY(hipMemcpyAsync(d_ray_in_.p, h_ray_stage_.p, bytes, hipMemcpyHostToDevice, stream_));
-    launch_raycast(p, d_ray_in_.as<const LosRay>(), d_ray_out_.as<RayHit>(), n, stream_);
-    TOPO_HIP_TRY(hipGetLastError());
-    TOPO_HIP_TRY(hipMemcpyAsync(h_ray_stage_.p, d_ray_out_.p, bytes, hipMemcpyDeviceToHost, stream_));
-    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-    std::memcpy(out, h_ray_stage_.p, bytes);
-    return query_fold_check();
-}
-
-// Device variant: queued on stream_, in order.
-int TerrainRenderer::raycast_device(uint32_t n, const topo_ray* rays_dev, topo_ray_hit* out_dev) {
-    if (n == 0) return TOPO_OK;
-    if (!rays_dev || !out_dev) return fail(TOPO_ERR_INVALID, "null argument");
-    if ((uintptr_t)rays_dev % 16 != 0 || (uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "rays_dev and out_dev must be 16-byte aligned");
-    RayParams p{};
-    if (int rc = ray_params(stream_, p)) return rc;
-    launch_raycast(p, (const LosRay*)rays_dev, (RayHit*)out_dev, n, stream_);
-    TOPO_HIP_TRY(hipGetLastError());
-    return TOPO_OK;
-}
-
-// The sunlit layer of views [first, first + n) of the latest submission: topo_ground_map_device's rules, one byte per pixel.
-int TerrainRenderer::sunlit_map_device(uint32_t first, uint32_t n, const double sun_dir[3], uint8_t* out_dev, size_t view_stride, size_t pitch) {
-    if (!out_dev || !sun_dir) return fail(TOPO_ERR_INVALID, "null argument");
-    const double len = std::sqrt(sun_dir[0] * sun_dir[0] + sun_dir[1] * sun_dir[1] + sun_dir[2] * sun_dir[2]);
-    if (!(len > 0.0) || !std::isfinite(len)) return fail(TOPO_ERR_INVALID, "sun_dir must be finite and non-zero");
-    const double sun[3] = {sun_dir[0] / len, sun_dir[1] / len, sun_dir[2] / len};
-    FrameCtx* c = nullptr;
-    hipStream_t s = nullptr;
-    if (int rc = query_prepare(first, n, &c, &s)) return rc;
-    if (pitch < (size_t)c->sub.query.W) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
-    if (n > 1 && view_stride < pitch * (c->sub.query.H - 1) + (size_t)c->sub.query.W) return fail(TOPO_ERR_INVALID, "view stride smaller than a view");
-    GroundParams p{};
-    if (int rc = ground_params(*c, s, p)) return rc;
-    p.q.first_view = first;
-    p.q.n_views = n;
-    RayParams rp{};
-    if (int rc = ray_params(s, rp)) return rc;      // (the tables are the ground query's: nothing is rebuilt here)
-    launch_sunlit_map(p, rp.s, sun, out_dev, view_stride, pitch, s);
-    TOPO_HIP_TRY(hipGetLastError());
-    if (s != stream_) c->pending = true;
-    return TOPO_OK;
-}
-
-// ---- unwrap -------------------------------------------------------------------------------------------------------------------
-
-// Queued on stream_, in order, like topo_visible_peaks_device: the sources are the caller's, whatever wrote them.  The tables are
-// rebuilt (host, f64) and uploaded only when the parameters, the views' matrices or the eye differ from the last call's.
-int TerrainRenderer::unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h,
-                                   const OutputParams& src, const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch) {
-    if (const char* why = unwrap_params_error(params)) return fail(TOPO_ERR_INVALID, why);
-    if (const char* why = unwrap_views_error(n_views, views, src_w, src_h)) return fail(TOPO_ERR_INVALID, why);
-    if (!out.rgba && !out.depth && !src_out_dev) return fail(TOPO_ERR_INVALID, "at least one output must be given");
-    if ((out.rgba && !src.rgba) || (out.depth && !src.depth)) return fail(TOPO_ERR_INVALID, "an output needs its source");
-    const size_t row = (size_t)params->out_w * 4, src_row = (size_t)src_w * 4;
-    auto bad_out = [&](const void* p, size_t pitch) { return p && ((uintptr_t)p % 16 != 0 || pitch % 16 != 0 || pitch < row); };
-    if (bad_out(out.rgba, out.rgba_pitch) || bad_out(out.depth, out.depth_pitch) || bad_out(src_out_dev, src_out_pitch))
-        return fail(TOPO_ERR_INVALID, "output pointers and pitches must be multiples of 16 bytes, a pitch at least a row");
-    auto bad_src = [&](const void* p, size_t stride, size_t pitch) {
-        return p && ((uintptr_t)p % 4 != 0 || pitch % 4 != 0 || stride % 4 != 0 || pitch < src_row || (n_views > 1 && stride < pitch * (src_h - 1) + src_row));
-    };
-    if ((out.rgba && bad_src(src.rgba, src.rgba_view_stride, src.rgba_pitch)) || (out.depth && bad_src(src.depth, src.depth_view_stride, src.depth_pitch)))
-        return fail(TOPO_ERR_INVALID, "source pointers, pitches and view strides must be multiples of 4 bytes, a pitch at least a row, a stride at least a view");
-    if (src_out_dev && (uint64_t)n_views * src_h * src_w >= (1ull << 31)) return fail(TOPO_ERR_INVALID, "the source map needs n_views * src_h * src_w < 2^31");
-    if ((((uint64_t)params->out_w + 255) / 256) * (((uint64_t)params->out_h + 3) / 4) > 0x7FFFFFFFull) return fail(TOPO_ERR_INVALID, "output too large");
-    if (int rc = bind_device()) return rc;
-
-    std::vector<uint8_t> key(sizeof *params + sizeof(uint32_t) + 3 * sizeof(float) + (size_t)n_views * 16 * sizeof(float));
-    uint8_t* k = key.data();
-    memcpy(k, params, sizeof *params); k += sizeof *params;
-    memcpy(k, &n_views, sizeof n_views); k += sizeof n_views;
-    memcpy(k, views[0].camera_pos, 3 * sizeof(float)); k += 3 * sizeof(float);
-    for (uint32_t v = 0; v < n_views; ++v, k += 16 * sizeof(float)) memcpy(k, views[v].camera_proj, 16 * sizeof(float));
-    const size_t tab_bytes = unwrap_table_doubles(n_views, params->out_w, params->out_h) * sizeof(double);
-    if (key != unwrap_key_ || !d_unwrap_tab_.p) {
-        // an earlier unwrap may still read the old tables, an earlier upload the old host copy: both are on stream_
-        TOPO_HIP_TRY(hipStreamSynchronize(stream_));
-        unwrap_key_.clear();
-        unwrap_tables(params, n_views, views, unwrap_tab_);
-        if (int rc = ensure(stream_, d_unwrap_tab_, tab_bytes)) return rc;
-        TOPO_HIP_TRY(hipMemcpyAsync(d_unwrap_tab_.p, unwrap_tab_.data(), tab_bytes, hipMemcpyHostToDevice, stream_));
-        unwrap_key_ = std::move(key);
-    }
-    if (int rc = ensure_query_check(stream_)) return rc;
-    UnwrapParams p{};
-    p.tab = d_unwrap_tab_.as<const double>();
-    p.rgba_src = out.rgba ? src.rgba : nullptr;
-    p.rgba_view_stride = src.rgba_view_stride;
-    p.rgba_pitch = src.rgba_pitch;
-    p.depth_src = out.depth ? reinterpret_cast<const uint8_t*>(src.depth) : nullptr;
-    p.depth_view_stride = src.depth_view_stride;
-    p.depth_pitch = src.depth_pitch;
-    p.rgba_out = out.rgba;
-    p.rgba_out_pitch = out.rgba_pitch;
-    p.depth_out = reinterpret_cast<uint8_t*>(out.depth);
-    p.depth_out_pitch = out.depth_pitch;
-    p.src_out = reinterpret_cast<uint8_t*>(src_out_dev);
-    p.src_out_pitch = src_out_pitch;
-    p.check = d_hz_check_.as<uint32_t>();
-    p.n_views = n_views;
-    p.src_w = src_w;
-    p.src_h = src_h;
-    p.out_w = params->out_w;
-    p.out_h = params->out_h;
-    p.srgb = format_ == TOPO_FORMAT_RGBA8_UNORM_SRGB || format_ == TOPO_FORMAT_BGRA8_UNORM_SRGB;
-    launch_unwrap(p, params->filter == TOPO_UNWRAP_BILINEAR, stream_);
-    TOPO_HIP_TRY(hipGetLastError());
-    return TOPO_OK;
 }
 
 int TerrainRenderer::render_device(uint8_t* rgba_dev, size_t rgba_pitch, float* depth_dev, size_t depth_pitch) {

@@ -195,7 +195,7 @@ class TerrainRenderer {
     int upload_tile_table();
     int overlay_upload(const void* a, size_t a_bytes, const void* b, size_t b_bytes, uint8_t** b_dev, bool* keys_fresh);
     template <class Draw> int overlay_host_image(uint8_t* rgba, size_t rgba_pitch, Draw draw);
-    int alloc_mask(Tile& t);
+    int alloc_mask(Tile& t);                                      // viewshed (terrain_queries.cpp)
     size_t mask_bytes() const { return (((size_t)(tile_w_ - 1) * (tile_h_ - 1) + 31) / 32) * 4; }
 
     int device_ = 0;
@@ -309,13 +309,10 @@ class TerrainRenderer {
     uint32_t overlay_w_ = 0, overlay_h_ = 0;
     bool have_depth_ = false;
     uint32_t depth_w_ = 0, depth_h_ = 0;
-    uint32_t last_blocks_tested_ = 0;
     bool last_far_phase_ = true;           // whether the last submission launched the far phase (test hook)
-    // the cull's tile prefilter: on / off, the tiles' spheres (kTileSphereDoubles each, draw order) and the tile set they were gathered
-    // from, the last submission's kept pairs (the launch copies them) and its counts (pairs launched, pairs in all: test hook)
+    // the cull's tile prefilter: on / off (the tiles' spheres: tile_spheres), the last submission's kept pairs (the launch copies
+    // them) and its counts (pairs launched, pairs in all: test hook)
     bool tile_prefilter_ = true;
-    std::vector<double> tile_spheres_;
-    uint64_t tile_spheres_gen_ = ~0ull;
     uint16_t cull_codes_[kMaxCullPairs] = {};
     uint32_t last_cull_pairs_[2] = {0, 0};
     // viewshed: render_frame launches k_viewshed while vs_on_; the masks exist (every tile has one) once vs_ever_.  The masks are shared
@@ -323,41 +320,50 @@ class TerrainRenderer {
     bool vs_on_ = false, vs_ever_ = false;
     DeviceBuffer d_vs_table_;      // rank -> the tile's mask, rebuilt with the tile table
     DeviceBuffer d_vs_stats_;      // kViewshedStatSlots x 4 counters of k_viewshed
-    // horizon, ground: the frame context of the latest submission (-1: none, or one that failed half-way), and the tile set's generation
-    // (add_terrain / unload_terrain bump it: a submission rendered with another tile order can no longer be decoded).  The rank ->
-    // (lat, lon) table and the host read's device buffer are made by the first query.
+    // what the frame path leaves for the queries: the frame context of the latest submission (-1: none, or one that failed half-way), and
+    // the tile set's generation (add_terrain / unload_terrain bump it: a submission of another tile order can no longer be decoded)
     int latest_ctx_ = -1;
     uint64_t tile_gen_ = 0;
-    std::vector<int32_t> hz_ll_;                                 // the table's host copy (the source of its upload)
-    uint64_t hz_ll_gen_ = ~0ull;
-    DeviceBuffer d_hz_ll_, d_hz_out_;
-    DeviceBuffer d_hz_check_;             // TOPO_BOUNDS_CHECK build: the queries' bounds record, folded into topo_frame_status
-    DeviceBuffer d_ground_q_, d_ground_out_;      // the ground host read's queries and records
-    // the tiles' f64 sin / cos tables (one entry per column and per row of every tile, draw order: topo_ground.h), made by the first
-    // ground query after the tile set changed -- 38 KB per 1200 x 1200 tile -- and the tile set they were made for
-    DeviceBuffer d_ground_trig_;
-    uint64_t ground_trig_gen_ = ~0ull;
-    // what the horizon and ground queries share: the latest submission if views [first, first + n) of it can be answered, the tables
-    // a query kernel reads, the end of a host read (wait, fold the submission's status), the bounds record of the check build
-    int query_prepare(uint32_t first_view, uint32_t n_views, FrameCtx** c, hipStream_t* s);
-    int ensure_query_check(hipStream_t s);      // the check build's bounds record of the query kernels (the product build: nothing)
-    int query_tables(hipStream_t s);
-    int query_finish_read(FrameCtx& c, hipStream_t s, const char* what);
-    int query_fold_check();
-    int horizon_launch(FrameCtx& c, uint32_t first_view, uint32_t n_views, HorizonPoint* out, size_t view_stride, hipStream_t s);
-    int ground_params(FrameCtx& c, hipStream_t s, GroundParams& p);
-    int ground_tables(hipStream_t s);           // the tiles' f64 tables (and spheres) of the current tile set, rebuilt after it changed
-    // rays: the device copy of the tiles' spheres (kLosSphereDoubles each, draw order; made with d_ground_trig_), the host read's
-    // pinned staging (rays in, records out) and its device buffers
-    DeviceBuffer d_los_spheres_, d_ray_in_, d_ray_out_;
-    PinnedBuffer h_ray_stage_;
-    int ray_params(hipStream_t s, RayParams& p);
 
-    // unwrap: the device copy of k_unwrap's f64 tables (topo_unwrap.h), kept for the parameter set they were built from -- the call's
-    // parameters, the views' direction blocks and the eye (unwrap_key_) -- and their host copy, the source of the upload
-    DeviceBuffer d_unwrap_tab_;
-    std::vector<double> unwrap_tab_;
-    std::vector<uint8_t> unwrap_key_;
+    // ---- the queries (terrain_queries.cpp): the frame path calls tile_spheres (host only) and query_fold_check, and never touches the rest.
+    // Tables made from the tile set, in three levels, each made by the first caller that needs it after the tile set changed.
+    struct TileTables {
+        // the tiles' spheres (kTileSphereDoubles = kLosSphereDoubles each, draw order): host memory, the cull prefilter's and d_spheres' source
+        std::vector<double> spheres;
+        // decode: rank -> (lat, lon), and its host copy (the source of the upload); all a horizon query builds
+        std::vector<int32_t> ll;
+        DeviceBuffer d_ll;
+        // geometry (ground, rays, sunlit): the tiles' f64 sin / cos tables (one entry per column and per row of every tile, draw
+        // order: topo_ground.h; 38 KB per 1200 x 1200 tile; trig_doubles in all) and the device copy of the spheres
+        DeviceBuffer d_trig, d_spheres;
+        size_t trig_doubles = 0;
+        uint64_t spheres_gen = ~0ull, decode_gen = ~0ull, geometry_gen = ~0ull;      // tile_gen_ when each level was made
+    } tables_;
+    enum TableLevel { kDecodeTables, kGeometryTables };
+    const std::vector<double>& tile_spheres();
+    int prepare_tables(TableLevel level, hipStream_t s);      // what a query kernel on s reads, up to `level`: once per public query
+    // The queries' own buffers: the bounds record of every query kernel (TOPO_BOUNDS_CHECK build, folded into topo_frame_status), the
+    // host reads' device buffers (horizon rows; ground queries, records; rays in, records out, their pinned staging), and the device
+    // copy of k_unwrap's f64 tables (topo_unwrap.h), kept for what they were built from -- the call's parameters, the views'
+    // direction blocks and the eye (unwrap_key) -- with their host copy, the source of the upload
+    struct QueryBuffers {
+        DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_unwrap_tab;
+        PinnedBuffer h_ray_stage;
+        std::vector<double> unwrap_tab;
+        std::vector<uint8_t> unwrap_key;
+    } query_;
+    int ensure_query_check(hipStream_t s);      // the check build's bounds record (the product build: nothing)
+    int query_fold_check();
+    // A query on the latest submission: its context, the stream it was queued on (the query goes behind it) and its shape.  begin: if
+    // views [first, first + n) of it can be answered; queued: a device variant's end (the pending mark); finish_read: a host read's.
+    struct LatestSubmission { FrameCtx* c; hipStream_t s; uint32_t W, H, n_views; };
+    int query_begin(uint32_t first_view, uint32_t n_views, LatestSubmission& q);
+    int query_queued(const LatestSubmission& q);
+    int query_finish_read(const LatestSubmission& q, const char* what);
+    int horizon_launch(const LatestSubmission& q, uint32_t first_view, uint32_t n_views, HorizonPoint* out, size_t view_stride);
+    int ground_prepare(const LatestSubmission& q);      // geometry tables + the submission's views on the device
+    GroundParams ground_params(const LatestSubmission& q, uint32_t first_view, uint32_t n_views) const;
+    RayParams ray_params() const;
 
     std::string err_;
 };
