@@ -32,6 +32,13 @@ int topo_debug_far_phase_launched(topo_ctx* ctx, int32_t* out);
 int topo_debug_set_tile_prefilter(topo_ctx* ctx, int32_t on);
 int topo_debug_cull_pairs(topo_ctx* ctx, uint32_t out[2]);
 
+/* Test accessor: the covered regions of the last frame (waits for it).  In the near phase a triangle that covers every pixel of a
+ * 64 x 64 px region inside the target may claim the region; k_raster_cover then writes it with plain stores instead of atomics.
+ * out[0] = items that covered their region (candidates), out[1] = claims won (one per region at most), out[2] = claims lost (the
+ * region was taken: the item went the atomic way).  TOPO_COVER=0 in the environment switches the path off: all three are 0; TOPO_COVER=1 takes it for
+ * every submission (by default only submissions of more than 2^25 pixels take it). */
+int topo_debug_cover_stats(topo_ctx* ctx, uint32_t out[3]);
+
 /* Test accessor: what k_viewshed did since accumulation was first enabled or last reset (waits for the frames in flight):
  * out[0] = terrain keys it read, out[1] = mask-word updates left after combining neighbouring lanes, out[2] = atomics issued
  * (updates that set at least one new bit).  All 0 before accumulation was ever enabled. */

@@ -115,6 +115,7 @@ def lib():
             "topo_debug_far_phase_launched": (C.c_int, [vp, vp]),
             "topo_debug_set_tile_prefilter": (C.c_int, [vp, i32]),
             "topo_debug_cull_pairs": (C.c_int, [vp, vp]),
+            "topo_debug_cover_stats": (C.c_int, [vp, vp]),
             "topo_pin_host_buffer": (C.c_int, [vp, vp, sz]),
             "topo_unpin_host_buffer": (C.c_int, [vp, vp]),
             "topo_get_timings": (C.c_int, [vp, vp]),
@@ -636,6 +637,12 @@ class TerrainRenderer:
         out = np.zeros(2, np.uint32)
         self._check(lib().topo_debug_cull_pairs(self._h, _p(out)))
         return int(out[0]), int(out[1])
+
+    def debug_cover_stats(self) -> dict:
+        """The last frame's covered regions: covering items, claims won, claims lost (include/topo_hip_test.h)."""
+        out = np.zeros(3, np.uint32)
+        self._check(lib().topo_debug_cover_stats(self._h, _p(out)))
+        return {"candidates": int(out[0]), "won": int(out[1]), "lost": int(out[2])}
 
     def timings(self) -> dict:
         out = np.zeros(TIMING_SLOTS, np.float32)

@@ -5,10 +5,11 @@
 //   k_occlusion                     drop the far candidates whose footprint is already covered by nearer depths
 //   k_raster                        one wave per block strip: vertices, small triangles in-wave
 //   k_raster_rare                   the generic exact path: near-clipped triangles and triangles >= 64 px across
+//   k_raster_cover                  one workgroup per region that ONE near-field giant covers whole: plain stores, no atomics
 //   k_raster_big                    one wave per (large triangle, 64 x 64 px region)
 //   k_put_views                     a submission's view constants into their device slot, where k_clear_cull does not carry them
 //
-// Launch order: [k_put_views ->] k_clear_cull (or k_clear -> k_cull) -> [near] k_raster -> k_raster_rare -> k_raster_big -> k_occlusion ->
+// Launch order: [k_put_views ->] k_clear_cull (or k_clear -> k_cull) -> [near] k_raster -> k_raster_rare -> k_raster_cover -> k_raster_big -> k_occlusion ->
 // [far survivors] k_raster -> k_raster_rare -> k_raster_big -> k_resolve (kernels_resolve.h).
 #pragma once
 
@@ -356,10 +357,35 @@ __device__ __forceinline__ void raster_box(const TriSetup& ts, const Vis& vis, i
         }
 }
 
+// A region that one giant covers whole needs no atomics: nobody else's fragment can be lost if the region is written in a launch of
+// its own (k_raster_cover), one lane per pixel taking min(old, mine).  k_raster_rare, in the near phase, asks every item it has room
+// for in the big queue whether it covers its region (setup_covers_region, exact); such an item is flagged kBigCovered and bids for
+// its (view, region): a 64-bit atomicMax of (the frame's serial << 32 | the item's queue index) into the region's owner word.  The
+// atomic returns nothing -- the lane never waits for it (with a returning claim and a list appended through one counter the kernel
+// took 43 instead of 19 us at c4: two trips to memory in every step of the whole-wave region loop) -- and nothing has to be reset
+// between frames: a word of an older serial loses against any bid.  When the kernel is done the word names the region's one winner:
+// k_raster_cover draws it, k_raster_big skips it and draws every other item, the losing bidders among them.
+// The frame keeps no statistics of this: the test hook counts the flagged items and the owner words afterwards, on the host.
+__device__ __forceinline__ uint32_t cover_region_index(const CoverParams& C, uint32_t view, int32_t rx, int32_t ry) {
+    return (view * C.regions_y + (uint32_t)ry) * C.regions_x + (uint32_t)rx;
+}
+__device__ __forceinline__ uint64_t cover_bid(const CoverParams& C, uint32_t big_index) { return ((uint64_t)C.serial << 32) | big_index; }
+__device__ __forceinline__ bool cover_claim(const FrameParams& P, const CoverParams& C, const TriSetup& ts, uint32_t view, int32_t rx, int32_t ry,
+                                            uint32_t big_index) {
+    if (!setup_covers_region(ts, P.W, P.H, rx, ry)) return false;
+    const uint32_t r = cover_region_index(C, view, rx, ry);
+    if (!TOPO_CHK(P.counters, view < P.n_views && (uint32_t)rx < C.regions_x && (uint32_t)ry < C.regions_y && r < C.cap, 30u, r)) return false;
+    atomicMax(reinterpret_cast<unsigned long long*>(C.owner + r), (unsigned long long)cover_bid(C, big_index));
+    return true;
+}
+
 // Hand a triangle whose pixel box is larger than 4x4 to k_raster_big: one BigItem per overlapped 64x64 px
-// region.  Returns false when the queue is full (the caller then rasterises in-lane).
-__device__ bool enqueue_big(const FrameParams& P, uint32_t view, uint32_t id, const SVert& s0, const SVert& s1, const SVert& s2,
-                            int32_t px0, int32_t px1, int32_t py0, int32_t py1) {
+// region.  Returns false when the queue is full (the caller then rasterises in-lane).  view_of(rx, ry, queue index): the word that
+// goes into the item's `view` -- the view itself (k_raster), or the view flagged kBigCovered where the item has bid for its region
+// (k_raster_rare: cover_claim).
+template <typename ViewOf>
+__device__ __forceinline__ bool enqueue_big_items(const FrameParams& P, uint32_t view, uint32_t id, const SVert& s0, const SVert& s1, const SVert& s2,
+                                                  int32_t px0, int32_t px1, int32_t py0, int32_t py1, ViewOf&& view_of) {
     const int32_t rx0 = px0 >> 6, rx1 = px1 >> 6, ry0 = py0 >> 6, ry1 = py1 >> 6;
     const uint32_t n = (uint32_t)((rx1 - rx0 + 1) * (ry1 - ry0 + 1));
     const uint32_t base = atomicAdd(&P.counters[kCtrBig], n);
@@ -381,10 +407,24 @@ __device__ bool enqueue_big(const FrameParams& P, uint32_t view, uint32_t id, co
     for (int32_t ry = ry0; ry <= ry1; ++ry)
         for (int32_t rx = rx0; rx <= rx1; ++rx) {
             it.region = ((uint32_t)ry << 16) | (uint32_t)rx;
-            if (TOPO_CHK(P.counters, k < P.big_cap && rx >= 0 && ry >= 0 && rx * 64 < P.W && ry * 64 < P.H, 7u, k)) P.big[k] = it;
+            if (TOPO_CHK(P.counters, k < P.big_cap && rx >= 0 && ry >= 0 && rx * 64 < P.W && ry * 64 < P.H, 7u, k)) {
+                it.view = view_of(rx, ry, k);
+                P.big[k] = it;
+            }
             ++k;
         }
     return true;
+}
+__device__ bool enqueue_big(const FrameParams& P, uint32_t view, uint32_t id, const SVert& s0, const SVert& s1, const SVert& s2,
+                            int32_t px0, int32_t px1, int32_t py0, int32_t py1) {
+    return enqueue_big_items(P, view, id, s0, s1, s2, px0, px1, py0, py1, [&](int32_t, int32_t, uint32_t) { return view; });
+}
+// k_raster_rare's: `ts` is the triangle's setup
+__device__ bool enqueue_big_cover(const FrameParams& P, const CoverParams& C, const TriSetup& ts, uint32_t view, uint32_t id, const SVert& s0, const SVert& s1,
+                                  const SVert& s2) {
+    return enqueue_big_items(P, view, id, s0, s1, s2, ts.px0, ts.px1, ts.py0, ts.py1, [&](int32_t rx, int32_t ry, uint32_t k) {
+        return C.serial && cover_claim(P, C, ts, view, rx, ry, k) ? view | kBigCovered : view;
+    });
 }
 
 // Triangles the lean kernel does not handle go to k_raster_rare.
@@ -646,8 +686,10 @@ __global__ __launch_bounds__(256, TOPO_RASTER_WAVES) void k_raster(FrameParams P
 // over the regions of a triangle that covers a good part of the target (the near field's largest, cut by the near plane: a thousand
 // regions and more) was this kernel's duration -- ~20 instructions per region on ONE lane, while the other 15 000 triangles had long
 // been done.
+// `C`: the near phase's launch lets covering items bid for their regions (C.serial != 0; cover_claim), only after their queue reservation
+// has succeeded; the far phase's launch and a frame with the path switched off pass serial 0.
 constexpr uint32_t kCoopRegions = 24;
-__global__ __launch_bounds__(256) void k_raster_rare(FrameParams P) {
+__global__ __launch_bounds__(256) void k_raster_rare(FrameParams P, CoverParams C) {
     uint32_t count = P.counters[kCtrRare];
     if (count > P.rare_cap) count = P.rare_cap;
     const uint32_t lane = threadIdx.x & 63;
@@ -667,7 +709,7 @@ __global__ __launch_bounds__(256) void k_raster_rare(FrameParams P) {
             const uint32_t rw = (uint32_t)(rx1 - rx0 + 1), n_regions = rw * (uint32_t)(ry1 - ry0 + 1);
             const bool coop = has && !small && n_regions >= kCoopRegions && rw <= 256u;
             bool in_lane = has && small;      // rasterised by this lane itself: boxes up to 4 x 4 px, and whatever the queue has no room for
-            if (has && !small && !coop) in_lane = !enqueue_big(P, ri.view, id, r.s[0], r.s[1], r.s[2], ts.px0, ts.px1, ts.py0, ts.py1);
+            if (has && !small && !coop) in_lane = !enqueue_big_cover(P, C, ts, ri.view, id, r.s[0], r.s[1], r.s[2]);
             // ---- the wave's large jobs, one after the other, every lane that is still in this loop taking part
             uint64_t jobs = __ballot(coop);
             if (jobs) {
@@ -698,16 +740,96 @@ __global__ __launch_bounds__(256) void k_raster_rare(FrameParams P) {
                         for (uint32_t k = mine; k < n && base + k < P.big_cap; k += n_act) P.big[base + k] = it;
                         continue;
                     }
+                    // the job's setup again, from its wave-uniform vertices (scalar registers), for the lanes' claims
+                    TriSetup jts;
+                    bool jcover = false;
+                    if (C.serial) {
+                        SVert q[3];
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) { q[k].X = it.X[k]; q[k].Y = it.Y[k]; q[k].z = it.z[k]; q[k].flag = kVtxOk; }
+                        jcover = triangle_setup(q[0], q[1], q[2], P.W, P.H, jts);
+                    }
+                    const uint32_t jview = it.view;
                     const uint32_t magic = region_split_magic(jw);
                     for (uint32_t k = mine; k < n; k += n_act) {
                         const uint32_t q = region_split_row(k, jw, n, magic);
                         const int32_t ry = jy0 + (int32_t)q, rx = jx0 + (int32_t)(k - q * jw);
                         it.region = ((uint32_t)ry << 16) | (uint32_t)rx;
-                        if (TOPO_CHK(P.counters, base + k < P.big_cap && rx >= 0 && ry >= 0 && rx * 64 < P.W && ry * 64 < P.H, 7u, base + k)) P.big[base + k] = it;
+                        if (TOPO_CHK(P.counters, base + k < P.big_cap && rx >= 0 && ry >= 0 && rx * 64 < P.W && ry * 64 < P.H, 7u, base + k)) {
+                            it.view = jcover && cover_claim(P, C, jts, jview, rx, ry, base + k) ? jview | kBigCovered : jview;
+                            P.big[base + k] = it;
+                        }
                     }
                 }
             }
             if (in_lane) raster_box(ts, vis, P.W, id, ts.px0, ts.px1, ts.py0, ts.py1);
+        }
+    }
+}
+
+// One workgroup per claimed region at a time: a near-field giant that covers its 64 x 64 px region (the part inside the target) and
+// has won it, so this launch -- behind k_raster and k_raster_rare, in front of k_raster_big -- has ONE writer per pixel of the region
+// and needs no atomics: key = min(old, mine) with a plain load and a plain store.  Workgroup b reads region b's owner word and is done
+// unless it carries this frame's serial (three regions in four at c4; with 16 regions per workgroup, drawn one after the other, the
+// kernel took 50 instead of 29 us: a region is three dependent trips to memory).  A wave takes 16 rows, a lane a pixel column (512
+// contiguous bytes per row and wave).  The rows' segment marks are read first: a row none of whose segments is marked has not been
+// touched since the clear, its keys are kVisClear and the store alone suffices; the marked rows' keys are loaded, all of them in
+// flight before the walk uses the first.  (A neighbouring region's workgroup may be marking a shared segment meanwhile: read as 0 or
+// as 1, the result is the same -- the neighbour writes none of this region's pixels.)  Plain stores, not non-temporal ones: k_raster_big
+// and k_resolve read the keys again soon.  The walk is big_cover_lane (topo_pipeline.h), run lane by lane on the CPU in the tests.
+constexpr int kCoverRows = 16;
+__global__ __launch_bounds__(256) void k_raster_cover(FrameParams P, CoverParams C) {
+    const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t view_keys = (size_t)P.W * P.H, nseg = ((size_t)P.n_views * view_keys + 63) >> 6;
+    (void)nseg;      // (the check build's)
+    const uint32_t region = blockIdx.x;      // (the grid is C.cap workgroups)
+    const uint64_t word = *const_space(C.owner + region);      // written by k_raster_rare, a launch ago: the scalar data path
+    for (bool won = (uint32_t)(word >> 32) == C.serial; won; won = false) {
+        const uint32_t item = (uint32_t)word;
+        if (!TOPO_CHK(P.counters, region < C.cap && item < P.big_cap, 32u, item)) continue;
+        BigItem bi;
+        {
+            const BigItem& g = P.big[item];
+            bi.view = wave_first(g.view); bi.id = wave_first(g.id); bi.region = wave_first(g.region);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { bi.X[k] = wave_first(g.X[k]); bi.Y[k] = wave_first(g.Y[k]); bi.z[k] = wave_first(g.z[k]); }
+        }
+        const uint32_t view = bi.view & ~kBigCovered;
+        const int32_t rx = (int32_t)(bi.region & 0xFFFFu), ry = (int32_t)(bi.region >> 16);
+        if (!TOPO_CHK(P.counters, (bi.view & kBigCovered) && bi.id != kNoTri && view < P.n_views && rx * 64 < P.W && ry * 64 < P.H &&
+                                      cover_region_index(C, view, rx, ry) == region, 33u, bi.region)) continue;
+        SVert s[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { s[k].X = bi.X[k]; s[k].Y = bi.Y[k]; s[k].z = bi.z[k]; s[k].flag = kVtxOk; }
+        TriSetup ts;
+        if (!triangle_setup(s[0], s[1], s[2], P.W, P.H, ts)) continue;
+        const bool narrow = giant_narrow(bi.X, bi.Y);
+        const Vis vis = view_vis(P, view);
+        const int32_t row0 = (int32_t)wave * kCoverRows, y0 = ry * 64 + row0, x0 = rx * 64, x1 = min(x0 + 63, P.W - 1);
+        if (y0 >= P.H) continue;      // (the region is cut by the image's lower edge above this wave's rows)
+        // lane j < 16: the marks of row j's segment(s) -- one, or two when W or the view origin is not a multiple of 64
+        const bool row = lane < (uint32_t)kCoverRows && y0 + (int32_t)lane < P.H;
+        const size_t first = (size_t)(vis.p - vis.base) + (size_t)(y0 + (int32_t)(row ? lane : 0u)) * P.W;
+        const size_t s0 = (first + x0) >> 6, s1 = (first + x1) >> 6;
+        const bool row_ok = row && TOPO_CHK(P.counters, s1 < nseg, 34u, s1);
+        const bool marked = row_ok && (vis.dirty[s0] | vis.dirty[s1]) != 0;
+        const uint32_t marked_rows = (uint32_t)__ballot(marked);      // bit j: row j holds somebody's keys
+        const int32_t px = x0 + (int32_t)lane;
+        uint64_t old[kCoverRows];
+#pragma unroll
+        for (int j = 0; j < kCoverRows; ++j) {
+            old[j] = kVisClear;
+            if ((marked_rows >> j & 1u) && px < P.W) {
+                const size_t pix = (size_t)(y0 + j) * P.W + px;
+                if (TOPO_CHK(P.counters, y0 + j < P.H && pix < view_keys, 35u, pix)) old[j] = vis.p[pix];
+            }
+        }
+        big_cover_lane<kCoverRows>(ts, narrow, bi.id, P.W, P.H, rx, ry, row0, lane, [&](size_t pix, uint64_t key, int j) {
+            if (TOPO_CHK(P.counters, pix < view_keys, 36u, pix)) vis.p[pix] = key < old[j] ? key : old[j];
+        });
+        if (row_ok) {
+            vis.dirty[s0] = 1;
+            if (s1 != s0) vis.dirty[s1] = 1;
         }
     }
 }
@@ -718,7 +840,7 @@ __global__ __launch_bounds__(256) void k_raster_rare(FrameParams P) {
 // form of the same integers (big_medium_lane), the giants that come through k_raster_rare the int64 form
 // (big_giant_lane); both are in topo_pipeline.h and run lane by lane on the CPU in the tests.  Fragments are issued
 // blind (no depth pre-test, see vis_min): only entries that carry a fragment (key != kVisClear) are dereferenced.
-__global__ __launch_bounds__(256) void k_raster_big(FrameParams P) {
+__global__ __launch_bounds__(256) void k_raster_big(FrameParams P, CoverParams C) {
     // Segment marks: an item stays inside one 64 x 64 px region, i.e. inside 64 pixel rows of one or two 64-key segments
     // each.  Instead of one mark store beside every atomic instruction (half of this kernel's memory instructions), the
     // lanes note the rows they hit in LDS and lane r marks row r's segment(s) once per item.
@@ -740,8 +862,15 @@ __global__ __launch_bounds__(256) void k_raster_big(FrameParams P) {
             for (int k = 0; k < 3; ++k) { bi.X[k] = wave_first(g.X[k]); bi.Y[k] = wave_first(g.Y[k]); bi.z[k] = wave_first(g.z[k]); }
         }
         if (bi.id == kNoTri) continue;
-        const Vis vis = view_vis(P, bi.view);
         const int32_t rx = (int32_t)(bi.region & 0xFFFFu), ry = (int32_t)(bi.region >> 16);
+        if (bi.view & kBigCovered) {      // a covering item: if its bid won the region, k_raster_cover has drawn it
+            bi.view &= ~kBigCovered;
+            const uint32_t r = cover_region_index(C, bi.view, rx, ry);
+            if (C.serial != 0u && TOPO_CHK(P.counters, bi.view < P.n_views && rx * 64 < P.W && ry * 64 < P.H && r < C.cap, 31u, r) &&
+                *const_space(C.owner + r) == cover_bid(C, item))
+                continue;
+        }
+        const Vis vis = view_vis(P, bi.view);
         if (!TOPO_CHK(P.counters, bi.view < P.n_views && rx * 64 < P.W && ry * 64 < P.H, 11u, bi.region)) continue;
         uint8_t* const rows = s_rows[wave];
         if (spans_fit_int32(bi.X[0], bi.Y[0], bi.X[1], bi.Y[1], bi.X[2], bi.Y[2])) {

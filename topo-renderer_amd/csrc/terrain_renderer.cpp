@@ -25,6 +25,7 @@ struct Switches {
     const bool fuse_clear_cull = env("TOPO_FUSE_CLEAR_CULL", 1) != 0;
     const bool tile_prefilter = env("TOPO_TILE_PREFILTER", 1) != 0;
     const int near_strip = env("TOPO_NEAR_STRIP", 0);      // 1..15; anything else: the default
+    const int cover = env("TOPO_COVER", -1);      // 0: off, 1: on for every submission; unset: on for the large ones (kCoverMinPixels)
 };
 const Switches& switches() { static const Switches s; return s; }
 
@@ -575,6 +576,25 @@ int TerrainRenderer::grow_frame_buffers(FrameCtx& c, hipStream_t stream, uint32_
     if (int rc = ensure(stream, c.d_far, (far_sub_cap ? far_sub_cap * kFarLists : 1) * sizeof(FarItem))) return rc;
     if (int rc = ensure(stream, c.d_big, p.big_cap * sizeof(BigItem))) return rc;
     if (int rc = ensure(stream, c.d_rare, p.rare_cap * sizeof(RareItem))) return rc;
+    // covered regions (CoverParams): a 64-bit owner word per (view, 64 x 64 px region).  A fresh table is zeroed -- older than any
+    // serial -- and so is the table when the context's serial wraps.
+    c.cover = CoverParams{};
+    // The path costs a launch over every region and the claims' arithmetic in k_raster_rare whatever the submission's size, and
+    // saves in proportion to its terrain pixels: by default it is taken where it was measured to pay, above kCoverMinPixels (the
+    // c4 panorama's 67 M pixels: profiles/cover_regions_ab.txt); smaller submissions keep the atomic way.
+    constexpr size_t kCoverMinPixels = (size_t)1 << 25;
+    if (p.n_tiles && (switches().cover > 0 || (switches().cover < 0 && pixels > kCoverMinPixels))) {
+        const uint32_t regions_x = (w + 63) / 64, regions_y = (h + 63) / 64;
+        const size_t regions = (size_t)n * regions_x * regions_y;      // < 2^32 / 4096 words
+        const bool fresh = regions * sizeof(uint64_t) > c.d_cover.cap;
+        if (int rc = ensure(stream, c.d_cover, regions * sizeof(uint64_t))) return rc;
+        if (fresh || c.cover_serial == 0xFFFFFFFFu) {
+            TOPO_HIP_TRY(hipMemsetAsync(c.d_cover.p, 0, c.d_cover.cap, stream));
+            c.cover_serial = 0;
+        }
+        c.cover = CoverParams{c.d_cover.as<uint64_t>(), ++c.cover_serial, (uint32_t)regions, regions_x, regions_y};
+        c.cover_big_cap = p.big_cap;
+    }
     if (!c.d_counters.p) {
         if (int rc = ensure(stream, c.d_counters, 2 * kCounterWords * sizeof(uint32_t))) return rc;      // two sets, alternating
         TOPO_HIP_TRY(hipMemsetAsync(c.d_counters.p, 0, 2 * kCounterWords * sizeof(uint32_t), stream));
@@ -713,16 +733,17 @@ int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p
     TOPO_HIP_TRY(mark(kStRasterNear));
     launch_raster(p, 0, stream);
     TOPO_HIP_TRY(mark(kStRareBigNear));
-    launch_raster_rare(p, stream);
-    launch_raster_big(p, stream);
+    launch_raster_rare(p, c.cover, stream);
+    launch_raster_cover(p, c.cover, stream);      // the regions one giant covers whole, with plain stores; the rest: k_raster_big's atomics
+    launch_raster_big(p, c.cover, stream);
     TOPO_HIP_TRY(mark(kStOcclusion));
     if (far_phase) launch_occlusion(p, stream);
     TOPO_HIP_TRY(mark(kStRasterFar));
     if (far_phase) launch_raster(p, 1, stream);
     TOPO_HIP_TRY(mark(kStRareBigFar));
     if (far_phase) {
-        launch_raster_rare(p, stream);
-        launch_raster_big(p, stream);
+        launch_raster_rare(p, CoverParams{}, stream);
+        launch_raster_big(p, CoverParams{}, stream);
     }
     TOPO_HIP_TRY(mark(kStResolve, true));
     const hipEvent_t ev_rstart = own(kStResolve), ev_rstop = own(kNumStages);
@@ -1148,6 +1169,27 @@ int TerrainRenderer::get_counters(uint32_t out[6]) {
     }
     static_assert(kCtrWork == 0 && kCtrFarSurvived == 5, "topo_get_counters hands out words kCtrWork .. kCtrFarSurvived");
     for (uint32_t i = kCtrWork; i <= kCtrFarSurvived; ++i) out[i] = c[i];
+    return TOPO_OK;
+}
+
+int TerrainRenderer::cover_stats(uint32_t out[3]) {
+    out[0] = out[1] = out[2] = 0;
+    FrameCtx& fc = ctx_[last_ctx_];
+    if (!fc.h_status.p || !fc.submitted) return TOPO_OK;
+    if (int rc = bind_device()) return rc;
+    if (fc.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(fc.last_stream));
+    // The frame itself counts nothing (a counter every claim goes through would be thousands of atomics on one address): the
+    // covering items are the flagged entries of the frame's part of the big queue, the claims won the owner words of its serial.
+    const CoverParams& cv = fc.cover;
+    if (!cv.serial) return TOPO_OK;
+    const uint32_t n_big = std::min(fc.latest_status()[kCtrBig], fc.cover_big_cap);
+    std::vector<BigItem> items(n_big);
+    std::vector<uint64_t> owner(cv.cap);
+    if (n_big) TOPO_HIP_TRY(hipMemcpy(items.data(), fc.d_big.p, n_big * sizeof(BigItem), hipMemcpyDeviceToHost));
+    if (cv.cap) TOPO_HIP_TRY(hipMemcpy(owner.data(), cv.owner, cv.cap * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (const BigItem& it : items) out[0] += it.id != kNoTri && (it.view & kBigCovered) ? 1u : 0u;
+    for (uint64_t w : owner) out[1] += (uint32_t)(w >> 32) == cv.serial ? 1u : 0u;
+    out[2] = out[0] - out[1];      // every covering item either wins its region or loses it to another one
     return TOPO_OK;
 }
 

@@ -133,6 +133,7 @@ class TerrainRenderer {
     int get_timings(float out[TOPO_TIMING_SLOTS]);
     int get_timing_history(uint32_t n_frames, float* out_ms, uint32_t* n_out);
     int get_counters(uint32_t out[6]);
+    int cover_stats(uint32_t out[3]);      // test hook: the last frame's covering items, regions claimed, claims lost
     int frame_status(uint32_t out[4]);
     int set_occlusion_split(float metres);
     int set_timing_slots(uint32_t mask);
@@ -252,6 +253,10 @@ class TerrainRenderer {
         const uint32_t* latest_status() const { return status_words(submitted - 1); }
         DeviceBuffer d_vis, d_dirty;      // d_dirty: one mark per 64 visibility keys (kernels_common.h: struct Vis)
         DeviceBuffer d_work, d_work2, d_far, d_big, d_rare, d_counters;
+        DeviceBuffer d_cover;             // the regions' owner words (topo_kernels.h: CoverParams)
+        uint32_t cover_serial = 0;        // the serial the context's latest frame claimed regions with
+        CoverParams cover{};              // this frame's; serial 0: the path is off
+        uint32_t cover_big_cap = 0;       // ... and its big queue's capacity (the test hook reads the queue back)
         DeviceBuffer d_pre_rgba, d_pre_depth;      // the pixelise branch: the render-target image k_post_pixelize samples, and a depth image when the caller wants none
         // the context's latest submission as the queries read it (its keys and marks are d_vis / d_dirty until the next one)
         struct Submission {

@@ -147,6 +147,12 @@ int topo_debug_cull_pairs(topo_ctx* ctx, uint32_t out[2]) {
     return TOPO_OK;
 }
 
+int topo_debug_cover_stats(topo_ctx* ctx, uint32_t out[3]) {
+    TOPO_GUARD(ctx);
+    if (!out) return TOPO_ERR_INVALID;
+    TOPO_CALL(ctx->r->cover_stats(out));
+}
+
 int topo_get_timings(topo_ctx* ctx, float out_ms[TOPO_TIMING_SLOTS]) {
     TOPO_GUARD(ctx);
     TOPO_CALL(ctx->r->get_timings(out_ms));

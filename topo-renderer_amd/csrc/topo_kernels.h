@@ -34,7 +34,7 @@ struct FarItem {           // a frustum-surviving block beyond the occlusion spl
 };
 
 struct BigItem {           // a triangle too large for the in-lane loop, restricted to one 64x64 px region
-    uint32_t view;
+    uint32_t view;         // bit 31 (kBigCovered): the item covers its region and has bid for it -- k_raster_cover draws the winner, k_raster_big the others
     uint32_t id;           // draw << 1 | fan   (kNoTri = empty slot)
     uint32_t region;       // ry << 16 | rx  (64 px units)
     int32_t X[3], Y[3];    // the snapped vertices: the consumer re-runs the exact integer setup on them
@@ -82,6 +82,17 @@ struct FrameParams {
     FastDiv div_rblocks_x, div_rblocks_view;
 };
 
+// Regions one near-field giant covers whole (k_raster_rare bids for them, k_raster_cover writes them with plain stores).  Per frame
+// context: `owner`, one 64-bit word per (view, 64 x 64 px region) of the submission -- the largest bid so far, serial of the frame
+// << 32 | big-queue index of the bidding item (atomicMax: a word of an older frame loses against any bid, so nothing has to be
+// reset between frames).  serial == 0: the path is off.
+struct CoverParams {
+    uint64_t* owner;
+    uint32_t serial;
+    uint32_t cap;              // words of owner: n_views * regions_x * regions_y
+    uint32_t regions_x, regions_y;
+};
+
 struct OutputParams {
     uint8_t* rgba;             // device pointer
     size_t rgba_view_stride, rgba_pitch;   // bytes
@@ -94,6 +105,7 @@ constexpr uint32_t kStatusRareOverflow = 2u;   // rare-triangle queue full: tria
 constexpr uint32_t kFarLists = 64;             // the far-candidate list is kept as 64 sub-lists, each with a counter on a cache line of its own
 constexpr uint32_t kStatusWords = 16;          // queue counters and status words of one frame: what reaches the host (the status ring)
 constexpr uint32_t kCounterWords = kStatusWords + 16 * kFarLists;      // ... then the sub-list counters, each on a cache line of its own
+constexpr uint32_t kBigCovered = 0x80000000u;   // BigItem::view flag (a submission holds far fewer views)
 constexpr uint32_t kStatusBounds = 4u;         // TOPO_BOUNDS_CHECK build only: an out-of-range index was formed (and not used);
                                                // kCtrBoundsTag = site tag, kCtrBoundsLo / Hi = the offending value
 // the words of a counter set
@@ -152,8 +164,9 @@ void launch_cull(const FrameParams& p, hipStream_t s, const uint16_t* pairs = nu
 size_t cull_workgroups_max(uint32_t n_views, uint32_t n_tiles, uint32_t blocks_per_tile);
 void launch_raster(const FrameParams& p, int phase, hipStream_t s);   // phase 0: near list, 1: far survivors
 void launch_occlusion(const FrameParams& p, hipStream_t s);
-void launch_raster_rare(const FrameParams& p, hipStream_t s);
-void launch_raster_big(const FrameParams& p, hipStream_t s);
+void launch_raster_rare(const FrameParams& p, const CoverParams& cover, hipStream_t s);      // cover.serial != 0 (the near phase only): covering items bid for their regions
+void launch_raster_cover(const FrameParams& p, const CoverParams& cover, hipStream_t s);     // between the near phase's launch_raster_rare and launch_raster_big
+void launch_raster_big(const FrameParams& p, const CoverParams& cover, hipStream_t s);          // cover: the near phase's, as passed to launch_raster_rare
 void launch_resolve(const FrameParams& p, const OutputParams& o, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // viewshed (topo_viewshed_*), behind the frame's last k_resolve: the DEM cells that won a pixel, OR-ed into per-tile bit masks.

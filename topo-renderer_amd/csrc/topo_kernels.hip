@@ -3,13 +3,13 @@
 //
 //   kernels_common.h    the visibility buffer's key and marks, the bounds-check build, wave helpers
 //   kernels_load.h      load phase (once per add_terrain): block tables, sin/cos tables, cull bounds, normals
-//   kernels_frame.h     frame phase: view constants, clear, cull, occlusion filter, the three raster kernels
+//   kernels_frame.h     frame phase: view constants, clear, cull, occlusion filter, the raster kernels
 //   kernels_resolve.h   k_resolve: shading of each pixel's winner + the post pass
 //   kernels_query.h     viewshed, horizon and ground points, over a finished frame's visibility buffer; the unwrap of finished images
 //   kernels_overlay.h   pixelise post pass, line / glyph overlays, visible peaks
 //   kernels_tiff.h      GeoTIFF rows, unit-test probes
 //
-// A frame:  [k_put_views ->] k_clear_cull (or k_clear -> k_cull) -> [near] k_raster -> k_raster_rare -> k_raster_big ->
+// A frame:  [k_put_views ->] k_clear_cull (or k_clear -> k_cull) -> [near] k_raster -> k_raster_rare -> k_raster_cover -> k_raster_big ->
 //           [k_occlusion -> [far survivors] k_raster -> k_raster_rare -> k_raster_big ->] k_resolve (one launch or several)
 //           [-> k_post_pixelize] [-> k_viewshed]
 // A load:   k_trig_tables -> k_normals_rolling<.., true> -> k_block_bounds, or k_block_tables -> k_normals_interior /
@@ -205,15 +205,20 @@ void launch_occlusion(const FrameParams& p, hipStream_t s) {
     hipLaunchKernelGGL(k_occlusion, dim3(grid), dim3(256), 0, s, p);
 }
 
-void launch_raster_rare(const FrameParams& p, hipStream_t s) {
+void launch_raster_rare(const FrameParams& p, const CoverParams& cover, hipStream_t s) {
     if (p.n_tiles == 0) return;
-    hipLaunchKernelGGL(k_raster_rare, dim3(256), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_raster_rare, dim3(256), dim3(256), 0, s, p, cover);
 }
 
-void launch_raster_big(const FrameParams& p, hipStream_t s) {
+void launch_raster_cover(const FrameParams& p, const CoverParams& cover, hipStream_t s) {
+    if (p.n_tiles == 0 || cover.serial == 0 || cover.cap == 0) return;
+    hipLaunchKernelGGL(k_raster_cover, dim3(cover.cap), dim3(256), 0, s, p, cover);      // a workgroup per region: most find theirs unclaimed and end
+}
+
+void launch_raster_big(const FrameParams& p, const CoverParams& cover, hipStream_t s) {
     if (p.n_tiles == 0) return;
     const unsigned grid = resident_grid<2>(k_raster_big, 256 * 4);
-    hipLaunchKernelGGL(k_raster_big, dim3(grid), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(k_raster_big, dim3(grid), dim3(256), 0, s, p, cover);
 }
 
 void launch_resolve(const FrameParams& p, const OutputParams& o, hipStream_t s, hipEvent_t start, hipEvent_t stop) {

@@ -388,6 +388,29 @@ TOPO_HD void big_medium_lane(const int32_t X[3], const int32_t Y[3], const float
     }
 }
 
+// Depth of a giant's pixel from its two unbiased edge functions U1, U2 (barycentric numerators, in [0, |area2|] for a covered
+// pixel): below 2^48 (`narrow`: any triangle under ~46000 px across) the int64 -> f32 conversion is one fma of two exact 24-bit
+// halves, the same single rounding.  False: the far plane clips the pixel.  One function for big_giant_lane and big_cover_lane,
+// so that the two cannot drift apart by a bit.
+TOPO_HD bool giant_narrow(const int32_t X[3], const int32_t Y[3]) {
+    return -((X[1] - (int64_t)X[0]) * (Y[2] - (int64_t)Y[0]) - (Y[1] - (int64_t)Y[0]) * (X[2] - (int64_t)X[0])) < (1ll << 48);
+}
+TOPO_HD bool giant_depth(const TriSetup& ts, bool narrow, int64_t U1, int64_t U2, float& z) {
+    float f1, f2;
+    if (narrow) {
+        f1 = fmaf((float)(int32_t)(U1 >> 24), 16777216.0f, (float)(int32_t)((uint32_t)U1 & 0xFFFFFFu));
+        f2 = fmaf((float)(int32_t)(U2 >> 24), 16777216.0f, (float)(int32_t)((uint32_t)U2 & 0xFFFFFFu));
+    } else {
+        f1 = (float)U1;
+        f2 = (float)U2;
+    }
+    float zz = fmaf(f1 * ts.iA, ts.dz1, fmaf(f2 * ts.iA, ts.dz2, ts.z0));
+    if (!(zz < 1.0f)) return false;
+    if (zz < 0.0f) zz = 0.0f;
+    z = zz;
+    return true;
+}
+
 // k_raster_big, giants (a vertex pair >= 64 px apart): the 64-bit edge functions of triangle_setup, evaluated once per
 // lane at its pixel of the first 8x8 sub-chunk of region (rx, ry) and then stepped (8 px in x: + 2048 dy, 8 px in y:
 // - 2048 dx), so a sub-chunk costs three 64-bit additions instead of six 64-bit multiplications.  emit(pixel index, key, py).
@@ -410,9 +433,7 @@ TOPO_HD void big_giant_lane(const int32_t X[3], const int32_t Y[3], const float 
     int64_t Fr2 = ts.dy[2] * (cx - ts.ax[2]) - ts.dx[2] * (cy - ts.ay[2]) + ts.bias[2];
     const int64_t ax0 = ts.dy[0] * 2048, ax1 = ts.dy[1] * 2048, ax2 = ts.dy[2] * 2048;
     const int64_t ay0 = ts.dx[0] * 2048, ay1 = ts.dx[1] * 2048, ay2 = ts.dx[2] * 2048;
-    // barycentric numerators of covered pixels are in [0, |area2|]: below 2^48 (any triangle under ~46000 px
-    // across) the int64 -> f32 conversion is one fma of two exact 24-bit halves, the same single rounding
-    const bool narrow = -((X[1] - (int64_t)X[0]) * (Y[2] - (int64_t)Y[0]) - (Y[1] - (int64_t)Y[0]) * (X[2] - (int64_t)X[0])) < (1ll << 48);
+    const bool narrow = giant_narrow(X, Y);
     const int32_t b1 = (int32_t)ts.bias[1], b2 = (int32_t)ts.bias[2];
     for (int32_t sy = sy0; sy <= by1; sy += 8) {
         int64_t F0 = Fr0, F1 = Fr1, F2 = Fr2;
@@ -421,24 +442,66 @@ TOPO_HD void big_giant_lane(const int32_t X[3], const int32_t Y[3], const float 
         for (int32_t sx = sx0; sx <= bx1; sx += 8) {
             const int32_t px = sx + lx;
             if (rowin && px >= bx0 && px <= bx1 && (F0 | F1 | F2) >= 0) {
-                const int64_t U1 = F1 - b1, U2 = F2 - b2;
-                float f1, f2;
-                if (narrow) {
-                    f1 = fmaf((float)(int32_t)(U1 >> 24), 16777216.0f, (float)(int32_t)((uint32_t)U1 & 0xFFFFFFu));
-                    f2 = fmaf((float)(int32_t)(U2 >> 24), 16777216.0f, (float)(int32_t)((uint32_t)U2 & 0xFFFFFFu));
-                } else {
-                    f1 = (float)U1;
-                    f2 = (float)U2;
-                }
-                float z = fmaf(f1 * ts.iA, ts.dz1, fmaf(f2 * ts.iA, ts.dz2, ts.z0));
-                if (z < 1.0f) {
-                    if (z < 0.0f) z = 0.0f;
-                    emit((size_t)py * W + px, vis_key(z, id), py);
-                }
+                float z;
+                if (giant_depth(ts, narrow, F1 - b1, F2 - b2, z)) emit((size_t)py * W + px, vis_key(z, id), py);
             }
             F0 += ax0; F1 += ax1; F2 += ax2;
         }
         Fr0 -= ay0; Fr1 -= ay1; Fr2 -= ay2;
+    }
+}
+
+// ---- regions one giant covers whole (k_raster_rare's claim, k_raster_cover) -----------------------------------------------
+// Does the triangle cover EVERY pixel of region (rx, ry) (64 px units) that lies inside the target?  Exact integers: true iff
+// the triangle's clipped pixel box contains the region's box [x0, x1] x [y0, y1] (the region cut by the image edge) and all three
+// biased edge functions are >= 0 at the box's four corner pixel centres.  An edge function is affine, so its minimum over the
+// four corners is taken at ONE of them, which the signs of dy and dx name: that corner is the one evaluated, and every pixel
+// centre between the corners is covered too (triangle_pixel's far-plane test is not part of this: it is the walk's).
+TOPO_HD bool setup_covers_region(const TriSetup& ts, int32_t W, int32_t H, int32_t rx, int32_t ry) {
+    const int32_t x0 = rx * 64, y0 = ry * 64;
+    const int32_t x1 = x0 + 63 < W - 1 ? x0 + 63 : W - 1, y1 = y0 + 63 < H - 1 ? y0 + 63 : H - 1;
+    if (rx < 0 || ry < 0 || x0 > x1 || y0 > y1) return false;
+    if (ts.px0 > x0 || ts.px1 < x1 || ts.py0 > y0 || ts.py1 < y1) return false;
+    bool in = true;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        // F(cx, cy) = dy (cx - ax) - dx (cy - ay) is smallest at the left column when dy >= 0 and at the bottom row when dx >= 0
+        const int64_t cx = (int64_t)(ts.dy[e] >= 0 ? x0 : x1) * 256 + 128, cy = (int64_t)(ts.dx[e] >= 0 ? y1 : y0) * 256 + 128;
+        in = in && ts.dy[e] * (cx - ts.ax[e]) - ts.dx[e] * (cy - ts.ay[e]) + ts.bias[e] >= 0;
+    }
+    return in;
+}
+TOPO_HD bool item_covers_region(const int32_t X[3], const int32_t Y[3], int32_t W, int32_t H, int32_t rx, int32_t ry) {
+    SVert s[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { s[k].X = X[k]; s[k].Y = Y[k]; s[k].z = 0.0f; s[k].flag = kVtxOk; }
+    TriSetup ts;
+    return triangle_setup(s[0], s[1], s[2], W, H, ts) && setup_covers_region(ts, W, H, rx, ry);
+}
+
+// k_raster_cover: the pixel walk of a triangle that covers region (rx, ry) (setup_covers_region) -- no edge tests.  Lane `lane`
+// owns pixel column rx * 64 + lane and walks the kRows rows from ry * 64 + row0 down; the depth is big_giant_lane's
+// (giant_depth of the same two integers, stepped by exact 64-bit additions: one row down = - 256 dx).  emit(pixel index, key,
+// row - first row) exactly once per pixel of those rows inside the target with z < 1; nothing outside the target, whatever the
+// triangle.
+template <int kRows, typename Emit>
+TOPO_HD void big_cover_lane(const TriSetup& ts, bool narrow, uint32_t id, int32_t W, int32_t H, int32_t rx, int32_t ry, int32_t row0,
+                            uint32_t lane, Emit&& emit) {
+    const int32_t px = rx * 64 + (int32_t)lane, py0 = ry * 64 + row0;
+    if (rx < 0 || ry < 0 || row0 < 0 || lane >= 64u || px >= W) return;
+    const int64_t cx = (int64_t)px * 256 + 128, cy = (int64_t)py0 * 256 + 128;
+    int64_t U1 = ts.dy[1] * (cx - ts.ax[1]) - ts.dx[1] * (cy - ts.ay[1]);
+    int64_t U2 = ts.dy[2] * (cx - ts.ax[2]) - ts.dx[2] * (cy - ts.ay[2]);
+    const int64_t s1 = ts.dx[1] * 256, s2 = ts.dx[2] * 256;
+    size_t pix = (size_t)py0 * W + px;
+#pragma unroll
+    for (int j = 0; j < kRows; ++j) {
+        if (py0 + j < H) {
+            float z;
+            if (giant_depth(ts, narrow, U1, U2, z)) emit(pix, vis_key(z, id), j);
+        }
+        U1 -= s1; U2 -= s2;
+        pix += (size_t)W;
     }
 }
 
