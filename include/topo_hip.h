@@ -439,6 +439,61 @@ int topo_sunlit_map_device(topo_ctx* ctx, uint32_t first_view, uint32_t n_views,
  * (up = the geocentric radius).  The direction towards the sun for a ray from the ground, for one. */
 void topo_sun_direction(double lon_deg, double lat_deg, double az_deg, double el_deg, double dir_out[3]);
 
+/* ---- surface: the drawn terrain under a longitude and latitude -- points, grids and profiles -----------------------------------
+ * "How high is the drawn terrain at this longitude and latitude?"  The mesh is that of the rays.  A triangle exists for these
+ * queries iff each of its three vertex heights is finite, < 1e9 and > -R0 (only then does every vertex lie over its own longitude
+ * and latitude); finite sentinel heights are geometry, as in the frame.  For the unit direction u of (lon, lat) the line is
+ * origin R0 u, direction u, so that t is the height over the sphere.  The test is that of the rays on vertices translated by the
+ * origin, with TOLERANT edges: hit iff u >= -e, v >= -e, u + v <= 1 + e with e = 2^-30, t finite and -R0 < t < 1e9 -- interior
+ * edges and vertices are watertight, and a point at an exact DEM post on the mesh border has terrain.  Among all triangles of all
+ * resident tiles the LARGEST t is reported (the surface seen from above); on equal t the tile that comes first in draw order, then
+ * the lower triangle index.  Tiles may overlap or leave gaps; the columns of a tile are taken to lie within 180 degrees of its
+ * model point, and a tile whose pixel scale is zero or not finite in x or y has no surface.  slope_deg is the angle between the triangle's normal n = (v1 - v0) x (v2 - v0), turned to the side of u, and u;
+ * aspect_deg the azimuth, clockwise from true north in [0, 360), of the horizontal part of that normal -- the downslope direction
+ * -- in the east / north / up frame of topo_sun_direction at the point, 0 where it vanishes.
+ * A point is valid iff lon and lat are finite and |lat| <= 90; any finite lon wraps, and at |lat| = 90 the given lon picks the
+ * column.  An invalid point is TOPO_SURFACE_INVALID; a valid point outside every tile, in a gap or over a void is TOPO_SURFACE_NONE.
+ * The calls read the resident tiles only and need no submission; they run on the context's stream (topo_set_stream) behind whatever
+ * was queued there, and write nothing but their outputs.  With no tiles every valid point is NONE; n = 0 is a no-op.
+ * TOPO_ERR_INVALID for null or misaligned pointers. */
+typedef struct topo_surface_point {      /* 48 bytes; written as three 16-byte stores */
+    double height_m;                     /* t: the height over the sphere of radius R0 */
+    float slope_deg, aspect_deg;
+    int32_t kind;                        /* TOPO_SURFACE_*; every other field is 0 unless TOPO_SURFACE_TERRAIN */
+    int32_t tile_lat_deg, tile_lon_deg;  /* tile of the triangle */
+    uint32_t cell_x, cell_y, tri;        /* its cell and triangle: viewshed / horizon / ground / ray numbering */
+    float w1, w2;                        /* u, v: the weights of the triangle's second and third vertex */
+} topo_surface_point;
+#define TOPO_SURFACE_TERRAIN 1
+#define TOPO_SURFACE_NONE 0
+#define TOPO_SURFACE_INVALID (-1)
+/* Host memory, n (lon, lat) pairs in degrees -> n records; waits. */
+int topo_surface_read(topo_ctx* ctx, uint32_t n, const double* lonlat_deg, topo_surface_point* out);
+/* Device memory (both 16-byte aligned); asynchronous on the context's stream. */
+int topo_surface_device(topo_ctx* ctx, uint32_t n, const double* lonlat_dev, topo_surface_point* out_dev);
+/* The dense form: the f32 height -- (float) of what the list calls report, bit for bit -- at lon0 + c * dlon, lat0 + r * dlat (one
+ * rounded product, one rounded sum) for c < nx, r < ny at out_dev + r * pitch_bytes + 4 * c (device memory; pointer and pitch
+ * multiples of 4; the bytes between nx and the pitch are left alone); a quiet NaN where there is no terrain or the point is
+ * invalid.  dlon and dlat may be negative or zero.  TOPO_ERR_INVALID also for a zero nx or ny, non-finite parameters and
+ * ceil(nx / 64) * ny >= 2^32.  Asynchronous. */
+int topo_surface_grid_device(topo_ctx* ctx, double lon0_deg, double lat0_deg, double dlon_deg, double dlat_deg, uint32_t nx, uint32_t ny, float* out_dev,
+                             size_t pitch_bytes);
+/* Profiles: the cross-section under a sight line, the companion of a line-of-sight answer.  A segment is a topo_ray with finite
+ * t_min and t_max (otherwise, or if the ray is invalid, the segment is TOPO_SURFACE_INVALID: a zero summary, NaN samples).  Sample
+ * k of m lies at t_k = t_min + (t_max - t_min) * (k / (m - 1)), p = origin + t_k * dir, every step rounded in f64; the terrain is
+ * looked up under p / |p|, and line = |p| - R0.  A sample is the pair (terrain, line), each rounded once to f32, terrain a quiet NaN
+ * where there is none; its clearance is the f32 difference line - terrain of the values as stored.  The summary is the smallest
+ * clearance over the samples that have terrain, on equal values the lowest sample index; with no sample over terrain
+ * min_clearance_m is a quiet NaN, min_sample 0xFFFFFFFF and kind TOPO_SURFACE_NONE.  The profile says BY HOW MUCH a line clears the
+ * terrain AT ITS SAMPLES; exact line of sight remains topo_raycast_*.  2 <= m <= 65536, n * m < 2^31. */
+typedef struct topo_profile_summary { float min_clearance_m; uint32_t min_sample; uint32_t n_terrain; int32_t kind; } topo_profile_summary;      /* 16 bytes, one store */
+/* Device memory: segs_dev and summary_dev 16-byte aligned; samples_dev null, or 8-byte aligned: segment i's m pairs at samples_dev
+ * + i * segment_stride_bytes (a multiple of 8, at least 8 * m; the bytes behind a segment's samples are left alone).  Asynchronous. */
+int topo_profile_device(topo_ctx* ctx, uint32_t n, const topo_ray* segs_dev, uint32_t m, float* samples_dev, size_t segment_stride_bytes,
+                        topo_profile_summary* summary_dev);
+/* Host memory: samples null, or n * m pairs, densely packed; waits. */
+int topo_profile_read(topo_ctx* ctx, uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary);
+
 /* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
  * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
  * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --

@@ -50,6 +50,12 @@ SUN_NONE, SUN_LIT, SUN_AWAY, SUN_SHADOW = 0, 1, 2, 3
 RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("dir", "<f8", 3), ("t_min", "<f8"), ("t_max", "<f8")])
 RAY_HIT_DTYPE = np.dtype([("t", "<f8"), ("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f4"), ("kind", "<i4"), ("tile_lat_deg", "<i4"),
                           ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("front", "<u4"), ("w1", "<f4"), ("w2", "<f4")])
+SURFACE_TERRAIN, SURFACE_NONE, SURFACE_INVALID = 1, 0, -1
+PROFILE_NO_SAMPLE = 0xFFFFFFFF
+# topo_surface_point, 48 bytes, and topo_profile_summary, 16 bytes
+SURFACE_DTYPE = np.dtype([("height_m", "<f8"), ("slope_deg", "<f4"), ("aspect_deg", "<f4"), ("kind", "<i4"), ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"),
+                          ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("w1", "<f4"), ("w2", "<f4")])
+PROFILE_SUMMARY_DTYPE = np.dtype([("min_clearance_m", "<f4"), ("min_sample", "<u4"), ("n_terrain", "<u4"), ("kind", "<i4")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
 # topo_unwrap_params, 48 bytes
@@ -178,6 +184,11 @@ def lib():
             "topo_raycast_device": (C.c_int, [vp, u32, vp, vp]),
             "topo_sunlit_map_device": (C.c_int, [vp, u32, u32, vp, vp, sz, sz]),
             "topo_sun_direction": (None, [C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+            "topo_surface_read": (C.c_int, [vp, u32, vp, vp]),
+            "topo_surface_device": (C.c_int, [vp, u32, vp, vp]),
+            "topo_surface_grid_device": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_double, u32, u32, vp, sz]),
+            "topo_profile_device": (C.c_int, [vp, u32, vp, u32, vp, sz, vp]),
+            "topo_profile_read": (C.c_int, [vp, u32, vp, u32, vp, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
         }
@@ -798,6 +809,40 @@ class TerrainRenderer:
         stride = pitch * h if view_stride_bytes is None else view_stride_bytes
         sun = np.ascontiguousarray(sun_dir, dtype=np.float64).reshape(3)
         self._check(lib().topo_sunlit_map_device(self._h, first_view, n, _p(sun), C.c_void_p(out_ptr) if out_ptr else None, stride, pitch))
+
+    # surface: the drawn terrain under a longitude and latitude (include/topo_hip.h); no submission needed
+    def surface(self, lonlat) -> np.ndarray:
+        """topo_surface_read: (n, 2) f64 (longitude, latitude) in degrees -> SURFACE_DTYPE records; waits."""
+        p = np.ascontiguousarray(lonlat, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros(len(p), SURFACE_DTYPE)
+        self._check(lib().topo_surface_read(self._h, len(p), _p(p) if len(p) else None, _p(out) if len(p) else None))
+        return out
+
+    def surface_device(self, lonlat_ptr: int, out_ptr: int, n: int):
+        """topo_surface_device: n (lon, lat) f64 pairs at lonlat_ptr -> n topo_surface_point at out_ptr (device memory, 16-byte
+        aligned), queued on the context's stream."""
+        self._check(lib().topo_surface_device(self._h, n, C.c_void_p(lonlat_ptr) if lonlat_ptr else None, C.c_void_p(out_ptr) if out_ptr else None))
+
+    def surface_grid_device(self, lon0: float, lat0: float, dlon: float, dlat: float, nx: int, ny: int, out_ptr: int, pitch_bytes: int = None):
+        """topo_surface_grid_device: the f32 height at lon0 + c * dlon, lat0 + r * dlat for c < nx, r < ny at out_ptr + r * pitch_bytes +
+        4 * c (device memory; default: densely packed), NaN where there is no terrain; queued on the context's stream."""
+        self._check(lib().topo_surface_grid_device(self._h, lon0, lat0, dlon, dlat, nx, ny, C.c_void_p(out_ptr) if out_ptr else None,
+                                                   4 * nx if pitch_bytes is None else pitch_bytes))
+
+    def profile(self, ray_records, m: int, samples: bool = True):
+        """topo_profile_read: RAY_DTYPE segments (finite t_min, t_max) -> (PROFILE_SUMMARY_DTYPE records, (n, m, 2) f32 (terrain,
+        line) samples or None); waits."""
+        r = np.ascontiguousarray(ray_records, dtype=RAY_DTYPE).reshape(-1)
+        summary = np.zeros(len(r), PROFILE_SUMMARY_DTYPE)
+        smp = np.zeros((len(r), m, 2), np.float32) if samples else None
+        self._check(lib().topo_profile_read(self._h, len(r), _p(r) if len(r) else None, m, _p(smp) if samples and len(r) else None, _p(summary) if len(r) else None))
+        return summary, smp
+
+    def profile_device(self, segs_ptr: int, n: int, m: int, summary_ptr: int, samples_ptr: int = 0, segment_stride_bytes: int = None):
+        """topo_profile_device: n topo_ray at segs_ptr -> n topo_profile_summary at summary_ptr and, unless samples_ptr is 0, m
+        (terrain, line) f32 pairs per segment at samples_ptr + i * segment_stride_bytes (default 8 * m); queued on the context's stream."""
+        self._check(lib().topo_profile_device(self._h, n, C.c_void_p(segs_ptr) if segs_ptr else None, m, C.c_void_p(samples_ptr) if samples_ptr else None,
+                                              8 * m if segment_stride_bytes is None else segment_stride_bytes, C.c_void_p(summary_ptr) if summary_ptr else None))
 
     # unwrap: finished views that share an eye as one azimuth / elevation image (include/topo_hip.h)
     def unwrap_device(self, params, uniforms_list, src_w: int, src_h: int, rgba_src_ptr: int = 0, rgba_view_stride: int = None, rgba_pitch: int = None,

@@ -1,6 +1,7 @@
-// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, unwrap), the tile-set
+// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, unwrap), the tile-set
 // tables they read and their handle on the latest submission.  The frame path is terrain_renderer.cpp (see terrain_renderer.hpp).
 #include "terrain_renderer.hpp"
+#include "topo_surface.h"
 
 #include <cmath>
 #include <cstring>
@@ -12,6 +13,9 @@ static_assert(sizeof(GroundPoint) == sizeof(topo_ground_point) && sizeof(topo_gr
 static_assert(sizeof(GroundQuery) == sizeof(topo_ground_query) && sizeof(topo_ground_query) == 16, "ground query layout");
 static_assert(sizeof(LosRay) == sizeof(topo_ray) && sizeof(topo_ray) == 64, "ray layout");
 static_assert(sizeof(RayHit) == sizeof(topo_ray_hit) && sizeof(topo_ray_hit) == 64, "ray record layout");
+static_assert(sizeof(SurfacePoint) == sizeof(topo_surface_point) && sizeof(topo_surface_point) == 48, "surface record layout");
+static_assert(sizeof(ProfileSummary) == sizeof(topo_profile_summary) && sizeof(topo_profile_summary) == 16, "profile summary layout");
+static_assert(kSurfaceTerrain == TOPO_SURFACE_TERRAIN && kSurfaceNone == TOPO_SURFACE_NONE && kSurfaceInvalid == TOPO_SURFACE_INVALID, "surface kinds");
 static_assert(kTileSphereDoubles == kLosSphereDoubles, "the cull prefilter and the rays read the same spheres: one gather, one layout");
 
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
@@ -392,6 +396,103 @@ int TerrainRenderer::sunlit_map_device(uint32_t first, uint32_t n, const double 
     if (int rc = ground_prepare(q)) return rc;
     launch_sunlit_map(ground_params(q, first, n), ray_params().s, sun, out_dev, view_stride, pitch, q.s);
     return query_queued(q);
+}
+
+// ---- surface ------------------------------------------------------------------------------------------------------------------
+
+// Host read: the points go in and the records come out through one pinned staging buffer, as the rays; waits for the stream.
+int TerrainRenderer::surface_read(uint32_t n, const double* lonlat_deg, topo_surface_point* out) {
+    if (n == 0) return TOPO_OK;
+    if (!lonlat_deg || !out) return fail(TOPO_ERR_INVALID, "null argument");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    const size_t in_bytes = (size_t)n * 2 * sizeof(double), out_bytes = (size_t)n * sizeof(SurfacePoint);
+    if (int rc = ensure(stream_, query_.d_surface_in, in_bytes)) return rc;
+    if (int rc = ensure(stream_, query_.d_surface_out, out_bytes)) return rc;
+    if (out_bytes > query_.h_surface_stage.cap) TOPO_HIP_TRY(hipStreamSynchronize(stream_));      // (nothing in flight reads the old staging block)
+    if (int rc = ensure_pinned(query_.h_surface_stage, out_bytes)) return rc;
+    std::memcpy(query_.h_surface_stage.p, lonlat_deg, in_bytes);
+    TOPO_HIP_TRY(hipMemcpyAsync(query_.d_surface_in.p, query_.h_surface_stage.p, in_bytes, hipMemcpyHostToDevice, stream_));
+    launch_surface(ray_params(), query_.d_surface_in.as<const double>(), query_.d_surface_out.as<SurfacePoint>(), n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipMemcpyAsync(query_.h_surface_stage.p, query_.d_surface_out.p, out_bytes, hipMemcpyDeviceToHost, stream_));
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    std::memcpy(out, query_.h_surface_stage.p, out_bytes);
+    return query_fold_check();
+}
+
+// Device variants: queued on stream_, in order.
+int TerrainRenderer::surface_device(uint32_t n, const double* lonlat_dev, topo_surface_point* out_dev) {
+    if (n == 0) return TOPO_OK;
+    if (!lonlat_dev || !out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)lonlat_dev % 16 != 0 || (uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "lonlat_dev and out_dev must be 16-byte aligned");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    launch_surface(ray_params(), lonlat_dev, (SurfacePoint*)out_dev, n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+int TerrainRenderer::surface_grid_device(double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny, float* out_dev, size_t pitch_bytes) {
+    if (!out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if (nx == 0 || ny == 0) return fail(TOPO_ERR_INVALID, "an empty grid");
+    if (!std::isfinite(lon0) || !std::isfinite(lat0) || !std::isfinite(dlon) || !std::isfinite(dlat)) return fail(TOPO_ERR_INVALID, "grid parameters must be finite");
+    if ((uintptr_t)out_dev % 4 != 0 || pitch_bytes % 4 != 0) return fail(TOPO_ERR_INVALID, "out_dev and the pitch must be multiples of 4 bytes");
+    if (pitch_bytes < (size_t)nx * sizeof(float)) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
+    if ((((uint64_t)nx + 63) / 64) * ny > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "grid too large");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    launch_surface_grid(ray_params(), lon0, lat0, dlon, dlat, nx, ny, out_dev, pitch_bytes, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// What is wrong with a profile call's shape, or null.
+static const char* profile_shape_error(uint32_t n, uint32_t m) {
+    if (m < kProfileMinSamples || m > kProfileMaxSamples) return "m must lie in 2 .. 65536";
+    if ((uint64_t)n * m >= (1ull << 31)) return "n * m must be below 2^31";
+    return nullptr;
+}
+
+int TerrainRenderer::profile_device(uint32_t n, const topo_ray* segs_dev, uint32_t m, float* samples_dev, size_t segment_stride_bytes, topo_profile_summary* summary_dev) {
+    if (n == 0) return TOPO_OK;
+    if (!segs_dev || !summary_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if (const char* why = profile_shape_error(n, m)) return fail(TOPO_ERR_INVALID, why);
+    if ((uintptr_t)segs_dev % 16 != 0 || (uintptr_t)summary_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "segs_dev and summary_dev must be 16-byte aligned");
+    if (samples_dev) {
+        if ((uintptr_t)samples_dev % 8 != 0 || segment_stride_bytes % 8 != 0) return fail(TOPO_ERR_INVALID, "samples_dev and the segment stride must be multiples of 8 bytes");
+        if (segment_stride_bytes < (size_t)m * 2 * sizeof(float)) return fail(TOPO_ERR_INVALID, "segment stride smaller than a segment's samples");
+    }
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    launch_profile(ray_params(), (const LosRay*)segs_dev, n, m, samples_dev, segment_stride_bytes, (ProfileSummary*)summary_dev, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Host read.  The caller's memory is pageable and the samples can be gigabytes (8 n m bytes), so nothing is staged: the stream is
+// drained, the segments go up with a blocking copy, the kernel runs on the stream -- behind whatever was queued there -- and the
+// results come down with blocking copies once it has finished.
+int TerrainRenderer::profile_read(uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary) {
+    if (n == 0) return TOPO_OK;
+    if (!segs || !summary) return fail(TOPO_ERR_INVALID, "null argument");
+    if (const char* why = profile_shape_error(n, m)) return fail(TOPO_ERR_INVALID, why);
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    const size_t in_bytes = (size_t)n * sizeof(LosRay), sum_bytes = (size_t)n * sizeof(ProfileSummary), row = (size_t)m * 2 * sizeof(float);
+    if (int rc = ensure(stream_, query_.d_ray_in, in_bytes)) return rc;
+    if (int rc = ensure(stream_, query_.d_surface_out, sum_bytes)) return rc;
+    if (samples)
+        if (int rc = ensure(stream_, query_.d_profile_samples, row * n)) return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    TOPO_HIP_TRY(hipMemcpy(query_.d_ray_in.p, segs, in_bytes, hipMemcpyHostToDevice));
+    launch_profile(ray_params(), query_.d_ray_in.as<const LosRay>(), n, m, samples ? query_.d_profile_samples.as<float>() : nullptr, row,
+                   query_.d_surface_out.as<ProfileSummary>(), stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (samples) TOPO_HIP_TRY(hipMemcpy(samples, query_.d_profile_samples.p, row * n, hipMemcpyDeviceToHost));
+    TOPO_HIP_TRY(hipMemcpy(summary, query_.d_surface_out.p, sum_bytes, hipMemcpyDeviceToHost));
+    return query_fold_check();
 }
 
 // ---- unwrap -------------------------------------------------------------------------------------------------------------------

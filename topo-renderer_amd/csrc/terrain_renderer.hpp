@@ -170,6 +170,13 @@ class TerrainRenderer {
     // ... and the sunlit layer of the latest submission's views, beside the ground map (topo_sunlit_map_device)
     int sunlit_map_device(uint32_t first_view, uint32_t n_views, const double sun_dir[3], uint8_t* out_dev, size_t view_stride_bytes, size_t pitch_bytes);
 
+    // surface: the drawn terrain under a longitude and latitude -- lists, grids and profiles (topo_surface_*, topo_profile_*): no submission needed
+    int surface_read(uint32_t n, const double* lonlat_deg, topo_surface_point* out);
+    int surface_device(uint32_t n, const double* lonlat_dev, topo_surface_point* out_dev);
+    int surface_grid_device(double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny, float* out_dev, size_t pitch_bytes);
+    int profile_device(uint32_t n, const topo_ray* segs_dev, uint32_t m, float* samples_dev, size_t segment_stride_bytes, topo_profile_summary* summary_dev);
+    int profile_read(uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary);
+
     // unwrap: finished views that share an eye as one azimuth / elevation image (topo_unwrap_device)
     int unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h, const OutputParams& src,
                       const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch);
@@ -348,12 +355,13 @@ class TerrainRenderer {
     const std::vector<double>& tile_spheres();
     int prepare_tables(TableLevel level, hipStream_t s);      // what a query kernel on s reads, up to `level`: once per public query
     // The queries' own buffers: the bounds record of every query kernel (TOPO_BOUNDS_CHECK build, folded into topo_frame_status), the
-    // host reads' device buffers (horizon rows; ground queries, records; rays in, records out, their pinned staging), and the device
+    // host reads' device buffers (horizon rows; ground queries, records; rays in, records out, their pinned staging; surface points in,
+    // records or profile summaries out, their pinned staging, a profile read's samples), and the device
     // copy of k_unwrap's f64 tables (topo_unwrap.h), kept for what they were built from -- the call's parameters, the views'
     // direction blocks and the eye (unwrap_key) -- with their host copy, the source of the upload
     struct QueryBuffers {
-        DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_unwrap_tab;
-        PinnedBuffer h_ray_stage;
+        DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_surface_in, d_surface_out, d_profile_samples, d_unwrap_tab;
+        PinnedBuffer h_ray_stage, h_surface_stage;
         std::vector<double> unwrap_tab;
         std::vector<uint8_t> unwrap_key;
     } query_;

@@ -422,6 +422,33 @@ void topo_sun_direction(double lon_deg, double lat_deg, double az_deg, double el
     topo::sun_direction(lon_deg, lat_deg, az_deg, el_deg, dir_out);
 }
 
+int topo_surface_read(topo_ctx* ctx, uint32_t n, const double* lonlat_deg, topo_surface_point* out) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->surface_read(n, lonlat_deg, out));
+}
+
+int topo_surface_device(topo_ctx* ctx, uint32_t n, const double* lonlat_dev, topo_surface_point* out_dev) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->surface_device(n, lonlat_dev, out_dev));
+}
+
+int topo_surface_grid_device(topo_ctx* ctx, double lon0_deg, double lat0_deg, double dlon_deg, double dlat_deg, uint32_t nx, uint32_t ny, float* out_dev,
+                             size_t pitch_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->surface_grid_device(lon0_deg, lat0_deg, dlon_deg, dlat_deg, nx, ny, out_dev, pitch_bytes));
+}
+
+int topo_profile_device(topo_ctx* ctx, uint32_t n, const topo_ray* segs_dev, uint32_t m, float* samples_dev, size_t segment_stride_bytes,
+                        topo_profile_summary* summary_dev) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->profile_device(n, segs_dev, m, samples_dev, segment_stride_bytes, summary_dev));
+}
+
+int topo_profile_read(topo_ctx* ctx, uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->profile_read(n, segs, m, samples, summary));
+}
+
 int topo_unwrap_device(topo_ctx* ctx, const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h,
                        const uint8_t* rgba_src_dev, size_t rgba_view_stride, size_t rgba_pitch, const float* depth_src_dev, size_t depth_view_stride,
                        size_t depth_pitch, uint8_t* rgba_out_dev, size_t rgba_out_pitch, float* depth_out_dev, size_t depth_out_pitch, int32_t* src_out_dev,

@@ -244,6 +244,27 @@ void launch_raycast(const RayParams& p, const LosRay* rays, RayHit* out, uint32_
 // `sun` (unit): view i at out + i * view_stride, rows pitch apart (bytes)
 void launch_sunlit_map(const GroundParams& g, const LosScene& scene, const double sun[3], uint8_t* out, size_t view_stride, size_t pitch, hipStream_t s);
 
+// surface (topo_surface_*, topo_profile_*): the drawn terrain under a longitude and latitude (topo_surface.h); needs no submission.
+// Reads the tile table, the DEMs and the tiles' f64 tables (RayParams: the rays' scene); writes only its outputs.
+struct SurfacePoint {      // = topo_surface_point (48 bytes)
+    double height_m;
+    float slope_deg, aspect_deg;
+    int32_t kind;
+    int32_t tile_lat, tile_lon;
+    uint32_t cell_x, cell_y, tri;
+    float w1, w2;
+};
+struct ProfileSummary {    // = topo_profile_summary (16 bytes)
+    float min_clearance_m;
+    uint32_t min_sample, n_terrain;
+    int32_t kind;
+};
+void launch_surface(const RayParams& p, const double* lonlat, SurfacePoint* out, uint32_t n, hipStream_t s);      // n (lon, lat) pairs, degrees
+// f32 heights at lon0 + c dlon, lat0 + r dlat for c < nx, r < ny, rows pitch bytes apart; ceil(nx / 64) * ny < 2^32
+void launch_surface_grid(const RayParams& p, double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny, float* out, size_t pitch, hipStream_t s);
+// m samples (terrain, line) of each of n segments at samples + i * stride bytes (samples null: none), and the segments' summaries
+void launch_profile(const RayParams& p, const LosRay* segs, uint32_t n, uint32_t m, float* samples, size_t stride, ProfileSummary* summary, hipStream_t s);
+
 // unwrap (topo_unwrap_*): n_views views of src_w x src_h that share an eye, resampled into one out_w x out_h azimuth / elevation
 // image (topo_unwrap.h).  Reads the tables and the source images; writes only the outputs given (each nullable; rgba_out needs
 // rgba_src, depth_out needs depth_src).
