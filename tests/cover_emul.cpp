@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../topo-renderer_amd/csrc/topo_pipeline.h"
+#include "emul_tiles.h"
 
 using namespace topo;
 
@@ -78,12 +79,6 @@ int emul_cover_item(const int32_t* X, const int32_t* Y, const float* z, uint32_t
     return violations;
 }
 
-struct EmulTile {      // = tests/host_emul.cpp
-    const float* heights;
-    uint32_t* normals;
-    float tu[24];
-};
-
 // The near phase of one view as the kernels order it, every block taken as a near block (the scenes of the tests have no far phase):
 //   old     what k_raster draws in-wave (boxes under 5 rows x 24 columns) and k_raster_rare in-lane (boxes up to 4 x 4): the keys and
 //           segment marks k_raster_cover finds;
@@ -133,11 +128,7 @@ int emul_cover_frame(const EmulTile* tiles, uint32_t n_tiles, uint32_t tile_w, u
     const uint32_t tris_per_tile = 2u * (tile_w - 1) * (tile_h - 1);
     std::vector<std::vector<float>> trig(n_tiles);
     for (uint32_t rank = 0; rank < n_tiles; ++rank) {
-        TileDev t{};
-        t.heights = tiles[rank].heights; t.normals = tiles[rank].normals;
-        t.raster_x = tiles[rank].tu[0]; t.raster_y = tiles[rank].tu[1]; t.model_x = tiles[rank].tu[2]; t.model_y = tiles[rank].tu[3];
-        t.scale_x = tiles[rank].tu[4]; t.scale_y = tiles[rank].tu[5];
-        for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) t.rot[c * 3 + r] = tiles[rank].tu[8 + c * 4 + r];
+        TileDev t = make_dev(tiles[rank]);
         trig[rank].resize(2 * (size_t)(tile_w + tile_h));
         for (uint32_t x = 0; x < tile_w; ++x) sincos_f(vertex_lon(t, x), trig[rank][2 * x], trig[rank][2 * x + 1]);
         for (uint32_t y = 0; y < tile_h; ++y) sincos_f(vertex_lat(t, y), trig[rank][2 * (tile_w + y)], trig[rank][2 * (tile_w + y) + 1]);

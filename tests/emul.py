@@ -2,31 +2,19 @@
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "_build", "libhost_emul.so")
+import native
+from emul_tiles import EmulTile, emul_tile
+
 _LIB = None
-
-
-class EmulTile(C.Structure):
-    _fields_ = [("heights", C.c_void_p), ("normals", C.c_void_p), ("tu", C.c_float * 24)]
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        src = os.path.join(_HERE, "host_emul.cpp")
-        hdrs = [os.path.join(_HERE, "..", "topo-renderer_amd", "csrc", f) for f in ("topo_math.h", "topo_pipeline.h", "srgb_tables.h")]
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if not os.path.exists(_SO) or any(os.path.getmtime(f) > os.path.getmtime(_SO) for f in [src] + hdrs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-shared",
-                                   "-o", _SO, src])
-        _LIB = C.CDLL(_SO)
-        _LIB.emul_render.restype = C.c_int
+        _LIB = native.load("libhost_emul.so", ["host_emul.cpp"], {"emul_render": C.c_int})
     return _LIB
 
 
@@ -49,12 +37,7 @@ class EmulRenderer:
         return (abs(lat), 1 if lat > 0 else 0, abs(lon), 1 if lon > 0 else 0)
 
     def _et(self, t):
-        e = EmulTile()
-        e.heights = t["h"].ctypes.data
-        e.normals = t["n"].ctypes.data
-        for i in range(24):
-            e.tu[i] = float(t["tu"][i])
-        return e
+        return emul_tile(t["h"], t["n"], t["tu"])
 
     def add_terrain(self, lat, lon, heights, rp, mp, ps):
         hts = np.ascontiguousarray(heights, dtype=np.float32)

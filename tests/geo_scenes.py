@@ -9,8 +9,7 @@ import math
 import numpy as np
 
 import topo_renderer_amd as T
-from scenes import Scene
-from test_ray_check_cpu import relief
+from scenes import Scene, relief
 
 TILE, EYE_DH, W, H, PITCH, FOV = 24, 4000.0, 96, 64, 25.0, 60.0
 

@@ -2,14 +2,9 @@
 // function k_ground and k_ground_map call for every pixel they answer, run here over a whole frame of winners on the CPU
 // (tests/ground_emul.py, tests/test_ground_cpu.py).  The glue around it -- key, decode, vertex texels, DEM loads -- is the kernels'.
 #include "../topo-renderer_amd/csrc/topo_ground.h"
+#include "emul_tiles.h"
 
 using namespace topo;
-
-struct EmulGroundTile {
-    const float* heights;
-    float tf[6];           // raster_point, model_point, pixel_scale
-    int32_t lat, lon;
-};
 
 struct EmulGroundOut {     // topo_ground_point's fields, the computed ones in f64
     double lon_deg, lat_deg, height, range, w1, w2;
@@ -19,7 +14,7 @@ struct EmulGroundOut {     // topo_ground_point's fields, the computed ones in f
 };
 
 // depth / winners: H x W (winner = rank * tris_per_tile + triangle, kNoTri = sky); uniforms: the view's 40 floats.
-extern "C" int emul_ground(const EmulGroundTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, const float* uniforms, uint32_t W, uint32_t H,
+extern "C" int emul_ground(const EmulGeoTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, const float* uniforms, uint32_t W, uint32_t H,
                            const float* depth, const uint32_t* winners, EmulGroundOut* out) {
     GroundView view{};
     memcpy(view.proj, uniforms, sizeof view.proj);
@@ -34,11 +29,8 @@ extern "C" int emul_ground(const EmulGroundTile* tiles, uint32_t n_tiles, uint32
                 const uint32_t id = winners[at] << 1;      // (the oracle's winners carry no fan piece)
                 const GroundTri g = ground_decode(id, tris_per_tile, hm1);
                 if (g.rank >= n_tiles) return -1;
-                const EmulGroundTile& et = tiles[g.rank];
-                TileDev t{};
-                t.raster_x = et.tf[0]; t.raster_y = et.tf[1];
-                t.model_x = et.tf[2]; t.model_y = et.tf[3];
-                t.scale_x = et.tf[4]; t.scale_y = et.tf[5];
+                const EmulGeoTile& et = tiles[g.rank];
+                const TileDev t = make_dev(et);
                 uint32_t vx[3], vy[3];
                 triangle_vertices(g.tri, hm1, vx, vy);
                 double p[3][3];

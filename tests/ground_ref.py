@@ -11,6 +11,7 @@ from oracle import ray_check as RC
 from viewshed_ref import NO_TRI, geo_order
 
 R0 = RC.R0
+NAN_BITS = 0x7FC00000
 EXACT = ("kind", "tile_lat_deg", "tile_lon_deg", "cell_x", "cell_y", "tri", "depth")      # what the winners and depths determine
 
 
@@ -123,3 +124,26 @@ def compare(got, want, what, f64=None, tol_m=1e-3, tol_w=1e-6):
     assert out["point_m"] <= tol_m and out["height_m"] <= tol_m and out["range_m"] <= tol_m, f"{what}: {out}"
     assert out["w"] <= tol_w, f"{what}: {out}"
     return out
+
+
+def all_pixels(topo, views, W, H):
+    """Queries for every pixel of the given view indices, view-major then row-major."""
+    v, y, x = np.meshgrid(np.asarray(views), np.arange(H), np.arange(W), indexing="ij")
+    return topo.ground_queries(np.stack([v.ravel(), x.ravel(), y.ravel()], axis=-1))
+
+
+def assert_sky(got, what):
+    sky = got[got["kind"] == 0]
+    assert (sky["depth"] == 1.0).all(), what
+    blank = sky.copy()
+    blank["depth"] = 0
+    assert not blank.view(np.uint8).any(), f"{what}: a sky record carries something besides depth 1.0"
+
+
+def assert_map_is_list(vals, rec, what):
+    """vals (..., 4) f32 of the map, rec (...) list records of the same pixels: np.float32 of the record bit for bit, NaN elsewhere."""
+    t = rec["kind"] == 1
+    want = np.stack([rec["lon_deg"].astype(np.float32), rec["lat_deg"].astype(np.float32), rec["height_m"], rec["range_m"]], axis=-1).view(np.uint32)
+    want = np.where(t[..., None], want, np.uint32(NAN_BITS))
+    bad = np.argwhere(vals.view(np.uint32) != want)
+    assert len(bad) == 0, f"{what}: the map differs from the list in {len(bad)} values (first {tuple(bad[0])}: {vals[tuple(bad[0])]!r} vs record {rec[tuple(bad[0][:-1])]})"

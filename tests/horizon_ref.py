@@ -40,3 +40,30 @@ def mismatches(got, want, field):
     if field == "depth":
         g, w = g.astype(np.float32).view(np.uint32), w.astype(np.float32).view(np.uint32)
     return np.nonzero(g != w)[0]
+
+
+def assert_view(got, want, what, frame_depth=None):
+    """got: (W,) records of one view; want: horizon_ref dict; frame_depth: (H, W) depth output of the same view."""
+    for f in FIELDS:
+        bad = mismatches(got, want, f)
+        assert len(bad) == 0, f"{what}: {f} differs in {len(bad)} columns (first {bad[0]}: got {got[f][bad[0]]}, want {want[f][bad[0]]})"
+    assert np.isin(got["fan"], (0, 1)).all() and (got["_reserved"] == 0).all(), what
+    if frame_depth is not None:
+        fd = np.asarray(frame_depth, np.float32)
+        rows = got["row"]
+        at = np.where(rows >= 0, fd[np.clip(rows, 0, None), np.arange(len(rows))], np.float32(1.0))
+        assert np.array_equal(at.view(np.uint32), got["depth"].view(np.uint32)), f"{what}: depth differs from the frame's depth output"
+        top = np.where(rows >= 0, rows, fd.shape[0])
+        sky_above = np.arange(fd.shape[0])[:, None] < top[None, :]
+        assert (fd[sky_above] == 1.0).all(), f"{what}: terrain depth above the reported row"
+
+
+FRAMES = [
+    # tile, n_lat, n_lon, eye_dh, W, H, [(yaw, pitch, fov)]  -- test_viewshed_gpu.py's frames, then an odd width and the mosaic's edge
+    (96, 2, 2, 50.0, 256, 128, [(40, 10, 70), (250, 0, 60)]),
+    (96, 2, 2, 100.0, 200, 150, [(120, 60, 90)]),                  # near clip / big triangles
+    (64, 1, 1, 400.0, 160, 160, [(10, 85, 100), (300, 70, 80)]),   # pitch 85: terrain up to row 0
+    (12, 2, 2, 60.0, 640, 480, [(10, 35, 110), (200, 80, 110), (100, 5, 110)]),   # the coarse mesh: every triangle large
+    (96, 2, 2, 80.0, 333, 97, [(70, 3, 75)]),                      # a width that is no multiple of 64
+    (64, 1, 1, 50.0, 190, 100, [(0, -27, 60), (90, -27, 60), (180, -27, 60), (270, -27, 60)]),   # out past the mosaic: sky columns
+]

@@ -8,25 +8,11 @@
 #include <vector>
 
 #include "../topo-renderer_amd/csrc/topo_pipeline.h"
+#include "emul_tiles.h"
 
 using namespace topo;
 
 extern "C" {
-
-struct EmulTile {
-    const float* heights;
-    uint32_t* normals;
-    float tu[24];   // TerrainUniforms, 96 B
-};
-
-static TileDev make_dev(const EmulTile& e) {
-    TileDev t{};
-    t.heights = e.heights; t.normals = e.normals; t.block_minmax = nullptr;
-    t.raster_x = e.tu[0]; t.raster_y = e.tu[1]; t.model_x = e.tu[2]; t.model_y = e.tu[3];
-    t.scale_x = e.tu[4]; t.scale_y = e.tu[5];
-    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) t.rot[c * 3 + r] = e.tu[8 + c * 4 + r];
-    return t;
-}
 
 uint32_t emul_fastdiv(uint32_t n, uint32_t d) { return fastdiv(n, fastdiv_make(d)); }
 void emul_markstein_div(const float* x, float C, float* out, size_t n) { for (size_t i = 0; i < n; ++i) out[i] = markstein_div(x[i], C, 1.0f / C); }

@@ -10,7 +10,7 @@ import numpy as np
 import los_ref as LR
 import topo_renderer_amd as T
 from oracle import ray_check as RC
-from scenes import Scene
+from scenes import Scene, relief
 
 R0 = LR.R0
 RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("dir", "<f8", 3), ("t_min", "<f8"), ("t_max", "<f8")])
@@ -163,9 +163,7 @@ CASES = {"ridges_ne": lambda: _ridges_case("ridges_ne"), "ridges_sw": lambda: _r
 
 
 # ---- off the 45N 15E quadrant: across the equator, the prime meridian, the antimeridian and the pole -----------------------------------
-def geo_relief(lat, lon):
-    from test_ray_check_cpu import relief
-    return relief(lat, lon)
+geo_relief = relief
 
 
 def placed_tiles(locs, n, height_fn=geo_relief):
@@ -424,3 +422,23 @@ def compose_sunlit(tiles, order, rec, sun):
     cls, bad = LE.sunlit(tiles, order, rank, tri, rec["w1"].astype(np.float64), rec["w2"].astype(np.float64), sun)
     assert bad == 0
     return cls.reshape(ok.shape)
+
+
+def against_emulation(got, emu, rays, what, keep):
+    """Every ray: kind, tile, cell, triangle and face identical.  The rays the reference does not mark ambiguous (keep): t * |dir|
+    within 1e-4 m (device and host sin / cos differ by an ulp or two: about 1.5e-9 m of vertex position, which 1 / |n . d| <= 1e3
+    turns into 1.5e-6 m at most) -- a grazing ray has no such bound."""
+    for f in ("kind", "tile_lat_deg", "tile_lon_deg", "cell_x", "cell_y", "tri", "front"):
+        bad = np.nonzero(got[f] != emu[f])[0]
+        assert len(bad) == 0, f"{what}: {f} differs from the emulation for {len(bad)} rays, first {bad[0]}: {got[bad[0]]} vs {emu[bad[0]]}"
+    err = (np.abs(got["t"] - emu["t"]) * np.linalg.norm(rays["dir"], axis=1))[keep]
+    print(f"{what}: largest |t| difference to the emulation {err.max():.3e} m")
+    assert err.max() <= 1e-4, f"{what}: {err.max():.3e} m"
+    hit = got["kind"] == LR.HIT
+    if hit.any():
+        assert np.abs(got["lon_deg"][hit] - emu["lon_deg"][hit]).max() < 1e-9 and np.abs(got["lat_deg"][hit] - emu["lat_deg"][hit]).max() < 1e-9
+        assert np.abs(got["height_m"][hit] - emu["height_m"][hit].astype(np.float32)).max() <= 1e-3
+        assert np.abs(got["w1"][hit] - emu["w1"][hit]).max() < 1e-5 and np.abs(got["w2"][hit] - emu["w2"][hit]).max() < 1e-5
+    z = got[~hit]
+    assert not z["t"].any() and not z["lon_deg"].any() and not z["cell_x"].any() and not z["w1"].any(), "every other field of a non-hit is 0"
+    return float(err.max())

@@ -7,14 +7,9 @@
 #include <vector>
 
 #include "../topo-renderer_amd/csrc/topo_los.h"
+#include "emul_tiles.h"
 
 using namespace topo;
-
-struct EmulLosTile {
-    const float* heights;
-    float tf[6];           // raster_point, model_point, pixel_scale
-    int32_t lat, lon;
-};
 
 struct EmulLosOut {        // topo_ray_hit's fields, the computed ones in f64, plus the winner's rank and triangle
     double t, lon_deg, lat_deg, height, w1, w2;
@@ -29,7 +24,7 @@ struct EmulScene {
     std::vector<std::vector<float>> minmax;
     std::vector<std::vector<double>> bounds;
     LosScene S;
-    EmulScene(const EmulLosTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h) {
+    EmulScene(const EmulGeoTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h) {
         const uint32_t bxc = (tile_w - 1 + kLosBCX - 1) / kLosBCX, byc = (tile_h - 1 + kLosBCY - 1) / kLosBCY, nb = bxc * byc;
         const size_t tab = ground_table_doubles(tile_w, tile_h);
         dev.resize(n_tiles);
@@ -39,14 +34,8 @@ struct EmulScene {
         bounds.resize(n_tiles);
         for (uint32_t r = 0; r < n_tiles; ++r) {
             TileDev& t = dev[r];
-            t = TileDev{};
-            t.heights = tiles[r].heights;
-            t.raster_x = tiles[r].tf[0]; t.raster_y = tiles[r].tf[1];
-            t.model_x = tiles[r].tf[2]; t.model_y = tiles[r].tf[3];
-            t.scale_x = tiles[r].tf[4]; t.scale_y = tiles[r].tf[5];
-            double* tg = trig.data() + tab * r;
-            for (uint32_t x = 0; x < tile_w; ++x) ground_trig_lon(t, x, tg[2 * x], tg[2 * x + 1]);
-            for (uint32_t y = 0; y < tile_h; ++y) ground_trig_lat(t, y, tg[2 * (tile_w + y)], tg[2 * (tile_w + y) + 1]);
+            t = make_dev(tiles[r]);
+            fill_trig(t, tile_w, tile_h, trig.data() + tab * r);
             minmax[r].assign(2 * (size_t)nb, 0.0f);
             bounds[r].assign(4 * (size_t)nb, 0.0);
             double tc[3] = {0.0, 0.0, 0.0}, rmax = 0.0;
@@ -99,7 +88,7 @@ struct EmulScene {
 };
 
 // mode 0: the traversal; 1: every triangle.  Returns the number of index checks that failed.
-extern "C" int emul_raycast(const EmulLosTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, const LosRay* rays, uint32_t n, int mode,
+extern "C" int emul_raycast(const EmulGeoTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, const LosRay* rays, uint32_t n, int mode,
                             EmulLosOut* out) {
     EmulScene scene(tiles, n_tiles, tile_w, tile_h);
     const LosScene& S = scene.S;
@@ -133,7 +122,7 @@ extern "C" int emul_raycast(const EmulLosTile* tiles, uint32_t n_tiles, uint32_t
 
 // The sunlit class (los_sunlit) of n ground points: triangle tri[i] of tile rank[i] with plane weights w1[i], w2[i] (ground_solve's).
 // mode as emul_raycast.  Returns the number of index checks that failed.
-extern "C" int emul_sunlit(const EmulLosTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, uint32_t n, const uint32_t* rank, const uint32_t* tri,
+extern "C" int emul_sunlit(const EmulGeoTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, uint32_t n, const uint32_t* rank, const uint32_t* tri,
                            const double* w1, const double* w2, const double* sun, uint8_t* out) {
     EmulScene scene(tiles, n_tiles, tile_w, tile_h);
     int bad = 0;

@@ -2,73 +2,45 @@
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "_build", "liblos_emul.so")
+import native
+from emul_tiles import RAY_DTYPE, geo_tile_array, vp
+
 _LIB = None
 
 OUT_DTYPE = np.dtype([("t", "<f8"), ("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f8"), ("w1", "<f8"), ("w2", "<f8"),
                       ("kind", "<i4"), ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"),
                       ("front", "<u4"), ("rank", "<u4"), ("triangle", "<u4"), ("_pad", "<u4")])
-RAY_DTYPE = np.dtype([("origin", "<f8", 3), ("dir", "<f8", 3), ("t_min", "<f8"), ("t_max", "<f8")])      # = topo_ray
-
-
-class EmulLosTile(C.Structure):
-    _fields_ = [("heights", C.c_void_p), ("tf", C.c_float * 6), ("lat", C.c_int32), ("lon", C.c_int32)]
-
 
 def lib():
     global _LIB
     if _LIB is None:
-        src = os.path.join(_HERE, "los_emul.cpp")
-        hdrs = [os.path.join(_HERE, "..", "topo-renderer_amd", "csrc", f) for f in ("topo_math.h", "topo_pipeline.h", "topo_ground.h", "topo_los.h")]
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if not os.path.exists(_SO) or any(os.path.getmtime(f) > os.path.getmtime(_SO) for f in [src] + hdrs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-shared", "-o", _SO, src])
-        _LIB = C.CDLL(_SO)
-        _LIB.emul_raycast.restype = C.c_int
-        assert C.sizeof(EmulLosTile) == 40 and OUT_DTYPE.itemsize == 88 and RAY_DTYPE.itemsize == 64
+        _LIB = native.load("liblos_emul.so", ["los_emul.cpp"], {"emul_raycast": C.c_int, "emul_sunlit": C.c_int})
+        assert OUT_DTYPE.itemsize == 88
     return _LIB
-
-
-def _tile_array(tiles, order):
-    keep = [np.ascontiguousarray(t[0], np.float32) for t in tiles]
-    arr = (EmulLosTile * len(tiles))()
-    for e, hts, t, (lat, lon) in zip(arr, keep, tiles, order):
-        e.heights = hts.ctypes.data
-        for i, v in enumerate(list(np.asarray(t[1], np.float32)) + list(np.asarray(t[2], np.float32)) + list(np.asarray(t[3], np.float32))):
-            e.tf[i] = float(v)
-        e.lat, e.lon = int(lat), int(lon)
-    return arr, keep
 
 
 def sunlit(tiles, order, rank, tri, w1, w2, sun):
     """The sunlit class (0 none, 1 lit, 2 away, 3 shadow) of the ground points (triangle tri of tile rank, plane weights w1, w2 as
     ground_solve gives them) under a sun in unit direction `sun`; rank >= len(tiles): no point.  -> (uint8 classes, failed checks)."""
-    arr, keep = _tile_array(tiles, order)
+    arr, keep = geo_tile_array(tiles, order)
     th, tw = keep[0].shape
     rank, tri = np.ascontiguousarray(rank, np.uint32).reshape(-1), np.ascontiguousarray(tri, np.uint32).reshape(-1)
     w1, w2 = np.ascontiguousarray(w1, np.float64).reshape(-1), np.ascontiguousarray(w2, np.float64).reshape(-1)
     s = np.ascontiguousarray(sun, np.float64).reshape(3)
     out = np.zeros(len(rank), np.uint8)
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    L = lib()
-    L.emul_sunlit.restype = C.c_int
-    bad = L.emul_sunlit(arr, len(tiles), tw, th, len(rank), vp(rank), vp(tri), vp(w1), vp(w2), vp(s), vp(out))
+    bad = lib().emul_sunlit(arr, len(tiles), tw, th, len(rank), vp(rank), vp(tri), vp(w1), vp(w2), vp(s), vp(out))
     return out, int(bad)
 
 
 def raycast(tiles, order, rays, brute=False):
     """tiles: [(heights f32 (h, w), raster_point, model_point, pixel_scale)] in draw order, order: their (lat, lon); rays: RAY_DTYPE
     records -> (OUT_DTYPE records, failed index checks).  brute: every triangle instead of the traversal."""
-    arr, keep = _tile_array(tiles, order)
+    arr, keep = geo_tile_array(tiles, order)
     th, tw = keep[0].shape
     r = np.ascontiguousarray(rays, dtype=RAY_DTYPE).reshape(-1)
     out = np.zeros(len(r), OUT_DTYPE)
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
     bad = lib().emul_raycast(arr, len(tiles), tw, th, vp(r), len(r), 1 if brute else 0, vp(out))
     return out, int(bad)

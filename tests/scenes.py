@@ -155,3 +155,35 @@ def glyph_scene(W, H, n_labels=14, seed=7):
     g["pos"], g["dim"], g["uv"], g["color"], g["content_type_with_srgb"], g["depth"] = (W // 2, H // 2), (20, 20), (aw - 8, ah - 8), 0xFF2040FF, (1, 1), 100.0 / 4096.0
     glyphs.append(g)
     return np.array(glyphs, dtype=GLYPH), atlas
+
+
+def relief(lat, lon):
+    """Strong, asymmetric relief at the scale of a coarse test tile (the fBm of the benchmark tiles is almost flat over
+    a 24-texel degree): kilometre-high ridges a tenth of a degree apart, no symmetry between the axes."""
+    return 1500.0 + 900.0 * np.sin(np.radians(37.0 * lon + 11.0 * lat)) * np.cos(np.radians(53.0 * lat)) \
+        + 500.0 * np.sin(np.radians(140.0 * lon)) + 0.0 * lat
+
+
+# the scenes of tests/test_ray_check_cpu.py, which the ground tests take too
+RELIEF_SCENES = [
+    # tile, n_lat, n_lon, lat0, lon0, W, H, yaw, pitch, fov, eye_dh
+    # (coarse tiles: vertices kilometres apart, so the eye sits kilometres up to be above the mesh it looks at)
+    (24, 2, 2, 45, 15, 96, 64, 30.0, 25.0, 60.0, 4000.0),      # north-east quadrant, four tiles, the gaps between them in view
+    (32, 1, 1, 45, 15, 80, 80, 250.0, 60.0, 90.0, 6000.0),     # steeply down: triangles tens of px across
+    (16, 3, 3, -34, -71, 96, 48, 200.0, 30.0, 79.28, 8000.0),  # southern + western hemisphere, panorama sector FOV
+]
+
+# the single frames of tests/test_gpu_parity.py, which tests/test_oracle_window_cpu.py takes too
+FRAMES = [
+    # tile, n_lat, n_lon, W, H, yaw, pitch, fov, mode, eye_dh
+    (64, 1, 1, 128, 64, 0, 0, 60, 0, 50),
+    (64, 1, 1, 128, 64, 0, 0, 60, 1, 50),
+    (64, 1, 1, 128, 64, 0, 0, 60, 2, 50),
+    (64, 2, 2, 128, 64, 30, 10, 60, 0, 50),
+    (48, 3, 3, 160, 96, 200, 30, 79.28, 0, 50),
+    (128, 2, 2, 256, 128, 123, -5, 45, 0, 50),
+    (64, 2, 2, 128, 128, 77, 60, 100, 0, 100),     # big near-field triangles, near-plane clipping
+    (64, 2, 2, 128, 128, 77, 85, 100, 1, 400),
+    (256, 1, 1, 300, 200, 10, 45, 90, 0, 20),
+    (200, 1, 2, 257, 131, 300, 20, 120, 2, 80),     # odd sizes
+]

@@ -6,14 +6,9 @@
 #include <vector>
 
 #include "../topo-renderer_amd/csrc/topo_surface.h"
+#include "emul_tiles.h"
 
 using namespace topo;
-
-struct EmulSurfaceTile {
-    const float* heights;
-    float tf[6];           // raster_point, model_point, pixel_scale
-    int32_t lat, lon;
-};
 
 struct EmulSurfaceOut {    // topo_surface_point's fields, the computed ones in f64, plus the winner's rank and triangle
     double height, slope_deg, aspect_deg, w1, w2;
@@ -31,27 +26,20 @@ struct EmulSurfaceScene {
     std::vector<TileDev> dev;
     std::vector<double> trig;
     LosScene S;
-    EmulSurfaceScene(const EmulSurfaceTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h) {
+    EmulSurfaceScene(const EmulGeoTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h) {
         const size_t tab = ground_table_doubles(tile_w, tile_h);
         dev.resize(n_tiles);
         trig.assign(tab * n_tiles + 2, 0.0);
         for (uint32_t r = 0; r < n_tiles; ++r) {
-            TileDev& t = dev[r];
-            t = TileDev{};
-            t.heights = tiles[r].heights;
-            t.raster_x = tiles[r].tf[0]; t.raster_y = tiles[r].tf[1];
-            t.model_x = tiles[r].tf[2]; t.model_y = tiles[r].tf[3];
-            t.scale_x = tiles[r].tf[4]; t.scale_y = tiles[r].tf[5];
-            double* tg = trig.data() + tab * r;
-            for (uint32_t x = 0; x < tile_w; ++x) ground_trig_lon(t, x, tg[2 * x], tg[2 * x + 1]);
-            for (uint32_t y = 0; y < tile_h; ++y) ground_trig_lat(t, y, tg[2 * (tile_w + y)], tg[2 * (tile_w + y) + 1]);
+            dev[r] = make_dev(tiles[r]);
+            fill_trig(dev[r], tile_w, tile_h, trig.data() + tab * r);
         }
         S = LosScene{dev.data(), trig.data(), nullptr, tab * n_tiles, n_tiles, tile_w, tile_h, 0u, 0u};      // (no block tables, no spheres: not read)
     }
 };
 
 // mode 0: the lookup; 1: every triangle.  Returns the number of index checks that failed.
-extern "C" int emul_surface(const EmulSurfaceTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, const double* lonlat, uint32_t n, int mode,
+extern "C" int emul_surface(const EmulGeoTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, const double* lonlat, uint32_t n, int mode,
                             EmulSurfaceOut* out) {
     EmulSurfaceScene scene(tiles, n_tiles, tile_w, tile_h);
     const LosScene& S = scene.S;
@@ -87,7 +75,7 @@ extern "C" int emul_surface(const EmulSurfaceTile* tiles, uint32_t n_tiles, uint
 
 // n segments of m samples each: samples (n x m x (terrain, line), f32) and summaries, reduced as k_profile reduces them (64 partials
 // that take every 64th sample, merged pairwise over six exchange steps).  Returns the number of index checks that failed.
-extern "C" int emul_profile(const EmulSurfaceTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, const LosRay* segs, uint32_t n, uint32_t m,
+extern "C" int emul_profile(const EmulGeoTile* tiles, uint32_t n_tiles, uint32_t tile_w, uint32_t tile_h, const LosRay* segs, uint32_t n, uint32_t m,
                             float* samples, EmulSummary* summary) {
     EmulSurfaceScene scene(tiles, n_tiles, tile_w, tile_h);
     int bad = 0;

@@ -310,17 +310,9 @@ def test_raster_rows_stays_in_bounds_and_matches_triangle_pixel():
 def _limits_driver(kind):
     """tests/limits_emul.cpp built as its own program: "opt" as host_emul.cpp is built, "ubsan" at -O0 with every undefined
     behaviour the sanitizer knows fatal (at -O1 and above g++ folds some of the overflowing products away unchecked)."""
-    import os
-    import subprocess
-    here = os.path.dirname(os.path.abspath(__file__))
-    src = os.path.join(here, "limits_emul.cpp")
-    hdrs = [os.path.join(here, "..", "topo-renderer_amd", "csrc", f) for f in ("topo_math.h", "topo_pipeline.h")]
-    exe = os.path.join(here, "_build", "limits_emul_" + kind)
-    flags = ["-O2"] if kind == "opt" else ["-O0", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=all"]
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    if not os.path.exists(exe) or any(os.path.getmtime(f) > os.path.getmtime(exe) for f in [src] + hdrs):
-        subprocess.check_call(["g++", *flags, "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-o", exe, src])
-    return exe
+    import native
+    flags = native.DEFAULT_FLAGS if kind == "opt" else ("-O0", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=all", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma")
+    return native.build("limits_emul_" + kind, ["limits_emul.cpp"], flags=flags, shared=False)
 
 
 def _run_limits(kind, *args):

@@ -19,14 +19,10 @@ import los_ref as LR
 import topo_renderer_amd as T
 import unwrap_cases as UC
 import unwrap_ref as UR
-from horizon_ref import horizon
+from gpu_support import ground_map, renderer, sunlit_map, unwrap_run
+from horizon_ref import assert_view, horizon
 from scenes import assert_same_frame
-from test_ground_gpu import _all_pixels, _assert_map_is_list, _assert_sky, _map
-from test_horizon_gpu import _assert_view
-from test_raycast_gpu import _against_emulation, _renderer, _sunlit
-from test_unwrap_gpu import run as unwrap_run
-from test_viewshed_gpu import _assert_masks
-from viewshed_ref import expected_masks
+from viewshed_ref import assert_masks, expected_masks
 
 pytestmark = pytest.mark.gpu
 
@@ -85,7 +81,7 @@ def test_frame_and_normals(topo, orc, name):
 def test_ground(topo, orc, name):
     p, g, o = pair(topo, orc, name)
     tiles = GR.scene_tiles(p.scene)
-    q = _all_pixels(topo, [0], p.W, p.H)
+    q = GR.all_pixels(topo, [0], p.W, p.H)
     named = set()
     for k, (u, d, w) in enumerate(winners(orc, name)):
         what = f"{name} pose {k}"
@@ -95,9 +91,9 @@ def test_ground(topo, orc, name):
         GR.compare(got, want, what)
         assert np.array_equal(got["depth"].view(np.uint32), np.asarray(frame[1], np.float32).view(np.uint32)), f"{what}: depth differs from the frame's depth output"
         assert (got["kind"] != -3).all(), what
-        _assert_sky(got, what)
-        vals, pad = _map(g, 1, p.W, p.H, pad_px=3, pad_rows=1)
-        _assert_map_is_list(vals, got.reshape(1, p.H, p.W), what)
+        GR.assert_sky(got, what)
+        vals, pad = ground_map(g, 1, p.W, p.H, pad_px=3, pad_rows=1)
+        GR.assert_map_is_list(vals, got.reshape(1, p.H, p.W), what)
         assert (pad == 0xAB).all()
         t = got["kind"] == 1
         mine = set(zip(got["tile_lat_deg"][t].tolist(), got["tile_lon_deg"][t].tolist()))
@@ -117,7 +113,7 @@ def test_horizon(topo, orc, name):
         frame = _render(topo, p, g, u)
         assert g.horizon_shape() == (1, p.W, p.H)
         got = g.horizon()
-        _assert_view(got[0], horizon(d, w, p.scene.locs, GS.TILE, GS.TILE), f"{name} pose {k}", frame[1])
+        assert_view(got[0], horizon(d, w, p.scene.locs, GS.TILE, GS.TILE), f"{name} pose {k}", frame[1])
         assert (got[0]["row"] >= 0).any()
 
 
@@ -131,7 +127,7 @@ def test_viewshed(topo, orc, name):
     g.viewshed_enable(False)
     want = expected_masks([w for _, _, w in winners(orc, name)], p.scene.locs, GS.TILE, GS.TILE)
     assert set(want) == set(p.scene.locs)
-    _assert_masks(g, want, name)
+    assert_masks(g, want, name)
     seen = {loc for loc, m in want.items() if m.any()}
     assert SEEN.get(name, set()) <= seen and seen
     for loc in set(p.scene.locs) - seen:
@@ -171,7 +167,7 @@ def test_sunlit(topo, orc, name):
     p.scene.load(g)
     for k, (u, sun, ref, amb, emu) in enumerate(poses):
         _render(topo, p, g, u)
-        got, pad = _sunlit(g, sun, 1, p.W, p.H, pad_px=5, pad_rows=2)
+        got, pad = sunlit_map(g, sun, 1, p.W, p.H, pad_px=5, pad_rows=2)
         assert (pad == 0xAB).all()
         got = got[0]
         terrain = ref != LR.NONE
@@ -290,13 +286,13 @@ def test_full_size_tile_rays(topo):
     brute, bad_b = LE.raycast(tiles, order, rays[::8], brute=True)
     t1 = time.time()
     assert bad == 0 and bad_b == 0
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     got = g.raycast(rays)
     g.close()
     print(f"full-size tile: {len(rays)} rays, {int((got['kind'] == 1).sum())} hits; the g++ builds took {t1 - t0:.1f} s")
     everyone = np.ones(len(rays), bool)
-    _against_emulation(got, emu, rays, "full-size tile", everyone)
-    _against_emulation(got[::8], brute, rays[::8], "full-size tile, every triangle", everyone[::8])
+    LC.against_emulation(got, emu, rays, "full-size tile", everyone)
+    LC.against_emulation(got[::8], brute, rays[::8], "full-size tile, every triangle", everyone[::8])
     hit = got["kind"] == topo.RAY_HIT
     assert hit.mean() > 0.4 and (got["kind"] == topo.RAY_MISS).mean() > 0.15
     blk = LC.block_of(got["cell_x"][hit], got["cell_y"][hit], 1200)

@@ -8,7 +8,8 @@ import os
 import numpy as np
 import pytest
 
-from scenes import Scene, assert_same_frame
+from gpu_support import checked_script, strip_host
+from scenes import FRAMES, Scene, assert_same_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -147,21 +148,6 @@ def test_normals_insertion_order_and_unload(topo, orc):
         assert np.array_equal(g2.read_normals(*loc), o2.read_normals(loc[0], loc[1], 40, 40))
 
 
-FRAMES = [
-    # tile, n_lat, n_lon, W, H, yaw, pitch, fov, mode, eye_dh
-    (64, 1, 1, 128, 64, 0, 0, 60, 0, 50),
-    (64, 1, 1, 128, 64, 0, 0, 60, 1, 50),
-    (64, 1, 1, 128, 64, 0, 0, 60, 2, 50),
-    (64, 2, 2, 128, 64, 30, 10, 60, 0, 50),
-    (48, 3, 3, 160, 96, 200, 30, 79.28, 0, 50),
-    (128, 2, 2, 256, 128, 123, -5, 45, 0, 50),
-    (64, 2, 2, 128, 128, 77, 60, 100, 0, 100),     # big near-field triangles, near-plane clipping
-    (64, 2, 2, 128, 128, 77, 85, 100, 1, 400),
-    (256, 1, 1, 300, 200, 10, 45, 90, 0, 20),
-    (200, 1, 2, 257, 131, 300, 20, 120, 2, 80),     # odd sizes
-]
-
-
 @pytest.mark.parametrize("cfg", FRAMES, ids=[f"f{i}" for i in range(len(FRAMES))])
 def test_frame_bit_exact(topo, orc, cfg):
     tile, n_lat, n_lon, W, H, yaw, pitch, fov, mode, dh = cfg
@@ -289,17 +275,6 @@ def test_gpu_reproduces_golden(topo, name):
             assert np.array_equal(depth.view(np.uint32), g["depth_bits"])
 
 
-def _strip(topo, r, views, sw, sh):
-    import torch
-    n = len(views)
-    rgba = torch.zeros((n, sh, sw, 4), dtype=torch.uint8, device="cuda")
-    depth = torch.zeros((n, sh, sw), dtype=torch.float32, device="cuda")
-    r.set_stream(torch.cuda.current_stream().cuda_stream)
-    r.render_views_device(views, sw, sh, rgba.data_ptr(), sh * sw * 4, sw * 4, depth.data_ptr(), sh * sw * 4, sw * 4)
-    torch.cuda.synchronize()
-    return rgba.cpu().numpy(), depth.cpu().numpy()
-
-
 def test_full_size_config2_against_oracle_and_properties(topo, orc):
     # BASELINE config 2: one 1200x1200 COP90-shaped tile, 4096x1024 panorama (8 sectors of 512x1024), f32
     sc = Scene(1200, 1, 1, lat0=40, lon0=10, vfrac=(0.623, 0.717))
@@ -307,12 +282,12 @@ def test_full_size_config2_against_oracle_and_properties(topo, orc):
     r = topo.TerrainRenderer(sw, sh)
     sc.load(r)
     views = sc.panorama(sw, sh)
-    rgba, depth = _strip(topo, r, views, sw, sh)
+    rgba, depth = strip_host(r, views, sw, sh)
     # idempotence + independence from how the sectors are batched (the multi-GPU sharding property)
-    rgba2, depth2 = _strip(topo, r, views, sw, sh)
+    rgba2, depth2 = strip_host(r, views, sw, sh)
     assert np.array_equal(rgba, rgba2) and np.array_equal(depth.view(np.uint32), depth2.view(np.uint32))
     for lo, hi in ((0, 4), (4, 8), (2, 3)):
-        ra, da = _strip(topo, r, views[lo:hi], sw, sh)
+        ra, da = strip_host(r, views[lo:hi], sw, sh)
         assert np.array_equal(ra, rgba[lo:hi]) and np.array_equal(da.view(np.uint32), depth[lo:hi].view(np.uint32))
     # every sector is a complete reference frame: compare all 8 with the oracle
     o = orc.OracleRenderer(sw, sh)
@@ -767,10 +742,10 @@ def test_full_size_config4_sectors_against_oracle(topo, orc):
     eye = topo.geometry_transform(ground + 50.0, vlon, vlat)
     views = topo.panorama_uniforms(eye, 0.0, sw, sh, vlon, vlat, 0)
     pick = [views[1], views[6]]
-    rg, dg = _strip(topo, g, pick, sw, sh)
+    rg, dg = strip_host(g, pick, sw, sh)
     c_on = g.counters()
     g.set_occlusion_split(0.0)
-    rg0, dg0 = _strip(topo, g, pick, sw, sh)
+    rg0, dg0 = strip_host(g, pick, sw, sh)
     c_off = g.counters()
     assert np.array_equal(rg, rg0) and np.array_equal(dg.view(np.uint32), dg0.view(np.uint32))
     assert c_on["far_tested"] > 10 * c_on["far_survived"] and c_off["far_tested"] == 0
@@ -786,7 +761,7 @@ def test_full_size_config4_sectors_against_oracle(topo, orc):
     want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "c4_sector_sha256.json")))
     assert want["sector_w"] == sw and want["sector_h"] == sh and want["n_tiles"] == len(locs)
     g.set_occlusion_split(90000.0)
-    ra, da = _strip(topo, g, views, sw, sh)
+    ra, da = strip_host(g, views, sw, sh)
     for k in range(8):
         assert hashlib.sha256(np.ascontiguousarray(ra[k]).tobytes()).hexdigest() == want["rgba"][k], f"sector {k}: colour bytes differ from the oracle's"
         assert hashlib.sha256(np.ascontiguousarray(da[k]).tobytes()).hexdigest() == want["depth"][k], f"sector {k}: depth bits differ from the oracle's"
@@ -1239,7 +1214,7 @@ def test_config1_single_tile_small_panorama(topo, orc):
     sc.load(o)
     for mode in (0, 1, 2):
         views = sc.panorama(sw, sh, mode=mode)
-        rgba, depth = _strip(topo, g, views, sw, sh)
+        rgba, depth = strip_host(g, views, sw, sh)
         o.update(sw, sh, views[0], topo.post_uniforms(sw, sh))
         ro, do = o.render_views(views, threads=8)
         for k in range(8):
@@ -1249,7 +1224,7 @@ def test_config1_single_tile_small_panorama(topo, orc):
     # split above the farthest block and leaves the far phase's four launches out
     assert not g.debug_far_phase_launched() and g.counters()["far_tested"] == 0
     g.set_occlusion_split(30000.0)          # ... which a split well inside the tile does not allow
-    rgba2, depth2 = _strip(topo, g, views, sw, sh)
+    rgba2, depth2 = strip_host(g, views, sw, sh)
     assert g.debug_far_phase_launched() and g.counters()["far_tested"] > 0
     assert np.array_equal(rgba2, rgba) and np.array_equal(depth2.view(np.uint32), depth.view(np.uint32))
 
@@ -1262,10 +1237,10 @@ def test_config3_mosaic25_sector_and_batching(topo, orc):
     sc.load(g)
     sc.load(o)
     views = sc.panorama(sw, sh)
-    rgba, depth = _strip(topo, g, views, sw, sh)
+    rgba, depth = strip_host(g, views, sw, sh)
     # whole-panorama batching invariance: one submission = two halves = eight single-view submissions
     for lo, hi in ((0, 4), (4, 8)) + tuple((k, k + 1) for k in (0, 3, 7)):
-        ra, da = _strip(topo, g, views[lo:hi], sw, sh)
+        ra, da = strip_host(g, views[lo:hi], sw, sh)
         assert np.array_equal(ra, rgba[lo:hi]) and np.array_equal(da.view(np.uint32), depth[lo:hi].view(np.uint32)), (lo, hi)
     # one full-size sector against the oracle (seams between the 25 tiles are in view), + its normals
     k = 5
@@ -1312,7 +1287,7 @@ def test_config5_batch_submission_over_the_mosaic(topo, orc, mosaic100):
             eye = topo.geometry_transform(ground + 50.0, lon, lat)
             vs += topo.panorama_uniforms(eye, yaw, sw, sh, lon, lat, 0)
         sets.append(vs)
-    serial = [_strip(topo, g, vs, sw, sh) for vs in sets]
+    serial = [strip_host(g, vs, sw, sh) for vs in sets]
     g.set_pipeline_depth(2)
     outs = [(torch.zeros((64, sh, sw, 4), dtype=torch.uint8, device="cuda"), torch.zeros((64, sh, sw), dtype=torch.float32, device="cuda")) for _ in range(2)]
     for rep in range(2):
@@ -1387,23 +1362,12 @@ def test_add_terrain_device_entry_point(topo, orc):
 
 
 def test_bounds_checked_build_is_clean_and_identical(topo):
-    """libtopo_hip_check.so = the product with every device-side index tested before use (TOPO_BOUNDS_CHECK; the GPU
+    """The bounds-checked build = the product with every device-side index tested before use (TOPO_BOUNDS_CHECK; the GPU
     address sanitizer this pool does not offer).  The scenes of tests/bounds_scenes.py -- near-field giants, clipping, queue
     overflows, a 64-view submission, odd sizes, a full-size config-2 panorama, frames in flight -- run through it in a
     child process: no index may be out of range, and every frame must hash to what the product build renders."""
-    import json
-    import os
-    import subprocess
-    import sys
     import bounds_scenes
-    check = os.path.join(os.path.dirname(topo.LIB_PATH), "libtopo_hip_check.so")
-    assert os.path.exists(check), "run __graft_entry__.build()"
-    env = dict(os.environ, TOPO_HIP_LIB=check)
-    out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "bounds_scenes.py")], env=env,
-                         capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    got = json.loads(out.stdout.strip().split("\n")[-1])
-    assert got["lib"].endswith("libtopo_hip_check.so")
+    got = checked_script("bounds_scenes.py", 900)
     want = bounds_scenes.run(topo)
     assert set(got["cases"]) == set(want["cases"]) and len(want["cases"]) >= 12
     for name, c in got["cases"].items():
@@ -1466,7 +1430,7 @@ def test_two_rank_panorama_over_rccl(topo, tmp_path):
     sw, sh = 96, 160
     g = topo.TerrainRenderer(sw, sh)
     sc.load(g)
-    ra, _ = _strip(topo, g, sc.panorama(sw, sh, yaw0_deg=25.0), sw, sh)
+    ra, _ = strip_host(g, sc.panorama(sw, sh, yaw0_deg=25.0), sw, sh)
     for rk in (0, 1):
         assert np.array_equal(np.load(os.path.join(str(tmp_path), f"strip{rk}.npy")), ra), f"rank {rk}'s strip differs from the world-of-one strip"
 
@@ -1492,7 +1456,7 @@ def test_panorama_and_batch_entry_points(topo, orc):
         g.render_panorama(use_comm, sc.eye, yaw0, sw, sh, sc.vlon, sc.vlat, strip.data_ptr(), depth.data_ptr())
         g.synchronize()
         views = sc.panorama(sw, sh, yaw0_deg=25.0)
-        ra, da = _strip(topo, g, views, sw, sh)
+        ra, da = strip_host(g, views, sw, sh)
         assert np.array_equal(strip.cpu().numpy(), ra) and np.array_equal(depth.cpu().numpy().view(np.uint32), da.view(np.uint32))
     o.update(sw, sh, views[3], topo.post_uniforms(sw, sh))
     assert_same_frame((ra[3], da[3]), o.render(), "panorama sector 3")
@@ -1524,7 +1488,7 @@ def test_panorama_and_batch_entry_points(topo, orc):
     g.set_pipeline_depth(1)
     for v in (0, 7, 8, 10):
         views = topo.panorama_uniforms(eyes[v], yaws[v], sw, sh, suns[v][0], suns[v][1], 0)
-        ra, da = _strip(topo, g, views, sw, sh)
+        ra, da = strip_host(g, views, sw, sh)
         assert np.array_equal(out[v].cpu().numpy(), ra) and np.array_equal(dout[v].cpu().numpy().view(np.uint32), da.view(np.uint32)), v
     o.update(sw, sh, views[5], topo.post_uniforms(sw, sh))
     assert_same_frame((out[10, 5].cpu().numpy(), dout[10, 5].cpu().numpy()), o.render(), "batch viewpoint 10 sector 5")

@@ -13,8 +13,7 @@ import pytest
 import geo_scenes as GS
 import ground_ref as GR
 from oracle import ray_check as RC
-from scenes import Scene
-from test_ray_check_cpu import SCENES, relief
+from scenes import RELIEF_SCENES as SCENES, Scene, relief
 from viewshed_ref import geo_order
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

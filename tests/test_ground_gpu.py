@@ -2,37 +2,25 @@
 give, and the positions lie within 1e-3 m of the numpy f64 reference (tests/ground_ref.py, itself checked against the f64 ray caster
 and the product's lane function on the CPU by tests/test_ground_cpu.py); the dense map equals the list bit for bit."""
 import hashlib
-import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import ground_ref as GR
+from gpu_support import checked_run, ground_map, pair, strip
+from horizon_ref import FRAMES
 from scenes import Scene
-from test_horizon_gpu import FRAMES
 from viewshed_ref import geo_order
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 FRAME = dict(zip(["2x2_dh50", "2x2_dh100_p60", "1x1_dh400_p85", "coarse12", "odd_width", "past_edge"], FRAMES))
-NAN_BITS = 0x7FC00000
 
 
 def _scene(cfg):
     tile, nla, nlo, dh, W, H, views = cfg
     return Scene(tile, nla, nlo, eye_dh=dh, vfrac=(0.5, 0.97) if W == 190 else (0.5123, 0.5217))
-
-
-def _pair(topo, orc, sc, W, H):
-    g, o = topo.TerrainRenderer(W, H), orc.OracleRenderer(W, H)
-    sc.load(g)
-    sc.load(o)
-    return g, o
 
 
 def _expect(o, sc, W, H, views, pu):
@@ -45,53 +33,14 @@ def _expect(o, sc, W, H, views, pu):
     return out
 
 
-def _all_pixels(topo, views, W, H):
-    """Queries for every pixel of the given view indices, view-major then row-major."""
-    v, y, x = np.meshgrid(np.asarray(views), np.arange(H), np.arange(W), indexing="ij")
-    return topo.ground_queries(np.stack([v.ravel(), x.ravel(), y.ravel()], axis=-1))
-
-
-def _assert_sky(got, what):
-    sky = got[got["kind"] == 0]
-    assert (sky["depth"] == 1.0).all(), what
-    blank = sky.copy()
-    blank["depth"] = 0
-    assert not blank.view(np.uint8).any(), f"{what}: a sky record carries something besides depth 1.0"
-
-
-def _map(g, n, W, H, first=0, pad_px=0, pad_rows=0):
-    """ground_map_device of views [first, first + n) into a torch tensor whose rows are pad_px pixels and whose views are pad_rows
-    rows longer than needed: ((n, H, W, 4) f32 values, the padding bytes)."""
-    import torch
-    pitch = (W + pad_px) * 16
-    stride = pitch * (H + pad_rows)
-    buf = torch.full((n * stride,), 0xAB, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    g.ground_map_device(buf.data_ptr(), first, n, stride, pitch)
-    g.synchronize()
-    raw = buf.cpu().numpy().reshape(n, H + pad_rows, W + pad_px, 16)
-    vals = np.ascontiguousarray(raw[:, :H, :W]).view(np.float32).reshape(n, H, W, 4)
-    pad = np.concatenate([raw[:, :H, W:].ravel(), raw[:, H:].ravel()])
-    return vals, pad
-
-
-def _assert_map_is_list(vals, rec, what):
-    """vals (..., 4) f32 of the map, rec (...) list records of the same pixels: np.float32 of the record bit for bit, NaN elsewhere."""
-    t = rec["kind"] == 1
-    want = np.stack([rec["lon_deg"].astype(np.float32), rec["lat_deg"].astype(np.float32), rec["height_m"], rec["range_m"]], axis=-1).view(np.uint32)
-    want = np.where(t[..., None], want, np.uint32(NAN_BITS))
-    bad = np.argwhere(vals.view(np.uint32) != want)
-    assert len(bad) == 0, f"{what}: the map differs from the list in {len(bad)} values (first {tuple(bad[0])}: {vals[tuple(bad[0])]!r} vs record {rec[tuple(bad[0][:-1])]})"
-
-
 @pytest.mark.parametrize("name", ["2x2_dh50", "2x2_dh100_p60", "odd_width", "past_edge"])
 def test_every_pixel_by_list(topo, orc, name):
     cfg = FRAME[name]
     tile, nla, nlo, dh, W, H, views = cfg
     sc = _scene(cfg)
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     pu = topo.post_uniforms(W, H)
-    q = _all_pixels(topo, [0], W, H)
+    q = GR.all_pixels(topo, [0], W, H)
     kinds = []
     for yaw, pitch, fov in views:
         u = sc.uniforms(W, H, yaw, pitch, fov, 0)
@@ -103,7 +52,7 @@ def test_every_pixel_by_list(topo, orc, name):
         GR.compare(got, want, what)
         assert np.array_equal(got["depth"].view(np.uint32), np.asarray(frame[1], np.float32).view(np.uint32)), f"{what}: depth differs from the frame's depth output"
         assert (got["kind"] != -3).all(), what
-        _assert_sky(got, what)
+        GR.assert_sky(got, what)
         kinds.append(got["kind"])
     kinds = np.concatenate([k.ravel() for k in kinds])
     assert (kinds == 1).any()
@@ -123,25 +72,16 @@ def test_dense_map_equals_the_list(topo, name):
     yaw, pitch, fov = views[0]
     g.update(W, H, sc.uniforms(W, H, yaw, pitch, fov, 0), topo.post_uniforms(W, H))
     g.render()
-    rec = g.ground(_all_pixels(topo, [0], W, H)).reshape(1, H, W)
-    vals, pad = _map(g, 1, W, H)
+    rec = g.ground(GR.all_pixels(topo, [0], W, H)).reshape(1, H, W)
+    vals, pad = ground_map(g, 1, W, H)
     assert len(pad) == 0
-    _assert_map_is_list(vals, rec, name)
-    vals, pad = _map(g, 1, W, H, pad_px=5, pad_rows=2)      # a pitch and a view stride larger than a row / a view
-    _assert_map_is_list(vals, rec, name + " padded")
+    GR.assert_map_is_list(vals, rec, name)
+    vals, pad = ground_map(g, 1, W, H, pad_px=5, pad_rows=2)      # a pitch and a view stride larger than a row / a view
+    GR.assert_map_is_list(vals, rec, name + " padded")
     assert len(pad) and (pad == 0xAB).all(), "the map wrote between rows or behind the view"
     assert np.isnan(vals[rec["kind"] != 1]).all()
     if name == "past_edge":
         assert (rec["kind"] == 0).any()
-
-
-def _strip(r, views, sw, sh):
-    import torch
-    n = len(views)
-    rgba = torch.zeros((n, sh, sw, 4), dtype=torch.uint8, device="cuda")
-    depth = torch.zeros((n, sh, sw), dtype=torch.float32, device="cuda")
-    r.render_views_device(views, sw, sh, rgba.data_ptr(), sh * sw * 4, sw * 4, depth.data_ptr(), sh * sw * 4, sw * 4)
-    return rgba, depth
 
 
 def test_submissions_of_several_views(topo, orc):
@@ -150,18 +90,18 @@ def test_submissions_of_several_views(topo, orc):
     import torch
     sc = Scene(96, 2, 2, eye_dh=120.0)
     sw, sh = 64, 48
-    g, o = _pair(topo, orc, sc, sw, sh)
+    g, o = pair(topo, orc, sc, sw, sh)
     pu = topo.post_uniforms(sw, sh)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     us = sc.panorama(sw, sh, yaw0_deg=25.0)
-    keep = _strip(g, us, sw, sh)
-    got = g.ground(_all_pixels(topo, range(8), sw, sh)).reshape(8, sh, sw)
+    keep = strip(g, us, sw, sh)
+    got = g.ground(GR.all_pixels(topo, range(8), sw, sh)).reshape(8, sh, sw)
     wants = _expect(o, sc, sw, sh, us, pu)
     for v in range(8):
         GR.compare(got[v], wants[v], f"sector {v}")
     assert np.array_equal(got["depth"], keep[1].cpu().numpy())
-    vals, pad = _map(g, 4, sw, sh, first=3, pad_px=3, pad_rows=1)
-    _assert_map_is_list(vals, got[3:7], "sectors 3..6")
+    vals, pad = ground_map(g, 4, sw, sh, first=3, pad_px=3, pad_rows=1)
+    GR.assert_map_is_list(vals, got[3:7], "sectors 3..6")
     assert (pad == 0xAB).all()
     assert np.array_equal(g.ground([(5, 7, 9)]), got[5, 9, 7].reshape(1))      # (view, x, y)
     # the batch: viewpoints 0..7 are the first submission, viewpoint 8 the second and latest
@@ -175,7 +115,7 @@ def test_submissions_of_several_views(topo, orc):
     out = torch.zeros((9, 8, sh, sw, 4), dtype=torch.uint8, device="cuda")
     g.render_batch(eyes, yaws, suns, sw, sh, out.data_ptr(), None)
     assert g.horizon_shape() == (8, sw, sh)
-    got = g.ground(_all_pixels(topo, range(8), sw, sh)).reshape(8, sh, sw)
+    got = g.ground(GR.all_pixels(topo, range(8), sw, sh)).reshape(8, sh, sw)
     last = list(topo.panorama_uniforms(eyes[8], yaws[8], sw, sh, suns[8][0], suns[8][1], 0))
     wants = _expect(o, sc, sw, sh, last, pu)
     for v in range(8):
@@ -192,17 +132,17 @@ def test_pipeline_depth_2_device_list_before_join(topo, orc):
     import torch
     sc = Scene(96, 2, 2, eye_dh=120.0)
     W, H = 150, 90
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     pu = topo.post_uniforms(W, H)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     g.set_pipeline_depth(2)
     first = [sc.uniforms(W, H, yaw, 4, 70, 0) for yaw in (0, 60)]
     us = [sc.uniforms(W, H, yaw, 6, 70, 0) for yaw in (130, 200, 290)]
-    q = _all_pixels(topo, range(3), W, H)
+    q = GR.all_pixels(topo, range(3), W, H)
     q_dev = torch.from_numpy(q.view(np.uint32).reshape(-1, 4).copy()).cuda()
     out = torch.full((len(q) * 64,), 0xAB, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
-    keep = [_strip(g, first, W, H), _strip(g, us, W, H)]      # two submissions in flight
+    keep = [strip(g, first, W, H), strip(g, us, W, H)]      # two submissions in flight
     g.ground_device(q_dev.data_ptr(), out.data_ptr(), len(q))
     g.join()
     got = out.cpu().numpy().view(topo.GROUND_DTYPE).reshape(3, H, W)
@@ -256,7 +196,7 @@ def test_errors(topo):
     for what, call in calls.items():
         invalid(call, what + " after add_terrain")
     g.render()
-    assert (g.ground(_all_pixels(topo, [0], W, H))["kind"] == 1).any()
+    assert (g.ground(GR.all_pixels(topo, [0], W, H))["kind"] == 1).any()
     g.unload_terrain(*order[0])
     for what, call in calls.items():
         invalid(call, what + " after unload_terrain")
@@ -268,10 +208,10 @@ def test_overflowed_rare_queue(topo, orc):
     import torch
     sc = Scene(12, 2, 2, eye_dh=60.0)
     W, H = 640, 480
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     u, pu = sc.uniforms(W, H, 10, 35, 110, 0), topo.post_uniforms(W, H)
     g.update(W, H, u, pu)
-    q = np.ascontiguousarray(_all_pixels(topo, [0], W, H)[::97])
+    q = np.ascontiguousarray(GR.all_pixels(topo, [0], W, H)[::97])
     q_dev = torch.from_numpy(q.view(np.uint32).reshape(-1, 4).copy()).cuda()
     out = torch.zeros((len(q) * 64,), dtype=torch.uint8, device="cuda")
     dense = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
@@ -290,7 +230,7 @@ def test_overflowed_rare_queue(topo, orc):
     blank = rec.copy()
     blank["kind"] = 0
     assert not blank.view(np.uint8).any()
-    assert (dense.cpu().numpy().view(np.uint32) == NAN_BITS).all()
+    assert (dense.cpu().numpy().view(np.uint32) == GR.NAN_BITS).all()
     with pytest.raises(topo.TopoError) as e:
         g.ground(q)      # still the latest submission: still incomplete
     assert e.value.code == topo.TOPO_ERR_CAPACITY
@@ -298,7 +238,7 @@ def test_overflowed_rare_queue(topo, orc):
     # topo_render grows the queue and renders again: the latest submission is the complete frame
     g.render()
     assert g.counters()["rare_items"] > 2
-    full = _all_pixels(topo, [0], W, H)
+    full = GR.all_pixels(topo, [0], W, H)
     GR.compare(g.ground(full).reshape(H, W), _expect(o, sc, W, H, [u], pu)[0], "grow-and-retry")
     g.join()
 
@@ -311,7 +251,7 @@ def test_void_scene(topo):
     void.load(g)
     g.update(W, H, sc.uniforms(W, H, *pose), topo.post_uniforms(W, H))
     frame = g.render()
-    got = g.ground(_all_pixels(topo, [0], W, H)).reshape(H, W)
+    got = g.ground(GR.all_pixels(topo, [0], W, H)).reshape(H, W)
     assert np.isin(got["kind"], (1, 0, -3)).all()
     t = got["kind"] == 1
     assert t.mean() > 0.25
@@ -319,8 +259,8 @@ def test_void_scene(topo):
         assert np.isfinite(got[f]).all(), f
     assert np.array_equal(got["depth"].view(np.uint32), np.asarray(frame[1], np.float32).view(np.uint32))
     assert np.array_equal(got["kind"] == 0, np.asarray(frame[1]) == 1.0)
-    vals, _ = _map(g, 1, W, H)
-    _assert_map_is_list(vals, got.reshape(1, H, W), "void scene")
+    vals, _ = ground_map(g, 1, W, H)
+    GR.assert_map_is_list(vals, got.reshape(1, H, W), "void scene")
     # the points lie on the mosaic, at the relief's heights (a void vertex would put them thousands of kilometres off)
     assert (got["lon_deg"][t] > 14.99).all() and (got["lon_deg"][t] < 17.01).all() and (got["lat_deg"][t] > 44.99).all() and (got["lat_deg"][t] < 47.01).all()
     assert (got["height_m"][t] > -100.0).all() and (got["height_m"][t] < 3100.0).all()
@@ -335,7 +275,7 @@ def test_queries_change_no_frame(topo):
     sc.load(a)
     sc.load(b)
     pu = topo.post_uniforms(W, H)
-    q = np.ascontiguousarray(_all_pixels(topo, [0], W, H)[::7])
+    q = np.ascontiguousarray(GR.all_pixels(topo, [0], W, H)[::7])
     q_dev = torch.from_numpy(q.view(np.uint32).reshape(-1, 4).copy()).cuda()
     out = torch.zeros((len(q) * 64,), dtype=torch.uint8, device="cuda")
     dense = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
@@ -362,7 +302,7 @@ def test_queries_change_no_frame(topo):
     keep = []
     for k in range(4):
         us = sc.panorama(sw, sh, yaw0_deg=9.0 * k)
-        keep.append((_strip(a, us, sw, sh), _strip(b, us, sw, sh)))
+        keep.append((strip(a, us, sw, sh), strip(b, us, sw, sh)))
         if k % 2:
             b.ground([(k, 3, 5), (7, sw - 1, sh - 1)])
         else:
@@ -385,12 +325,12 @@ def _checked_run(T):
     g = T.TerrainRenderer(W, H)
     sc.load(g)
     pu = T.post_uniforms(W, H)
-    q = _all_pixels(T, [0], W, H)
+    q = GR.all_pixels(T, [0], W, H)
     for yaw, pitch in ((10, 35), (200, 80), (100, -20)):
         g.update(W, H, sc.uniforms(W, H, yaw, pitch, 110, 0), pu)
         g.render()
         h.update(g.ground(q).tobytes())
-        h.update(_map(g, 1, W, H, pad_px=1)[0].tobytes())
+        h.update(ground_map(g, 1, W, H, pad_px=1)[0].tobytes())
         status |= g.frame_status()["status"]
     sc2 = Scene(96, 2, 2, eye_dh=120.0)
     sw, sh = 70, 48
@@ -398,12 +338,12 @@ def _checked_run(T):
     sc2.load(p)
     p.set_stream(torch.cuda.current_stream().cuda_stream)
     p.set_pipeline_depth(2)
-    keep = _strip(p, sc2.panorama(sw, sh, yaw0_deg=3.0), sw, sh)
-    h.update(p.ground(_all_pixels(T, range(1, 7), sw, sh)).tobytes())
-    h.update(_map(p, 5, sw, sh, first=3)[0].tobytes())
+    keep = strip(p, sc2.panorama(sw, sh, yaw0_deg=3.0), sw, sh)
+    h.update(p.ground(GR.all_pixels(T, range(1, 7), sw, sh)).tobytes())
+    h.update(ground_map(p, 5, sw, sh, first=3)[0].tobytes())
     p.unload_terrain(*geo_order(sc2.locs)[0])
-    keep = (keep, _strip(p, sc2.panorama(sw, sh, yaw0_deg=30.0), sw, sh))
-    h.update(p.ground(_all_pixels(T, range(8), sw, sh)).tobytes())
+    keep = (keep, strip(p, sc2.panorama(sw, sh, yaw0_deg=30.0), sw, sh))
+    h.update(p.ground(GR.all_pixels(T, range(8), sw, sh)).tobytes())
     p.synchronize()
     status |= p.frame_status()["status"]
     torch.cuda.synchronize()
@@ -411,14 +351,6 @@ def _checked_run(T):
 
 
 def test_bounds_checked_build_records_no_out_of_range_index(topo):
-    check = os.path.join(os.path.dirname(topo.LIB_PATH), "libtopo_hip_check.so")
-    assert os.path.exists(check), "run __graft_entry__.build()"
-    code = f"import sys, json; sys.path[:0] = [{os.path.dirname(HERE)!r}, {HERE!r}]; import topo_renderer_amd as T; " \
-           f"import test_ground_gpu as m; print(json.dumps(dict(m._checked_run(T), lib=T.LIB_PATH)))"
-    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TOPO_HIP_LIB=check), capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    got = json.loads(res.stdout.strip().split("\n")[-1])
-    assert got["lib"].endswith("libtopo_hip_check.so")
-    assert not (got["status"] & 4), got          # kStatusBounds: an index k_ground / k_ground_map (or any kernel) formed was out of range
+    got = checked_run("test_ground_gpu")      # kStatusBounds: an index k_ground / k_ground_map (or any kernel) formed was out of range
     want = _checked_run(topo)
     assert got["sha"] == want["sha"] and got["status"] == want["status"]

@@ -2,29 +2,18 @@
 oracle's per-pixel winners and depths give (render_winners(), tests/horizon_ref.py), and the depth also equals the frame's own
 depth output.  (The fan piece of a near-clipped triangle is not part of the oracle's winners: it is checked to be 0 or 1.)"""
 import hashlib
-import json
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from horizon_ref import FIELDS, horizon, mismatches
+from gpu_support import checked_run, padded_device_output, pair, strip
+from horizon_ref import FRAMES, assert_view, horizon
 from scenes import Scene, assert_same_frame
 from viewshed_ref import geo_order
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _pair(topo, orc, sc, W, H):
-    g, o = topo.TerrainRenderer(W, H), orc.OracleRenderer(W, H)
-    sc.load(g)
-    sc.load(o)
-    return g, o
 
 
 def _expect(o, W, H, views, pu, locs, tile):
@@ -36,44 +25,17 @@ def _expect(o, W, H, views, pu, locs, tile):
     return out
 
 
-def _assert_view(got, want, what, frame_depth=None):
-    """got: (W,) records of one view; want: horizon_ref dict; frame_depth: (H, W) depth output of the same view."""
-    for f in FIELDS:
-        bad = mismatches(got, want, f)
-        assert len(bad) == 0, f"{what}: {f} differs in {len(bad)} columns (first {bad[0]}: got {got[f][bad[0]]}, want {want[f][bad[0]]})"
-    assert np.isin(got["fan"], (0, 1)).all() and (got["_reserved"] == 0).all(), what
-    if frame_depth is not None:
-        fd = np.asarray(frame_depth, np.float32)
-        rows = got["row"]
-        at = np.where(rows >= 0, fd[np.clip(rows, 0, None), np.arange(len(rows))], np.float32(1.0))
-        assert np.array_equal(at.view(np.uint32), got["depth"].view(np.uint32)), f"{what}: depth differs from the frame's depth output"
-        top = np.where(rows >= 0, rows, fd.shape[0])
-        sky_above = np.arange(fd.shape[0])[:, None] < top[None, :]
-        assert (fd[sky_above] == 1.0).all(), f"{what}: terrain depth above the reported row"
-
-
 def _assert_all(got, wants, what, frame_depths=None):
     assert got.shape[0] == len(wants), (got.shape, len(wants))
     for v, want in enumerate(wants):
-        _assert_view(got[v], want, f"{what} view {v}", None if frame_depths is None else frame_depths[v])
-
-
-FRAMES = [
-    # tile, n_lat, n_lon, eye_dh, W, H, [(yaw, pitch, fov)]  -- test_viewshed_gpu.py's frames, then an odd width and the mosaic's edge
-    (96, 2, 2, 50.0, 256, 128, [(40, 10, 70), (250, 0, 60)]),
-    (96, 2, 2, 100.0, 200, 150, [(120, 60, 90)]),                  # near clip / big triangles
-    (64, 1, 1, 400.0, 160, 160, [(10, 85, 100), (300, 70, 80)]),   # pitch 85: terrain up to row 0
-    (12, 2, 2, 60.0, 640, 480, [(10, 35, 110), (200, 80, 110), (100, 5, 110)]),   # the coarse mesh: every triangle large
-    (96, 2, 2, 80.0, 333, 97, [(70, 3, 75)]),                      # a width that is no multiple of 64
-    (64, 1, 1, 50.0, 190, 100, [(0, -27, 60), (90, -27, 60), (180, -27, 60), (270, -27, 60)]),   # out past the mosaic: sky columns
-]
+        assert_view(got[v], want, f"{what} view {v}", None if frame_depths is None else frame_depths[v])
 
 
 @pytest.mark.parametrize("cfg", FRAMES, ids=["2x2_dh50", "2x2_dh100_p60", "1x1_dh400_p85", "coarse12", "odd_width", "past_edge"])
 def test_single_frames_match_oracle(topo, orc, cfg):
     tile, nla, nlo, dh, W, H, views = cfg
     sc = Scene(tile, nla, nlo, eye_dh=dh, vfrac=(0.5, 0.97) if W == 190 else (0.5123, 0.5217))
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     pu = topo.post_uniforms(W, H)
     rows = []
     for yaw, pitch, fov in views:
@@ -85,7 +47,7 @@ def test_single_frames_match_oracle(topo, orc, cfg):
         assert g.horizon_shape() == (1, W, H)
         got = g.horizon()
         assert got.shape == (1, W)
-        _assert_view(got[0], _expect(o, W, H, [u], pu, sc.locs, tile)[0], f"{cfg[:6]} yaw {yaw} pitch {pitch}", frame[1])
+        assert_view(got[0], _expect(o, W, H, [u], pu, sc.locs, tile)[0], f"{cfg[:6]} yaw {yaw} pitch {pitch}", frame[1])
         rows.append(got[0]["row"])
     rows = np.concatenate(rows)
     assert (rows >= 0).any()
@@ -95,30 +57,18 @@ def test_single_frames_match_oracle(topo, orc, cfg):
         assert (rows == -1).any()     # all-sky columns
 
 
-def _strip(r, views, sw, sh):
-    import torch
-    n = len(views)
-    rgba = torch.zeros((n, sh, sw, 4), dtype=torch.uint8, device="cuda")
-    depth = torch.zeros((n, sh, sw), dtype=torch.float32, device="cuda")
-    r.render_views_device(views, sw, sh, rgba.data_ptr(), sh * sw * 4, sw * 4, depth.data_ptr(), sh * sw * 4, sw * 4)
-    return rgba, depth
-
-
 def _device_horizon(g, n, W, first=0, stride=None):
-    import torch
-    stride = W if stride is None else stride
-    buf = torch.full((n * stride * 32,), 0xAB, dtype=torch.uint8, device="cuda")
-    g.horizon_device(buf.data_ptr(), first, n, stride)
-    g.synchronize()
     import topo_renderer_amd as T
-    return buf.cpu().numpy().view(T.HORIZON_DTYPE).reshape(n, stride)
+    stride = W if stride is None else stride
+    rec, _ = padded_device_output(g, n, 1, stride, 32, lambda p, *_: g.horizon_device(p, first, n, stride))
+    return rec.view(T.HORIZON_DTYPE).reshape(n, stride)
 
 
 def test_panorama_world_of_one_and_slot_path(topo, orc):
     import torch
     sc = Scene(96, 2, 2, eye_dh=120.0)
     sw, sh = 96, 160
-    g, o = _pair(topo, orc, sc, sw, sh)
+    g, o = pair(topo, orc, sc, sw, sh)
     pu = topo.post_uniforms(sw, sh)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     strip = torch.zeros((8, sh, sw, 4), dtype=torch.uint8, device="cuda")
@@ -151,7 +101,7 @@ def test_batch_and_views_device(topo, orc):
     import torch
     sc = Scene(96, 2, 2, eye_dh=120.0)
     sw, sh = 96, 130
-    g, o = _pair(topo, orc, sc, sw, sh)
+    g, o = pair(topo, orc, sc, sw, sh)
     pu = topo.post_uniforms(sw, sh)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     rng = np.random.default_rng(4)
@@ -176,7 +126,7 @@ def test_batch_and_views_device(topo, orc):
     # five views of an odd width, one submission
     W, H = 150, 90
     us = [sc.uniforms(W, H, yaw, 4, 70, 0) for yaw in (0, 60, 130, 200, 290)]
-    rgba, depth = _strip(g, us, W, H)
+    rgba, depth = strip(g, us, W, H)
     sub = _device_horizon(g, 2, W, first=2, stride=W + 13)
     got = g.horizon()
     g.join()
@@ -194,7 +144,7 @@ def test_queue_overflow(topo, orc):
     import torch
     sc = Scene(12, 2, 2, eye_dh=60.0)
     W, H = 640, 480
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     u, pu = sc.uniforms(W, H, 10, 35, 110, 0), topo.post_uniforms(W, H)
     g.update(W, H, u, pu)
     want = _expect(o, W, H, [u], pu, sc.locs, 12)
@@ -216,14 +166,14 @@ def test_queue_overflow(topo, orc):
     # topo_render grows the queue and renders again: the latest submission is the complete frame
     frame = g.render()
     assert g.counters()["rare_items"] > 2
-    _assert_view(g.horizon()[0], want[0], "grow-and-retry", frame[1])
+    assert_view(g.horizon()[0], want[0], "grow-and-retry", frame[1])
     g.join()
 
 
 def test_tile_lifecycle(topo, orc):
     sc = Scene(64, 2, 2, eye_dh=150.0)
     W, H = 256, 128
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     pu = topo.post_uniforms(W, H)
     with pytest.raises(topo.TopoError) as e:
         g.horizon()      # nothing rendered yet
@@ -231,7 +181,7 @@ def test_tile_lifecycle(topo, orc):
     u = sc.uniforms(W, H, 30, 12, 80, 0)
     g.update(W, H, u, pu)
     frame = g.render()
-    _assert_view(g.horizon()[0], _expect(o, W, H, [u], pu, sc.locs, 64)[0], "before", frame[1])
+    assert_view(g.horizon()[0], _expect(o, W, H, [u], pu, sc.locs, 64)[0], "before", frame[1])
     order = geo_order(sc.locs)
     replaced, gone = order[1], order[0]
     hts = sc.heights[replaced] * np.float32(0.7) + np.float32(30.0)
@@ -242,7 +192,7 @@ def test_tile_lifecycle(topo, orc):
             call()
         assert e.value.code == topo.TOPO_ERR_INVALID
     frame = g.render()
-    _assert_view(g.horizon()[0], _expect(o, W, H, [u], pu, sc.locs, 64)[0], "after replacing a tile", frame[1])
+    assert_view(g.horizon()[0], _expect(o, W, H, [u], pu, sc.locs, 64)[0], "after replacing a tile", frame[1])
     g.unload_terrain(*gone)
     o.unload_terrain(*gone)
     with pytest.raises(topo.TopoError) as e:
@@ -253,7 +203,7 @@ def test_tile_lifecycle(topo, orc):
         u = sc.uniforms(W, H, yaw, 12, 80, 0)
         g.update(W, H, u, pu)
         frame = g.render()
-        _assert_view(g.horizon()[0], _expect(o, W, H, [u], pu, left, 64)[0], f"after unloading a tile (ranks shifted), yaw {yaw}", frame[1])
+        assert_view(g.horizon()[0], _expect(o, W, H, [u], pu, left, 64)[0], f"after unloading a tile (ranks shifted), yaw {yaw}", frame[1])
 
 
 def test_queries_change_no_frame(topo):
@@ -281,7 +231,7 @@ def test_queries_change_no_frame(topo):
     keep = []
     for k in range(4):
         us = sc.panorama(64, 96, yaw0_deg=9.0 * k)
-        keep.append((_strip(a, us, 64, 96), _strip(b, us, 64, 96)))
+        keep.append((strip(a, us, 64, 96), strip(b, us, 64, 96)))
         if k % 2:
             b.horizon()
         else:
@@ -298,7 +248,7 @@ def test_full_size_tiles(topo, orc):
     import torch
     sc = Scene(1200, 2, 2, eye_dh=300.0)
     sw, sh = 1024, 512
-    g, o = _pair(topo, orc, sc, sw, sh)
+    g, o = pair(topo, orc, sc, sw, sh)
     pu = topo.post_uniforms(sw, sh)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     strip = torch.zeros((8, sh, sw, 4), dtype=torch.uint8, device="cuda")
@@ -383,11 +333,11 @@ def _checked_run(T):
     sc2.load(p)
     p.set_stream(torch.cuda.current_stream().cuda_stream)
     p.set_pipeline_depth(2)
-    keep = _strip(p, sc2.panorama(sw, sh, yaw0_deg=3.0), sw, sh)
+    keep = strip(p, sc2.panorama(sw, sh, yaw0_deg=3.0), sw, sh)
     h.update(p.horizon(1, 6).tobytes())
     h.update(_device_horizon(p, 8, sw).tobytes())
     p.unload_terrain(*geo_order(sc2.locs)[0])
-    keep = (keep, _strip(p, sc2.panorama(sw, sh, yaw0_deg=30.0), sw, sh))
+    keep = (keep, strip(p, sc2.panorama(sw, sh, yaw0_deg=30.0), sw, sh))
     h.update(p.horizon().tobytes())
     p.synchronize()
     status |= p.frame_status()["status"]
@@ -396,14 +346,6 @@ def _checked_run(T):
 
 
 def test_bounds_checked_build_records_no_out_of_range_index(topo):
-    check = os.path.join(os.path.dirname(topo.LIB_PATH), "libtopo_hip_check.so")
-    assert os.path.exists(check), "run __graft_entry__.build()"
-    code = f"import sys, json; sys.path[:0] = [{os.path.dirname(HERE)!r}, {HERE!r}]; import topo_renderer_amd as T; " \
-           f"import test_horizon_gpu as m; print(json.dumps(dict(m._checked_run(T), lib=T.LIB_PATH)))"
-    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TOPO_HIP_LIB=check), capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    got = json.loads(res.stdout.strip().split("\n")[-1])
-    assert got["lib"].endswith("libtopo_hip_check.so")
-    assert not (got["status"] & 4), got          # kStatusBounds: an index k_horizon (or any kernel) formed was out of range
+    got = checked_run("test_horizon_gpu")      # kStatusBounds: an index k_horizon (or any kernel) formed was out of range
     want = _checked_run(topo)
     assert got["sha"] == want["sha"] and got["status"] == want["status"]

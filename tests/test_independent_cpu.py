@@ -11,8 +11,7 @@ import pytest
 
 from oracle import ray_check as RC
 from oracle import shade_check as SC
-from scenes import Scene
-from test_ray_check_cpu import relief
+from scenes import Scene, relief
 
 
 def _btree_order(locs):

@@ -4,20 +4,15 @@ Targets of 65536 px a side, one view past 2^31 px, a submission just under 2^32 
 whose 65792 regions take k_raster_rare's dividing split, FarItem boxes near x = 65535, view offsets and pixel indices past 2^31.
 Frames too large for the whole oracle are compared through oracle windows (OracleRenderer.render_window).  Every case first
 runs in the bounds-checked build in a child process; the product cases run only if that is clean."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import limits_scenes as LS
+from gpu_support import checked_script
 from scenes import Scene, assert_same_frame
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 _PEAK = {"device_used": 0}
 
 
@@ -29,20 +24,14 @@ def _note_memory():
 
 @pytest.fixture(scope="module")
 def checked(topo):
-    """Every case through libtopo_hip_check.so in a child process: no out-of-range index, no queue overflow.  Fails (never
+    """Every case through the bounds-checked build in a child process: no out-of-range index, no queue overflow.  Fails (never
     skips) the product cases below when it is not clean."""
     import torch
     free, total = torch.cuda.mem_get_info()
     if free < 90 * 2 ** 30:
         pytest.fail(f"the limit cases need about 80 GB of device memory; {free / 2 ** 30:.1f} GB free")
-    lib = os.path.join(os.path.dirname(topo.LIB_PATH), "libtopo_hip_check.so")
-    assert os.path.exists(lib), "run __graft_entry__.build()"
-    r = subprocess.run([sys.executable, os.path.join(HERE, "limits_scenes.py")], env=dict(os.environ, TOPO_HIP_LIB=lib),
-                       capture_output=True, text=True, timeout=600)
-    if r.returncode != 0:
-        pytest.fail(f"bounds-checked limit run failed ({r.returncode}): {r.stderr[-3000:]}")
-    got = json.loads(r.stdout.strip().split("\n")[-1])
-    assert got["lib"].endswith("libtopo_hip_check.so") and set(got["cases"]) == set(LS.CASES)
+    got = checked_script("limits_scenes.py", 600)      # (a child that does not exit cleanly fails the fixture)
+    assert set(got["cases"]) == set(LS.CASES)
     bad = {k: c for k, c in got["cases"].items() if c["bounds_violation"] or c["status"]}
     if bad:
         pytest.fail(f"bounds-checked limit run not clean: {bad}")

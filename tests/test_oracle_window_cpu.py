@@ -7,8 +7,7 @@ import math
 import numpy as np
 import pytest
 
-from scenes import Scene, assert_same_frame
-from test_gpu_parity import FRAMES
+from scenes import FRAMES, Scene, assert_same_frame
 
 
 def _windows(rng, W, H, n):

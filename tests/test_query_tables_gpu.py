@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 import los_cases as LC
-from scenes import Scene
-from test_ray_check_cpu import relief
+from gpu_support import padded_device_output, strip
+from scenes import Scene, relief
 
 pytestmark = pytest.mark.gpu
 
@@ -38,12 +38,7 @@ def _renderer(topo):
 
 def _device(g, fill_bytes, call):
     """A device variant's output: a dense tensor of fill_bytes handed to call(pointer), read back after the renderer's streams."""
-    import torch
-    buf = torch.full((fill_bytes,), 0xAB, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    call(buf.data_ptr())
-    g.synchronize()
-    return buf.cpu().numpy().tobytes()
+    return padded_device_output(g, 1, 1, fill_bytes, 1, lambda p, *_: call(p))[0].tobytes()
 
 
 def _ask(g, kind):
@@ -114,15 +109,6 @@ def test_any_kind_may_build_the_tables(topo, first):
     assert between == base[1], "raycast between the tile set's change and the next render"
 
 
-def _strip(r, views):
-    import torch
-    n = len(views)
-    rgba = torch.zeros((n, H, W, 4), dtype=torch.uint8, device="cuda")
-    depth = torch.zeros((n, H, W), dtype=torch.float32, device="cuda")
-    r.render_views_device(views, W, H, rgba.data_ptr(), H * W * 4, W * 4, depth.data_ptr(), H * W * 4, W * 4)
-    return rgba, depth
-
-
 @pytest.mark.parametrize("variant", ["horizon_device", "ground_map_device"])
 def test_device_variant_in_flight_at_depth_2(topo, variant):
     """The variant queued behind a two-view frame on a context's own stream, then two frames of other views (the second reuses that
@@ -137,7 +123,7 @@ def test_device_variant_in_flight_at_depth_2(topo, variant):
     views = [sc.uniforms(W, H, yaw, 25.0, 60.0, 1) for yaw in (30.0, 75.0)]
     others = [sc.uniforms(W, H, yaw, 10.0, 60.0, 1) for yaw in (200.0, 290.0)]
     size = 2 * W * 32 if variant == "horizon_device" else 2 * W * H * 16
-    keep = [_strip(g, views)]
+    keep = [strip(g, views, W, H)]
     want = torch.full((size,), 0xAB, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     getattr(g, variant)(want.data_ptr())
@@ -147,9 +133,9 @@ def test_device_variant_in_flight_at_depth_2(topo, variant):
     g.set_pipeline_depth(2)
     got = torch.full((size,), 0xAB, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
-    keep.append(_strip(g, views))
+    keep.append(strip(g, views, W, H))
     getattr(g, variant)(got.data_ptr())
-    keep += [_strip(g, others), _strip(g, others[::-1])]
+    keep += [strip(g, others, W, H), strip(g, others[::-1], W, H)]
     g.join()
     torch.cuda.synchronize()
     assert np.array_equal(got.cpu().numpy(), want)

@@ -8,22 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import ray_check as RC
-from scenes import Scene
-
-def relief(lat, lon):
-    """Strong, asymmetric relief at the scale of a coarse test tile (the fBm of the benchmark tiles is almost flat over
-    a 24-texel degree): kilometre-high ridges a tenth of a degree apart, no symmetry between the axes."""
-    return 1500.0 + 900.0 * np.sin(np.radians(37.0 * lon + 11.0 * lat)) * np.cos(np.radians(53.0 * lat)) \
-        + 500.0 * np.sin(np.radians(140.0 * lon)) + 0.0 * lat
-
-
-SCENES = [
-    # tile, n_lat, n_lon, lat0, lon0, W, H, yaw, pitch, fov, eye_dh
-    # (coarse tiles: vertices kilometres apart, so the eye sits kilometres up to be above the mesh it looks at)
-    (24, 2, 2, 45, 15, 96, 64, 30.0, 25.0, 60.0, 4000.0),      # north-east quadrant, four tiles, the gaps between them in view
-    (32, 1, 1, 45, 15, 80, 80, 250.0, 60.0, 90.0, 6000.0),     # steeply down: triangles tens of px across
-    (16, 3, 3, -34, -71, 96, 48, 200.0, 30.0, 79.28, 8000.0),  # southern + western hemisphere, panorama sector FOV
-]
+from scenes import RELIEF_SCENES as SCENES, Scene, relief
 
 
 @pytest.mark.parametrize("cfg", SCENES, ids=["ne_2x2", "down_1x1", "sw_3x3"])

@@ -1,11 +1,6 @@
 """Ray queries on the GPU (topo_raycast_*, topo_sunlit_map_device): k_raycast and k_sunlit_map against the numpy reference (tests/los_ref.py) and the g++ build of the same
 traversal (tests/los_emul.py) on the cases of tests/los_cases.py, the calls' contract, and their side effects (none)."""
 import hashlib
-import json
-import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,53 +8,26 @@ import pytest
 import los_cases as LC
 import los_emul as LE
 import los_ref as LR
+from gpu_support import checked_run, renderer, strip, sunlit_map
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _renderer(T, tiles, order, W=64, H=48):
-    g = T.TerrainRenderer(W, H)
-    for (lat, lon), t in zip(order, tiles):
-        g.add_terrain(lat, lon, *t)
-    return g
-
-
-def _against_emulation(got, emu, rays, what, keep):
-    """Every ray: kind, tile, cell, triangle and face identical.  The rays the reference does not mark ambiguous (keep): t * |dir|
-    within 1e-4 m (device and host sin / cos differ by an ulp or two: about 1.5e-9 m of vertex position, which 1 / |n . d| <= 1e3
-    turns into 1.5e-6 m at most) -- a grazing ray has no such bound."""
-    for f in ("kind", "tile_lat_deg", "tile_lon_deg", "cell_x", "cell_y", "tri", "front"):
-        bad = np.nonzero(got[f] != emu[f])[0]
-        assert len(bad) == 0, f"{what}: {f} differs from the emulation for {len(bad)} rays, first {bad[0]}: {got[bad[0]]} vs {emu[bad[0]]}"
-    err = (np.abs(got["t"] - emu["t"]) * np.linalg.norm(rays["dir"], axis=1))[keep]
-    print(f"{what}: largest |t| difference to the emulation {err.max():.3e} m")
-    assert err.max() <= 1e-4, f"{what}: {err.max():.3e} m"
-    hit = got["kind"] == LR.HIT
-    if hit.any():
-        assert np.abs(got["lon_deg"][hit] - emu["lon_deg"][hit]).max() < 1e-9 and np.abs(got["lat_deg"][hit] - emu["lat_deg"][hit]).max() < 1e-9
-        assert np.abs(got["height_m"][hit] - emu["height_m"][hit].astype(np.float32)).max() <= 1e-3
-        assert np.abs(got["w1"][hit] - emu["w1"][hit]).max() < 1e-5 and np.abs(got["w2"][hit] - emu["w2"][hit]).max() < 1e-5
-    z = got[~hit]
-    assert not z["t"].any() and not z["lon_deg"].any() and not z["cell_x"].any() and not z["w1"].any(), "every other field of a non-hit is 0"
-    return float(err.max())
 
 
 @pytest.mark.parametrize("name", sorted(LC.CASES))
 def test_cases(topo, name):
     tiles, order, rays, ref = LC.case(name)
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     got = g.raycast(rays)
     LR.compare(ref, got, rays, order, tiles[0][0].shape[0], 1e-3, name)
     emu, _ = LE.raycast(tiles, order, rays)
-    _against_emulation(got, emu, rays, name, ~ref["ambiguous"])
+    LC.against_emulation(got, emu, rays, name, ~ref["ambiguous"])
     g.close()
 
 
 def test_invalid_rays_and_the_calls_contract(topo):
     import torch
     tiles, order, rays, ref = LC.case("blocks")
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     planted, idx = LC.with_invalid(rays)
     clean, got = g.raycast(rays), g.raycast(planted)
     assert (got["kind"][idx] == topo.RAY_INVALID).all()
@@ -117,8 +85,7 @@ def test_consistent_with_the_ground_queries(topo):
     """tests/test_ray_check_cpu.py's ne_2x2 scene: the ray from camera_pos towards a pixel's ground point hits the triangle the ground
     record names for at least 0.999 of the pixels at least 0.03 barycentric inside their triangle (the statistic and threshold the
     oracle is held to there), at the record's range to 1e-2 m (both rounded to f32)."""
-    from scenes import Scene
-    from test_ray_check_cpu import relief
+    from scenes import Scene, relief
     sc = Scene(24, 2, 2, lat0=45, lon0=15, eye_dh=4000.0, height_fn=relief)
     W, H = 96, 64
     g = topo.TerrainRenderer(W, H)
@@ -194,29 +161,6 @@ def test_ray_calls_change_no_frame_and_no_mask(topo):
 
 # ---- the sunlit layer (topo_sunlit_map_device) -----------------------------------------------------------------------------------
 
-def _sunlit(g, sun, n, W, H, first=0, pad_px=0, pad_rows=0):
-    """sunlit_map_device of views [first, first + n) into a tensor whose rows are pad_px bytes and whose views pad_rows rows longer
-    than needed: ((n, H, W) classes, the padding bytes)."""
-    import torch
-    pitch = W + pad_px
-    stride = pitch * (H + pad_rows)
-    buf = torch.full((n * stride,), 0xAB, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    g.sunlit_map_device(sun, buf.data_ptr(), first, n, stride, pitch)
-    g.synchronize()
-    raw = buf.cpu().numpy().reshape(n, H + pad_rows, W + pad_px)
-    return np.ascontiguousarray(raw[:, :H, :W]), np.concatenate([raw[:, :H, W:].ravel(), raw[:, H:].ravel()])
-
-
-def _strip(r, views, sw, sh):
-    import torch
-    n = len(views)
-    rgba = torch.zeros((n, sh, sw, 4), dtype=torch.uint8, device="cuda")
-    depth = torch.zeros((n, sh, sw), dtype=torch.float32, device="cuda")
-    r.render_views_device(views, sw, sh, rgba.data_ptr(), sh * sw * 4, sw * 4, depth.data_ptr(), sh * sw * 4, sw * 4)
-    return rgba, depth
-
-
 @pytest.mark.parametrize("name", sorted(LC.RIDGES))
 def test_sunlit_map(topo, orc, name):
     sc, W, H, u, tiles, order, sun, ref, amb, emu = LC.sunlit_case(name, orc)
@@ -224,7 +168,7 @@ def test_sunlit_map(topo, orc, name):
     sc.load(g)
     g.update(W, H, u, topo.post_uniforms(W, H))
     g.render()
-    got, pad = _sunlit(g, sun, 1, W, H, pad_px=5, pad_rows=2)
+    got, pad = sunlit_map(g, sun, 1, W, H, pad_px=5, pad_rows=2)
     assert (pad == 0xAB).all(), "bytes between the width and the pitch, and between the views, are left alone"
     got = got[0]
     terrain = ref != LR.NONE
@@ -237,7 +181,7 @@ def test_sunlit_map(topo, orc, name):
     assert len(bad) == 0, f"{len(bad)} pixels differ from the reference, first {tuple(bad[0])}: {got[tuple(bad[0])]} vs {ref[tuple(bad[0])]}"
     bad = np.argwhere((got != emu) & ~amb)
     assert len(bad) == 0, f"{len(bad)} pixels differ from the emulation, first {tuple(bad[0])}"
-    dense, _ = _sunlit(g, 3.0 * sun, 1, W, H)
+    dense, _ = sunlit_map(g, 3.0 * sun, 1, W, H)
     assert np.array_equal(dense[0], got), "sun_dir is normalised"
     g.close()
 
@@ -254,9 +198,9 @@ def test_sunlit_sub_range_and_frames_in_flight(topo):
     sc.load(g)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     us = sc.panorama(sw, sh, yaw0_deg=25.0)
-    keep = _strip(g, us, sw, sh)
-    full, _ = _sunlit(g, sun, 8, sw, sh)
-    part, pad = _sunlit(g, sun, 4, sw, sh, first=3, pad_px=3, pad_rows=1)
+    keep = strip(g, us, sw, sh)
+    full, _ = sunlit_map(g, sun, 8, sw, sh)
+    part, pad = sunlit_map(g, sun, 4, sw, sh, first=3, pad_px=3, pad_rows=1)
     assert np.array_equal(part, full[3:7]) and (pad == 0xAB).all()
     assert all((full == c).sum() > 50 for c in (topo.SUN_NONE, topo.SUN_LIT, topo.SUN_AWAY, topo.SUN_SHADOW)), np.bincount(full.ravel(), minlength=4)
     # ... and it is the class of each pixel's own ground record (f32 weights: a pixel may differ where its point sits on an edge)
@@ -267,7 +211,7 @@ def test_sunlit_sub_range_and_frames_in_flight(topo):
     assert (composed != full).mean() <= 0.005, float((composed != full).mean())
     # two submissions in flight, the map queued behind the second before the join
     g.set_pipeline_depth(2)
-    keep2 = [_strip(g, us[:2], sw, sh), _strip(g, us[2:7], sw, sh)]
+    keep2 = [strip(g, us[:2], sw, sh), strip(g, us[2:7], sw, sh)]
     buf = torch.full((5 * sh * sw,), 0xAB, dtype=torch.uint8, device="cuda")
     g.sunlit_map_device(sun, buf.data_ptr())
     g.join()
@@ -332,12 +276,12 @@ def _checked_run(T):
     status = 0
     for name in ("blocks", "ridges_sw", "void_pinf"):
         tiles, order, rays, _ = LC.case(name)
-        g = _renderer(T, tiles, order)
+        g = renderer(T, tiles, order)
         h.update(g.raycast(LC.with_invalid(rays)[0]).tobytes())
         status |= g.frame_status()["status"]
         g.close()
     for tiles, order, rays in (LC.batch_scene("tall")[:3], LC.case("polar")[:3]):      # the second batch of 64 blocks; tiles whose row 0 is the pole
-        g = _renderer(T, tiles, order)
+        g = renderer(T, tiles, order)
         h.update(g.raycast(rays).tobytes())
         status |= g.frame_status()["status"]
         g.close()
@@ -349,7 +293,7 @@ def _checked_run(T):
     sc.load(g)
     g.update(W, H, sc.uniforms(W, H, 200.0, 35.0, 79.28, 0), T.post_uniforms(W, H))
     g.render()
-    h.update(_sunlit(g, LC.sun_of(sc), 1, W, H, pad_px=1)[0].tobytes())
+    h.update(sunlit_map(g, LC.sun_of(sc), 1, W, H, pad_px=1)[0].tobytes())
     status |= g.frame_status()["status"]
     g.close()
     torch.cuda.synchronize()
@@ -357,13 +301,5 @@ def _checked_run(T):
 
 
 def test_bounds_checked_build_records_no_out_of_range_index(topo):
-    check = os.path.join(os.path.dirname(topo.LIB_PATH), "libtopo_hip_check.so")
-    assert os.path.exists(check), "run __graft_entry__.build()"
-    code = f"import sys, json; sys.path[:0] = [{os.path.dirname(HERE)!r}, {HERE!r}]; import topo_renderer_amd as T; " \
-           f"import test_raycast_gpu as m; print(json.dumps(dict(m._checked_run(T), lib=T.LIB_PATH)))"
-    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TOPO_HIP_LIB=check), capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    got = json.loads(res.stdout.strip().split("\n")[-1])
-    assert got["lib"].endswith("libtopo_hip_check.so")
-    assert not (got["status"] & 4), got          # kStatusBounds: an index k_raycast formed was out of range
+    got = checked_run("test_raycast_gpu")      # kStatusBounds: an index k_raycast formed was out of range
     assert got["sha"] == _checked_run(topo)["sha"], "the bounds-checked build answers as the product build"

@@ -2,10 +2,6 @@
 (tests/surface_ref.py) and the g++ build of the same lookup (tests/surface_emul.py) on the cases of tests/surface_cases.py, the
 calls' contract, their agreement with the ray and ground queries, and their side effects (none)."""
 import hashlib
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,16 +10,9 @@ import los_cases as LC
 import surface_cases as SC
 import surface_emul as SE
 import surface_ref as SR
+from gpu_support import checked_run, padded_device_output, renderer, strip
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _renderer(T, tiles, order, W=64, H=48):
-    g = T.TerrainRenderer(W, H)
-    for (lat, lon), t in zip(order, tiles):
-        g.add_terrain(lat, lon, *t)
-    return g
 
 
 def _against_emulation(got, emu, what, tri_ambiguous, kind_ambiguous):
@@ -52,7 +41,7 @@ def _against_emulation(got, emu, what, tri_ambiguous, kind_ambiguous):
 @pytest.mark.parametrize("name", sorted(SC.CASES))
 def test_cases(topo, name):
     tiles, order, pts, label = SC.case(name)
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     got = g.surface(pts)
     g.close()
     ref = SC.reference(name)
@@ -72,7 +61,7 @@ def test_full_size_tile_against_the_emulation(topo):
     tiles, order, pts = SC.big_tile()
     emu, bad = SE.surface(tiles, order, pts)
     assert bad == 0
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     got = g.surface(pts)
     g.close()
     w0 = 1.0 - emu["w1"] - emu["w2"]
@@ -88,7 +77,7 @@ def test_invalid_points_and_the_device_variant(topo):
     import torch
     tiles, order, pts, label = SC.case("blocks")
     pts = pts[label == SC.RANDOM]
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     planted, idx = SC.with_invalid(pts)
     clean, got = g.surface(pts), g.surface(planted)
     assert (got["kind"][idx] == topo.SURFACE_INVALID).all()
@@ -161,7 +150,7 @@ def test_consistent_with_the_ray_calls(topo, name):
     ref = SC.reference(name)
     keep = ~ref["tri_ambiguous"] & ~ref["kind_ambiguous"] & (label == SC.RANDOM)
     pts = pts[keep]
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     got = g.surface(pts)
     up = SR.direction(pts[:, 0], pts[:, 1])
     hit = g.raycast(topo.rays((SR.R0 + 20000.0) * up, -up, 0.0, 1.0e6))
@@ -180,8 +169,7 @@ def test_consistent_with_the_ground_queries(topo):
     """tests/test_ray_check_cpu.py's ne_2x2 scene: for the TERRAIN records of a rendered frame whose three weights are >= 0, the
     surface under the record's longitude and latitude is the record's tile, cell and triangle, at the record's height to 1e-3 m
     (the record's height is an f32)."""
-    from scenes import Scene
-    from test_ray_check_cpu import relief
+    from scenes import Scene, relief
     sc = Scene(24, 2, 2, lat0=45, lon0=15, eye_dh=4000.0, height_fn=relief)
     W, H = 96, 64
     g = topo.TerrainRenderer(W, H)
@@ -206,13 +194,8 @@ def test_consistent_with_the_ground_queries(topo):
 
 def _grid(g, lon0, lat0, dlon, dlat, nx, ny, pad_px=0):
     """surface_grid_device into a tensor whose rows are pad_px floats longer than needed: ((ny, nx) f32, the padding bytes)."""
-    import torch
-    buf = torch.full((ny, (nx + pad_px) * 4), 0xAB, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    g.surface_grid_device(lon0, lat0, dlon, dlat, nx, ny, buf.data_ptr(), (nx + pad_px) * 4)
-    g.synchronize()
-    raw = buf.cpu().numpy()
-    return np.ascontiguousarray(raw[:, :nx * 4]).view(np.float32), raw[:, nx * 4:]
+    vals, pad = padded_device_output(g, 1, ny, nx, 4, lambda p, stride, pitch: g.surface_grid_device(lon0, lat0, dlon, dlat, nx, ny, p, pitch), pad_px)
+    return vals.view(np.float32).reshape(ny, nx), pad
 
 
 def _grid_expected(g, T, lon0, lat0, dlon, dlat, nx, ny):
@@ -226,7 +209,7 @@ def _grid_expected(g, T, lon0, lat0, dlon, dlat, nx, ny):
 def test_grid(topo):
     import torch
     tiles, order, _, _ = SC.case("blocks")
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     # 150 x 37 (nx no multiple of 64) over the tile and a margin, north to south (negative dlat), rows padded by 5 floats
     nx, ny = 150, 37
@@ -273,7 +256,7 @@ def test_profile(topo, m):
     n = len(segs)
     valid = np.ones(n, bool)
     valid[invalid] = False
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     summary, samples = g.profile(segs, m)
     # the summary is the reduction of the device's own samples, exactly; ties go to the first sample
     SC.check_summaries(summary, samples, invalid, f"m = {m}")
@@ -343,7 +326,7 @@ def test_profile_errors(topo):
     import torch
     tiles, order, _, _ = SC.case("long")
     segs, _ = SC.profile_segments()
-    g = _renderer(topo, tiles, order)
+    g = renderer(topo, tiles, order)
     s_dev = torch.from_numpy(segs.view(np.uint8).reshape(-1, 64).copy()).cuda()
     smp = torch.zeros((len(segs), 8 * 16 + 8), dtype=torch.uint8, device="cuda")
     out = torch.zeros((len(segs), 16), dtype=torch.uint8, device="cuda")
@@ -363,15 +346,6 @@ def test_profile_errors(topo):
     assert L.topo_profile_read(g._h, 1, vp(segs), 1, None, vp(one)) == topo.TOPO_ERR_INVALID
     g.synchronize()
     g.close()
-
-
-def _strip(r, views, sw, sh):
-    import torch
-    n = len(views)
-    rgba = torch.zeros((n, sh, sw, 4), dtype=torch.uint8, device="cuda")
-    depth = torch.zeros((n, sh, sw), dtype=torch.float32, device="cuda")
-    r.render_views_device(views, sw, sh, rgba.data_ptr(), sh * sw * 4, sw * 4, depth.data_ptr(), sh * sw * 4, sw * 4)
-    return rgba, depth
 
 
 def test_surface_calls_change_no_frame_and_no_mask(topo):
@@ -423,7 +397,7 @@ def test_surface_calls_change_no_frame_and_no_mask(topo):
     for r, ask in ((a, False), (b, True)):
         r.set_stream(torch.cuda.current_stream().cuda_stream)
         r.set_pipeline_depth(2)
-        keep = [_strip(r, us[:2], sw, sh), _strip(r, us[2:7], sw, sh)]
+        keep = [strip(r, us[:2], sw, sh), strip(r, us[2:7], sw, sh)]
         if ask:
             r.surface_device(p_dev.data_ptr(), rec_dev.data_ptr(), len(pts))
             r.profile_device(s_dev.data_ptr(), len(segs), 50, sum_dev.data_ptr())
@@ -446,19 +420,19 @@ def _checked_run(T):
     status = 0
     for name in ("blocks", "polar", "void_pinf"):
         tiles, order, pts, _ = SC.case(name)
-        g = _renderer(T, tiles, order)
+        g = renderer(T, tiles, order)
         h.update(g.surface(SC.with_invalid(pts)[0]).tobytes())
         if name == "blocks":
             h.update(_grid(g, 6.99, 47.012, 1.013 / 150, -1.021 / 37, 150, 37, pad_px=1)[0].tobytes())
         status |= g.frame_status()["status"]
         g.close()
     tiles, order, pts = SC.big_tile()
-    g = _renderer(T, tiles, order)
+    g = renderer(T, tiles, order)
     h.update(g.surface(pts[::10]).tobytes())
     status |= g.frame_status()["status"]
     g.close()
     tiles, order, _, _ = SC.case("long")
-    g = _renderer(T, tiles, order)
+    g = renderer(T, tiles, order)
     for m in (2, 257):
         summary, samples = g.profile(SC.profile_segments()[0], m)
         h.update(summary.tobytes())
@@ -470,13 +444,5 @@ def _checked_run(T):
 
 
 def test_bounds_checked_build_records_no_out_of_range_index(topo):
-    check = os.path.join(os.path.dirname(topo.LIB_PATH), "libtopo_hip_check.so")
-    assert os.path.exists(check), "run __graft_entry__.build()"
-    code = f"import sys, json; sys.path[:0] = [{os.path.dirname(HERE)!r}, {HERE!r}]; import topo_renderer_amd as T; " \
-           f"import test_surface_gpu as m; print(json.dumps(dict(m._checked_run(T), lib=T.LIB_PATH)))"
-    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TOPO_HIP_LIB=check), capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    got = json.loads(res.stdout.strip().split("\n")[-1])
-    assert got["lib"].endswith("libtopo_hip_check.so")
-    assert not (got["status"] & 4), got          # kStatusBounds: an index a surface kernel formed was out of range
+    got = checked_run("test_surface_gpu")      # kStatusBounds: an index a surface kernel formed was out of range
     assert got["sha"] == _checked_run(topo)["sha"], "the bounds-checked build answers as the product build"

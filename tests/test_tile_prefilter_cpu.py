@@ -3,32 +3,21 @@ device's frustum test keeps: 1 000 seeded random views over a 3 x 3 mosaic, the 
 numpy.  A containment check: no tolerance."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import native
 import topo_renderer_amd as T
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "topo-renderer_amd", "csrc")
-_SO = os.path.join(_HERE, "_build", "libprefilter_shim.so")
 R0 = 6371000.0
 BCX, BCY = 60, 15          # cells per raster block (topo_kernels.h)
 
 
 @pytest.fixture(scope="module")
 def shim():
-    srcs = [os.path.join(_HERE, "prefilter_shim.cpp"), os.path.join(_CSRC, "host_math.cpp")]
-    deps = srcs + [os.path.join(_CSRC, f) for f in ("host_math.hpp", "topo_math.h")]
-    os.makedirs(os.path.dirname(_SO), exist_ok=True)
-    if not os.path.exists(_SO) or any(os.path.getmtime(f) > os.path.getmtime(_SO) for f in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-shared", "-o", _SO] + srcs)
-    L = C.CDLL(_SO)
-    L.shim_tile_prefilter.restype = C.c_uint32
+    L = native.load("libprefilter_shim.so", ["prefilter_shim.cpp", native.HOST_MATH], {"shim_tile_prefilter": C.c_uint32, "shim_tile_sphere_doubles": C.c_uint32})
     L.shim_tile_prefilter.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
-    L.shim_tile_sphere_doubles.restype = C.c_uint32
     assert L.shim_tile_sphere_doubles() == 5
     return L
 

@@ -3,20 +3,16 @@ agreement with the independent reference tests/test_unwrap_cpu.py establishes; t
 through the source map; pitches, partial outputs, errors, and that an unwrap changes no frame."""
 import ctypes as C
 import hashlib
-import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import unwrap_cases as UC
 import unwrap_ref as UR
+from gpu_support import checked_run, unwrap_run
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 _SOURCES = {}
 
 
@@ -44,32 +40,12 @@ def rendered(T, name, fmt=None):
     return _SOURCES[key]
 
 
-def run(T, g, params, views, sw, sh, rgba_src, depth_src, want="rds", slack=48):
-    """topo_unwrap_device into 0xAB-filled outputs whose pitch is `slack` bytes (rounded up to 16) more than a row; -> dict of numpy
-    arrays (rgba (H, W, 4) u8, depth (H, W) u32 bits, src (H, W) i32) for the outputs in `want`; the bytes beyond out_w must be untouched."""
-    import torch
-    W, H = int(params["out_w"][0]), int(params["out_h"][0])
-    pitch = (W * 4 + slack + 15) // 16 * 16
-    bufs = {k: torch.full((H, pitch), 0xAB, dtype=torch.uint8, device="cuda") for k in want}
-    ptr = lambda k: bufs[k].data_ptr() if k in bufs else 0
-    g.unwrap_device(params, views, sw, sh, rgba_src_ptr=rgba_src.data_ptr() if "r" in want else 0, depth_src_ptr=depth_src.data_ptr() if "d" in want else 0,
-                    rgba_out_ptr=ptr("r"), rgba_out_pitch=pitch, depth_out_ptr=ptr("d"), depth_out_pitch=pitch, src_out_ptr=ptr("s"), src_out_pitch=pitch)
-    g.synchronize()
-    out = {}
-    for k, b in bufs.items():
-        a = b.cpu().numpy()
-        assert (a[:, W * 4:] == 0xAB).all(), f"output {k}: bytes between out_w and the pitch were written"
-        body = np.ascontiguousarray(a[:, :W * 4])
-        out[k] = body.reshape(H, W, 4) if k == "r" else body.view(np.uint32 if k == "d" else np.int32).reshape(H, W)
-    return out
-
-
 @pytest.mark.parametrize("name", UC.NEAREST_CASES)
 def test_nearest_cases(topo, name):
     import unwrap_emul
     views, sw, sh, params, _ = UC.case(name)
     g, rgba, depth = rendered(topo, name)
-    got = run(topo, g, params, views, sw, sh, rgba, depth)
+    got = unwrap_run(topo, g, params, views, sw, sh, rgba, depth)
     emu = unwrap_emul.unwrap(params, views, sw, sh)
     assert np.array_equal(got["s"], emu["src"]), f"{int((got['s'] != emu['src']).sum())} source-map entries differ from the emulation"
     r, d = rgba.cpu().numpy(), depth.cpu().numpy().view(np.uint32)
@@ -86,7 +62,7 @@ def test_bilinear_equals_the_emulation(topo, fmt):
     fmt = getattr(topo, fmt)
     views, sw, sh, params, _ = UC.case("g")
     g, rgba, depth = rendered(topo, "g", fmt)
-    got = run(topo, g, params, views, sw, sh, rgba, depth)
+    got = unwrap_run(topo, g, params, views, sw, sh, rgba, depth)
     emu = unwrap_emul.unwrap(params, views, sw, sh, rgba.cpu().numpy(), depth.cpu().numpy(), srgb=fmt == topo.FORMAT_RGBA8_UNORM_SRGB)
     assert np.array_equal(got["s"], emu["src"])
     assert np.array_equal(got["r"], emu["rgba"]), f"{int((got['r'] != emu['rgba']).sum())} channels differ from the emulation"
@@ -97,9 +73,9 @@ def test_bilinear_equals_the_emulation(topo, fmt):
 def test_partial_outputs(topo):
     views, sw, sh, params, _ = UC.case("b")
     g, rgba, depth = rendered(topo, "b")
-    full = run(topo, g, params, views, sw, sh, rgba, depth)
+    full = unwrap_run(topo, g, params, views, sw, sh, rgba, depth)
     for want in ("r", "d", "s", "rd", "ds"):
-        part = run(topo, g, params, views, sw, sh, rgba, depth, want=want, slack=0)
+        part = unwrap_run(topo, g, params, views, sw, sh, rgba, depth, want=want, slack=0)
         for k in want:
             assert np.array_equal(part[k], full[k]), (want, k)
 
@@ -163,7 +139,7 @@ def test_unwrap_changes_no_frame(topo):
     for yaw, pitch, fov in ((40, 10, 70), (120, 60, 90), (300, 2, 50)):
         b.render_views_device(views, sw, sh, rgba.data_ptr(), sh * sw * 4, sw * 4, depth.data_ptr(), sh * sw * 4, sw * 4)
         a.render_views_device(views, sw, sh, rgba_a.data_ptr(), sh * sw * 4, sw * 4, depth_a.data_ptr(), sh * sw * 4, sw * 4)
-        run(topo, b, params, views, sw, sh, rgba, depth)
+        unwrap_run(topo, b, params, views, sw, sh, rgba, depth)
         a.synchronize()
         assert torch.equal(rgba, rgba_a) and torch.equal(depth, depth_a)
         u = sc.uniforms(W, H, yaw, pitch, fov, 0)
@@ -182,7 +158,7 @@ def _checked_run(T):
     for name in ("b", "c", "d", "f", "g"):
         views, sw, sh, params, _ = UC.case(name)
         g, rgba, depth = rendered(T, name)
-        got = run(T, g, params, views, sw, sh, rgba, depth)
+        got = unwrap_run(T, g, params, views, sw, sh, rgba, depth)
         for k in "rds":
             h.update(got[k].tobytes())
         status |= g.frame_status()["status"]
@@ -191,14 +167,6 @@ def _checked_run(T):
 
 
 def test_bounds_checked_build_records_no_out_of_range_index(topo):
-    check = os.path.join(os.path.dirname(topo.LIB_PATH), "libtopo_hip_check.so")
-    assert os.path.exists(check), "run __graft_entry__.build()"
-    code = f"import sys, json; sys.path[:0] = [{os.path.dirname(HERE)!r}, {HERE!r}]; import topo_renderer_amd as T; " \
-           f"import test_unwrap_gpu as m; print(json.dumps(dict(m._checked_run(T), lib=T.LIB_PATH)))"
-    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TOPO_HIP_LIB=check), capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    got = json.loads(res.stdout.strip().split("\n")[-1])
-    assert got["lib"].endswith("libtopo_hip_check.so")
-    assert not (got["status"] & 4), got          # kStatusBounds: an index k_unwrap (or any kernel) formed was out of range
+    got = checked_run("test_unwrap_gpu")      # kStatusBounds: an index k_unwrap (or any kernel) formed was out of range
     want = _checked_run(topo)
     assert got["sha"] == want["sha"] and got["status"] == want["status"]

@@ -94,7 +94,7 @@ def test_expected_masks_agree_with_f64_ray_cast(orc):
     import topo_renderer_amd as T
     from oracle import ray_check as RC
     from scenes import Scene
-    from test_ray_check_cpu import relief
+    from scenes import relief
     tile, W, H, yaw, pitch, fov = 24, 96, 64, 30.0, 25.0, 60.0
     sc = Scene(tile, 2, 2, eye_dh=4000.0, height_fn=relief)
     o = orc.OracleRenderer(W, H)

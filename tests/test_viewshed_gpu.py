@@ -1,20 +1,16 @@
 """Viewshed on the GPU (topo_viewshed_*): every tile's mask equals, bit for bit, the cells of the oracle's per-pixel winners
 (render_winners()) OR-ed over the same frames."""
 import hashlib
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from gpu_support import checked_run, pair, strip
 from scenes import Scene, assert_same_frame
-from viewshed_ref import expected_masks, geo_order, mark
+from viewshed_ref import assert_masks, expected_masks, geo_order, mark
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _oracle_winners(o, W, H, views, pu):
@@ -23,22 +19,6 @@ def _oracle_winners(o, W, H, views, pu):
         o.update(W, H, u, pu)
         out.append(o.render_winners()[1])
     return out
-
-
-def _assert_masks(g, want, what):
-    for loc, m in want.items():
-        got = g.viewshed(*loc)
-        assert got.shape == m.shape
-        bad = np.argwhere(got != m)
-        assert len(bad) == 0, f"{what}: tile {loc}: {len(bad)} cells differ (first (y, x) {tuple(bad[0])}: got {got[tuple(bad[0])]}); " \
-                              f"{int(m.sum())} expected marked"
-
-
-def _pair(topo, orc, sc, W, H):
-    g, o = topo.TerrainRenderer(W, H), orc.OracleRenderer(W, H)
-    sc.load(g)
-    sc.load(o)
-    return g, o
 
 
 FRAMES = [
@@ -54,7 +34,7 @@ FRAMES = [
 def test_single_frames_match_oracle_winners(topo, orc, cfg):
     tile, nla, nlo, dh, W, H, views = cfg
     sc = Scene(tile, nla, nlo, eye_dh=dh)
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     g.viewshed_enable(True)
     pu = topo.post_uniforms(W, H)
     marked = 0
@@ -67,14 +47,14 @@ def test_single_frames_match_oracle_winners(topo, orc, cfg):
         assert_same_frame(frame, o.render(), f"yaw {yaw} pitch {pitch}")
         want = expected_masks([o.render_winners()[1]], sc.locs, tile, tile)
         marked += sum(int(m.sum()) for m in want.values())
-        _assert_masks(g, want, f"{cfg[:4]} yaw {yaw} pitch {pitch}")
+        assert_masks(g, want, f"{cfg[:4]} yaw {yaw} pitch {pitch}")
     assert marked > 0
 
 
 def test_accumulation_over_frames_and_reset(topo, orc):
     sc = Scene(96, 2, 2, eye_dh=80.0)
     W, H = 192, 96
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     pu = topo.post_uniforms(W, H)
     views = [sc.uniforms(W, H, yaw, 8, 70, 0) for yaw in (0, 90, 180, 270)]
     with pytest.raises(topo.TopoError) as e:
@@ -88,7 +68,7 @@ def test_accumulation_over_frames_and_reset(topo, orc):
         g.update(W, H, u, pu)
         g.render()
     want = expected_masks(_oracle_winners(o, W, H, views, pu), sc.locs, 96, 96)
-    _assert_masks(g, want, "four yaws")
+    assert_masks(g, want, "four yaws")
     single = expected_masks(_oracle_winners(o, W, H, views[:1], pu), sc.locs, 96, 96)
     assert sum(int(m.sum()) for m in want.values()) > sum(int(m.sum()) for m in single.values())
     st = g.debug_viewshed_stats()
@@ -97,7 +77,7 @@ def test_accumulation_over_frames_and_reset(topo, orc):
     g.viewshed_enable(False)
     g.update(W, H, sc.uniforms(W, H, 45, 30, 70, 0), pu)
     g.render()
-    _assert_masks(g, want, "after accumulation off")
+    assert_masks(g, want, "after accumulation off")
     g.viewshed_reset()
     for loc in sc.locs:
         assert not g.viewshed(*loc).any()
@@ -107,39 +87,30 @@ def test_accumulation_over_frames_and_reset(topo, orc):
     assert e.value.code == topo.TOPO_ERR_NOT_FOUND
 
 
-def _strip(r, views, sw, sh):
-    import torch
-    n = len(views)
-    rgba = torch.zeros((n, sh, sw, 4), dtype=torch.uint8, device="cuda")
-    depth = torch.zeros((n, sh, sw), dtype=torch.float32, device="cuda")
-    r.render_views_device(views, sw, sh, rgba.data_ptr(), sh * sw * 4, sw * 4, depth.data_ptr(), sh * sw * 4, sw * 4)
-    return rgba, depth
-
-
 def test_panorama_submission_and_pipelined_burst(topo, orc):
     import torch
     sc = Scene(96, 2, 2, eye_dh=120.0)
     sw, sh = 96, 128
-    g, o = _pair(topo, orc, sc, sw, sh)
+    g, o = pair(topo, orc, sc, sw, sh)
     pu = topo.post_uniforms(sw, sh)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     g.viewshed_enable(True)
     us = sc.panorama(sw, sh, yaw0_deg=11.0)
-    keep = _strip(g, us, sw, sh)
+    keep = strip(g, us, sw, sh)
     g.synchronize()
     want = expected_masks(_oracle_winners(o, sw, sh, us, pu), sc.locs, 96, 96)
-    _assert_masks(g, want, "8-sector submission")
+    assert_masks(g, want, "8-sector submission")
     # frames in flight on two contexts, several submissions
     g.viewshed_reset()
     g.set_pipeline_depth(2)
     views = []
     for k in range(5):
         us = sc.panorama(sw, sh, yaw0_deg=7.0 * k)
-        keep = (keep, _strip(g, us, sw, sh))
+        keep = (keep, strip(g, us, sw, sh))
         views += list(us)
     g.join()
     want = expected_masks(_oracle_winners(o, sw, sh, views, pu), sc.locs, 96, 96)
-    _assert_masks(g, want, "pipeline depth 2 burst")
+    assert_masks(g, want, "pipeline depth 2 burst")
     torch.cuda.synchronize()
 
 
@@ -150,7 +121,7 @@ def test_panorama_slot_path_and_batch(topo, orc):
     import torch
     sc = Scene(96, 2, 2, eye_dh=120.0)
     sw, sh = 96, 160
-    g, o = _pair(topo, orc, sc, sw, sh)
+    g, o = pair(topo, orc, sc, sw, sh)
     pu = topo.post_uniforms(sw, sh)
     g.set_stream(torch.cuda.current_stream().cuda_stream)
     g.viewshed_enable(True)
@@ -159,7 +130,7 @@ def test_panorama_slot_path_and_batch(topo, orc):
     want = expected_masks(_oracle_winners(o, sw, sh, sc.panorama(sw, sh, yaw0_deg=25.0), pu), sc.locs, 96, 96)
     g.render_panorama(None, sc.eye, math.radians(25.0), sw, sh, sc.vlon, sc.vlat, strip.data_ptr(), depth.data_ptr())
     g.synchronize()
-    _assert_masks(g, want, "panorama, world of one")
+    assert_masks(g, want, "panorama, world of one")
     os.environ["TOPO_PANORAMA_FORCE_SLOTS"] = "1"
     os.environ["TOPO_PANORAMA_BAND_BYTES"] = str(sw * 4 * 50)
     try:
@@ -169,7 +140,7 @@ def test_panorama_slot_path_and_batch(topo, orc):
             want = expected_masks(_oracle_winners(o, sw, sh, sc.panorama(sw, sh, yaw0_deg=yaw0), pu), sc.locs, 96, 96)
             g.render_panorama(topo.Comm(0, 1), sc.eye, math.radians(yaw0), sw, sh, sc.vlon, sc.vlat, strip.data_ptr(), depth.data_ptr())
             g.synchronize()
-            _assert_masks(g, want, f"slot-by-slot panorama yaw0 {yaw0}")
+            assert_masks(g, want, f"slot-by-slot panorama yaw0 {yaw0}")
     finally:
         del os.environ["TOPO_PANORAMA_FORCE_SLOTS"], os.environ["TOPO_PANORAMA_BAND_BYTES"]
     rng = np.random.default_rng(4)
@@ -190,14 +161,14 @@ def test_panorama_slot_path_and_batch(topo, orc):
         views += list(topo.panorama_uniforms(eyes[v], yaws[v], sw, sh, suns[v][0], suns[v][1], 0))
     want = expected_masks(_oracle_winners(o, sw, sh, views, pu), sc.locs, 96, 96)
     assert sum(int(m.sum()) for m in want.values()) > 0
-    _assert_masks(g, want, "batch of three viewpoints")
+    assert_masks(g, want, "batch of three viewpoints")
     torch.cuda.synchronize()
 
 
 def test_tile_lifecycle_replace_and_unload(topo, orc):
     sc = Scene(64, 2, 2, eye_dh=150.0)
     W, H = 256, 128
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     pu = topo.post_uniforms(W, H)
     g.viewshed_enable(True)
     va = [sc.uniforms(W, H, yaw, 12, 80, 0) for yaw in (30, 150, 260)]
@@ -205,7 +176,7 @@ def test_tile_lifecycle_replace_and_unload(topo, orc):
         g.update(W, H, u, pu)
         g.render()
     masks = expected_masks(_oracle_winners(o, W, H, va, pu), sc.locs, 64, 64)
-    _assert_masks(g, masks, "before")
+    assert_masks(g, masks, "before")
     order = geo_order(sc.locs)
     replaced, gone = order[1], order[0]          # unloading rank 0 shifts every other rank
     assert masks[replaced].any() and masks[gone].any()
@@ -214,7 +185,7 @@ def test_tile_lifecycle_replace_and_unload(topo, orc):
     o.add_terrain(replaced[0], replaced[1], hts, *sc.transform(replaced))
     assert not g.viewshed(*replaced).any()
     masks[replaced][:] = False
-    _assert_masks(g, masks, "after replacing a tile")
+    assert_masks(g, masks, "after replacing a tile")
     g.unload_terrain(*gone)
     o.unload_terrain(*gone)
     with pytest.raises(topo.TopoError) as e:
@@ -228,13 +199,13 @@ def test_tile_lifecycle_replace_and_unload(topo, orc):
         g.render()
     for w in _oracle_winners(o, W, H, vb, pu):
         mark(masks, w, left, 64, 64)
-    _assert_masks(g, masks, "after unloading a tile (ranks shifted)")
+    assert_masks(g, masks, "after unloading a tile (ranks shifted)")
 
 
 def test_queue_overflow_frames_mark_only_when_complete(topo, orc):
     sc = Scene(12, 2, 2, eye_dh=60.0)
     W, H = 640, 480
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     u, pu = sc.uniforms(W, H, 10, 35, 110, 0), topo.post_uniforms(W, H)
     g.update(W, H, u, pu)
     o.update(W, H, u, pu)
@@ -244,7 +215,7 @@ def test_queue_overflow_frames_mark_only_when_complete(topo, orc):
     g.debug_set_queue_caps(0, 2 | 0x80000000)
     assert_same_frame(g.render(), o.render(), "rare queue grown on demand")
     assert g.counters()["rare_items"] > 2
-    _assert_masks(g, want, "grow-and-retry")
+    assert_masks(g, want, "grow-and-retry")
     # an explicit small rare cap on the asynchronous path: the frame is incomplete, join() says so, the masks are untouched
     import torch
     g.viewshed_reset()
@@ -259,7 +230,7 @@ def test_queue_overflow_frames_mark_only_when_complete(topo, orc):
     g.debug_set_queue_caps(0, 0)
     g.render_device(rgba.data_ptr(), W * 4)
     g.join()
-    _assert_masks(g, want, "defaults restored")
+    assert_masks(g, want, "defaults restored")
 
 
 def test_accumulation_changes_no_output(topo):
@@ -285,7 +256,7 @@ def test_full_size_tiles(topo, orc):
     """1200 x 1200 tiles: 1.44 M cells, so bit indices run past 2^20."""
     sc = Scene(1200, 1, 1, eye_dh=300.0)
     W, H = 256, 96
-    g, o = _pair(topo, orc, sc, W, H)
+    g, o = pair(topo, orc, sc, W, H)
     g.viewshed_enable(True)
     pu = topo.post_uniforms(W, H)
     views = [sc.uniforms(W, H, yaw, 3, 70, 0) for yaw in (0, 120, 240)]
@@ -293,7 +264,7 @@ def test_full_size_tiles(topo, orc):
         g.update(W, H, u, pu)
         g.render()
     want = expected_masks(_oracle_winners(o, W, H, views, pu), sc.locs, 1200, 1200)
-    _assert_masks(g, want, "1200 x 1200 tiles")
+    assert_masks(g, want, "1200 x 1200 tiles")
     high = 0
     for m in want.values():
         y, x = np.nonzero(m)
@@ -322,10 +293,10 @@ def _checked_run(T):
     sc2.load(p)
     p.viewshed_enable(True)
     p.set_stream(torch.cuda.current_stream().cuda_stream)
-    keep = _strip(p, sc2.panorama(sw, sh, yaw0_deg=3.0), sw, sh)
+    keep = strip(p, sc2.panorama(sw, sh, yaw0_deg=3.0), sw, sh)
     p.synchronize()
     p.unload_terrain(*geo_order(sc2.locs)[0])
-    keep = (keep, _strip(p, sc2.panorama(sw, sh, yaw0_deg=30.0), sw, sh))
+    keep = (keep, strip(p, sc2.panorama(sw, sh, yaw0_deg=30.0), sw, sh))
     p.synchronize()
     status |= p.frame_status()["status"]
     h = hashlib.sha256()
@@ -341,14 +312,6 @@ def _checked_run(T):
 
 
 def test_bounds_checked_build_marks_no_out_of_range_index(topo):
-    check = os.path.join(os.path.dirname(topo.LIB_PATH), "libtopo_hip_check.so")
-    assert os.path.exists(check), "run __graft_entry__.build()"
-    code = f"import sys, json; sys.path[:0] = [{os.path.dirname(HERE)!r}, {HERE!r}]; import topo_renderer_amd as T; " \
-           f"import test_viewshed_gpu as m; print(json.dumps(dict(m._checked_run(T), lib=T.LIB_PATH)))"
-    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, TOPO_HIP_LIB=check), capture_output=True, text=True, timeout=600)
-    assert res.returncode == 0, res.stderr[-2000:]
-    got = json.loads(res.stdout.strip().split("\n")[-1])
-    assert got["lib"].endswith("libtopo_hip_check.so")
-    assert not (got["status"] & 4), got          # kStatusBounds: an index k_viewshed (or any kernel) formed was out of range
+    got = checked_run("test_viewshed_gpu")      # kStatusBounds: an index k_viewshed (or any kernel) formed was out of range
     want = _checked_run(topo)
     assert got["sha"] == want["sha"] and got["status"] == want["status"]

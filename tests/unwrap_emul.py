@@ -3,28 +3,20 @@ of host_math.cpp)."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "..", "topo-renderer_amd", "csrc")
-_SO = os.path.join(_HERE, "_build", "libunwrap_emul.so")
+import native
+from emul_tiles import vp
+
 _LIB = None
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        srcs = [os.path.join(_HERE, "unwrap_emul.cpp"), os.path.join(_CSRC, "host_math.cpp")]
-        hdrs = [os.path.join(_CSRC, f) for f in ("topo_math.h", "topo_pipeline.h", "topo_unwrap.h", "srgb_tables.h", "host_math.hpp")]
-        hdrs.append(os.path.join(_HERE, "..", "include", "topo_hip.h"))
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if not os.path.exists(_SO) or any(os.path.getmtime(f) > os.path.getmtime(_SO) for f in srcs + hdrs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-shared", "-o", _SO] + srcs)
-        _LIB = C.CDLL(_SO)
-        _LIB.emul_unwrap.restype = C.c_int
+        _LIB = native.load("libunwrap_emul.so", ["unwrap_emul.cpp", native.HOST_MATH],
+                           {"emul_unwrap": C.c_int})
     return _LIB
 
 
@@ -34,7 +26,6 @@ def unwrap(params, uniforms_list, src_w, src_h, rgba_src=None, depth_src=None, s
     p = np.ascontiguousarray(params).reshape(-1)[:1]
     us = np.ascontiguousarray(np.stack([np.ascontiguousarray(u).view(np.float32).reshape(40) for u in uniforms_list]))
     W, H = int(p["out_w"][0]), int(p["out_h"][0])
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
     rs = None if rgba_src is None else np.ascontiguousarray(rgba_src, np.uint8)
     ds = None if depth_src is None else np.ascontiguousarray(depth_src, np.float32)
     for a, shape in ((rs, (len(us), src_h, src_w, 4)), (ds, (len(us), src_h, src_w))):

@@ -38,3 +38,12 @@ def expected_masks(frames_winners, locs, tile_w, tile_h):
     for w in frames_winners:
         mark(masks, w, locs, tile_w, tile_h)
     return masks
+
+
+def assert_masks(g, want, what):
+    for loc, m in want.items():
+        got = g.viewshed(*loc)
+        assert got.shape == m.shape
+        bad = np.argwhere(got != m)
+        assert len(bad) == 0, f"{what}: tile {loc}: {len(bad)} cells differ (first (y, x) {tuple(bad[0])}: got {got[tuple(bad[0])]}); " \
+                              f"{int(m.sum())} expected marked"
