@@ -494,6 +494,49 @@ int topo_profile_device(topo_ctx* ctx, uint32_t n, const topo_ray* segs_dev, uin
 /* Host memory: samples null, or n * m pairs, densely packed; waits. */
 int topo_profile_read(topo_ctx* ctx, uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary);
 
+/* ---- visibility: what an observer sees, as a map or over a list ------------------------------------------------------------------
+ * "From this hut, which ground can be seen?"  "Which of these 5000 peaks are in sight from here?" -- without a rendered frame, its
+ * pixels or its field of view.  No new geometry: a point is found on the drawn terrain exactly as topo_surface_* finds it, and the
+ * sight line is tested exactly as the shadow ray of topo_sunlit_map_device is.
+ * Observer.  u is the unit direction of (lon_deg, lat_deg); with TOPO_OBSERVER_ABOVE_TERRAIN in flags height_m is measured above
+ * the drawn terrain under the point (base = the height topo_surface_* reports there), otherwise above the sphere R0 (base = 0);
+ * O = ((R0 + base) + height_m) u.  An observer is UNUSABLE when its point is invalid (as topo_surface_* defines it), its height is
+ * not finite, or the flag is set and no terrain lies under it: each of its targets is TOPO_VIS_NO_OBSERVER.
+ * Target.  A point (lon, lat) and the call's target_height_m (finite, 0 <= h <= 1e5, else TOPO_ERR_INVALID).  An invalid point or one
+ * with no terrain under it is TOPO_VIS_NONE; otherwise T = ((R0 + t) + h) u with t and the triangle from the surface rule.
+ * Class.  D = O - T, L = |D|, d = D / L.  (1) !(L > 2e-3 m): the observer sits at the target, TOPO_VIS_VISIBLE.  (2) Only for h == 0:
+ * with N = (v1 - v0) x (v2 - v0) of the target's triangle, turned to the side of u, !(N . D > 0) is TOPO_VIS_AWAY -- the ground itself
+ * faces away.  (3) The ray from T along d against the triangles of the rays, a hit counting for 1e-3 m < t <= L: any hit
+ * TOPO_VIS_HIDDEN, none TOPO_VIS_VISIBLE.  For h == 0 the target's own triangle does not count; for h > 0 every triangle does (a mast
+ * on a back slope can be hidden by its own slope).  The answer is a function of the observer, the target and the tile set.
+ * The calls read the resident tiles only and need no submission; they run on the context's stream (topo_set_stream) behind whatever
+ * was queued there, and write nothing but their outputs.  observers is HOST memory, read before the call returns;
+ * n_observers <= 64, and zero observers (or n = 0) is a no-op.  TOPO_ERR_INVALID for null pointers, more than 64 observers and a
+ * target height out of range. */
+typedef struct topo_observer { double lon_deg, lat_deg, height_m; uint32_t flags; uint32_t _reserved; } topo_observer;      /* 32 bytes */
+#define TOPO_OBSERVER_ABOVE_TERRAIN 1u
+#define TOPO_VIS_NONE 0          /* no terrain under the target, or an invalid point */
+#define TOPO_VIS_VISIBLE 1
+#define TOPO_VIS_AWAY 2          /* h == 0 only: the target's own triangle faces away from the observer */
+#define TOPO_VIS_HIDDEN 3        /* other terrain is in the way */
+#define TOPO_VIS_NO_OBSERVER 4   /* the observer is unusable */
+/* The dense form: one byte per (observer o, row r, column c) at out_dev + o * layer_stride_bytes + r * pitch_bytes + c for the target
+ * at lon0 + c * dlon, lat0 + r * dlat (one rounded product, one rounded sum, as topo_surface_grid_device) -- the byte the list call
+ * gives for the same numbers.  Device memory, no alignment; the bytes between nx and the pitch and between layers are left alone.
+ * dlon and dlat may be negative or zero.  TOPO_ERR_INVALID also for a zero nx or ny, non-finite grid parameters, pitch_bytes < nx,
+ * layer_stride_bytes < ny * pitch_bytes and ceil(nx / 64) * ny * n_observers >= 2^32.  Asynchronous. */
+int topo_visibility_grid_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double lon0_deg, double lat0_deg, double dlon_deg, double dlat_deg,
+                                uint32_t nx, uint32_t ny, double target_height_m, uint8_t* out_dev, size_t layer_stride_bytes, size_t pitch_bytes);
+/* The list form: n (lon, lat) pairs in degrees at lonlat_dev (device memory, 16-byte aligned) -> out_dev[o * list_stride_bytes + i]
+ * (device memory; list_stride_bytes >= n, the bytes behind a list are left alone).  Asynchronous. */
+int topo_visibility_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_dev, double target_height_m,
+                           uint8_t* out_dev, size_t list_stride_bytes);
+/* Host memory: n pairs in, out[o * n + i]; waits. */
+int topo_visibility_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out);
+/* Host helper, f64, no GPU: the ECEF point (R0 + height_m) u of (lon_deg, lat_deg) in the frame of the rays -- an endpoint of a
+ * topo_ray, or the O and T above. */
+void topo_ecef_from_lonlat(double lon_deg, double lat_deg, double height_m, double out[3]);
+
 /* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
  * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
  * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --

@@ -56,6 +56,10 @@ PROFILE_NO_SAMPLE = 0xFFFFFFFF
 SURFACE_DTYPE = np.dtype([("height_m", "<f8"), ("slope_deg", "<f4"), ("aspect_deg", "<f4"), ("kind", "<i4"), ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"),
                           ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("w1", "<f4"), ("w2", "<f4")])
 PROFILE_SUMMARY_DTYPE = np.dtype([("min_clearance_m", "<f4"), ("min_sample", "<u4"), ("n_terrain", "<u4"), ("kind", "<i4")])
+VIS_NONE, VIS_VISIBLE, VIS_AWAY, VIS_HIDDEN, VIS_NO_OBSERVER = 0, 1, 2, 3, 4
+OBSERVER_ABOVE_TERRAIN = 1
+# topo_observer, 32 bytes
+OBSERVER_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f8"), ("flags", "<u4"), ("_reserved", "<u4")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
 # topo_unwrap_params, 48 bytes
@@ -189,6 +193,10 @@ def lib():
             "topo_surface_grid_device": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_double, u32, u32, vp, sz]),
             "topo_profile_device": (C.c_int, [vp, u32, vp, u32, vp, sz, vp]),
             "topo_profile_read": (C.c_int, [vp, u32, vp, u32, vp, vp]),
+            "topo_visibility_grid_device": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, C.c_double, C.c_double, u32, u32, C.c_double, vp, sz, sz]),
+            "topo_visibility_device": (C.c_int, [vp, u32, vp, u32, vp, C.c_double, vp, sz]),
+            "topo_visibility_read": (C.c_int, [vp, u32, vp, u32, vp, C.c_double, vp]),
+            "topo_ecef_from_lonlat": (None, [C.c_double, C.c_double, C.c_double, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
         }
@@ -329,6 +337,23 @@ def rays(origin, direction, t_min=0.0, t_max=np.inf) -> np.ndarray:
     o, d = np.broadcast_arrays(np.atleast_2d(np.asarray(origin, np.float64)), np.atleast_2d(np.asarray(direction, np.float64)))
     out = np.zeros(len(o), RAY_DTYPE)
     out["origin"], out["dir"], out["t_min"], out["t_max"] = o, d, t_min, t_max
+    return out
+
+
+def ecef_from_lonlat(lon_deg: float, lat_deg: float, height_m: float = 0.0) -> np.ndarray:
+    """topo_ecef_from_lonlat: the f64 ECEF point height_m above the sphere R0 at (lon_deg, lat_deg), in the frame of the rays."""
+    out = np.zeros(3, dtype=np.float64)
+    lib().topo_ecef_from_lonlat(lon_deg, lat_deg, height_m, _p(out))
+    return out
+
+
+def observers(lon_deg, lat_deg, height_m, above_terrain=True) -> np.ndarray:
+    """OBSERVER_DTYPE records (topo_observer) from arrays (or scalars) of longitude, latitude and height; above_terrain: the height is
+    measured above the drawn terrain (OBSERVER_ABOVE_TERRAIN), else above the sphere R0."""
+    lo, la, h, f = np.broadcast_arrays(np.atleast_1d(np.asarray(lon_deg, np.float64)), np.asarray(lat_deg, np.float64), np.asarray(height_m, np.float64),
+                                       np.asarray(above_terrain, bool))
+    out = np.zeros(len(lo), OBSERVER_DTYPE)
+    out["lon_deg"], out["lat_deg"], out["height_m"], out["flags"] = lo, la, h, np.where(f, OBSERVER_ABOVE_TERRAIN, 0)
     return out
 
 
@@ -843,6 +868,35 @@ class TerrainRenderer:
         (terrain, line) f32 pairs per segment at samples_ptr + i * segment_stride_bytes (default 8 * m); queued on the context's stream."""
         self._check(lib().topo_profile_device(self._h, n, C.c_void_p(segs_ptr) if segs_ptr else None, m, C.c_void_p(samples_ptr) if samples_ptr else None,
                                               8 * m if segment_stride_bytes is None else segment_stride_bytes, C.c_void_p(summary_ptr) if summary_ptr else None))
+
+    # visibility: what observers see of the drawn terrain (include/topo_hip.h); no submission needed
+    def visibility_grid_device(self, obs, lon0: float, lat0: float, dlon: float, dlat: float, nx: int, ny: int, out_ptr: int, target_height_m: float = 0.0,
+                               layer_stride_bytes: int = None, pitch_bytes: int = None):
+        """topo_visibility_grid_device: one byte (VIS_*) per (observer o, row r, column c) at out_ptr + o * layer_stride_bytes + r *
+        pitch_bytes + c for the target at lon0 + c * dlon, lat0 + r * dlat (device memory; defaults: densely packed); obs:
+        OBSERVER_DTYPE records (see observers()); queued on the context's stream."""
+        o = np.ascontiguousarray(obs, dtype=OBSERVER_DTYPE).reshape(-1)
+        pitch = nx if pitch_bytes is None else pitch_bytes
+        stride = pitch * ny if layer_stride_bytes is None else layer_stride_bytes
+        self._check(lib().topo_visibility_grid_device(self._h, len(o), _p(o) if len(o) else None, lon0, lat0, dlon, dlat, nx, ny, target_height_m,
+                                                      C.c_void_p(out_ptr) if out_ptr else None, stride, pitch))
+
+    def visibility_device(self, obs, lonlat_ptr: int, n: int, out_ptr: int, target_height_m: float = 0.0, list_stride_bytes: int = None):
+        """topo_visibility_device: n (lon, lat) f64 pairs at lonlat_ptr (device memory, 16-byte aligned) -> one byte (VIS_*) per
+        (observer o, entry i) at out_ptr + o * list_stride_bytes + i (default stride n); queued on the context's stream."""
+        o = np.ascontiguousarray(obs, dtype=OBSERVER_DTYPE).reshape(-1)
+        self._check(lib().topo_visibility_device(self._h, len(o), _p(o) if len(o) else None, n, C.c_void_p(lonlat_ptr) if lonlat_ptr else None, target_height_m,
+                                                 C.c_void_p(out_ptr) if out_ptr else None, n if list_stride_bytes is None else list_stride_bytes))
+
+    def visibility(self, obs, lonlat, target_height_m: float = 0.0) -> np.ndarray:
+        """topo_visibility_read: OBSERVER_DTYPE records and (n, 2) f64 (longitude, latitude) in degrees -> (observers, n) uint8 classes
+        (VIS_*); waits."""
+        o = np.ascontiguousarray(obs, dtype=OBSERVER_DTYPE).reshape(-1)
+        p = np.ascontiguousarray(lonlat, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros((len(o), len(p)), np.uint8)
+        self._check(lib().topo_visibility_read(self._h, len(o), _p(o) if len(o) else None, len(p), _p(p) if len(p) else None, target_height_m,
+                                               _p(out) if out.size else None))
+        return out
 
     # unwrap: finished views that share an eye as one azimuth / elevation image (include/topo_hip.h)
     def unwrap_device(self, params, uniforms_list, src_w: int, src_h: int, rgba_src_ptr: int = 0, rgba_view_stride: int = None, rgba_pitch: int = None,

@@ -1,7 +1,8 @@
-// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, unwrap), the tile-set
+// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, visibility, unwrap), the tile-set
 // tables they read and their handle on the latest submission.  The frame path is terrain_renderer.cpp (see terrain_renderer.hpp).
 #include "terrain_renderer.hpp"
 #include "topo_surface.h"
+#include "topo_visibility.h"
 
 #include <cmath>
 #include <cstring>
@@ -16,6 +17,9 @@ static_assert(sizeof(RayHit) == sizeof(topo_ray_hit) && sizeof(topo_ray_hit) == 
 static_assert(sizeof(SurfacePoint) == sizeof(topo_surface_point) && sizeof(topo_surface_point) == 48, "surface record layout");
 static_assert(sizeof(ProfileSummary) == sizeof(topo_profile_summary) && sizeof(topo_profile_summary) == 16, "profile summary layout");
 static_assert(kSurfaceTerrain == TOPO_SURFACE_TERRAIN && kSurfaceNone == TOPO_SURFACE_NONE && kSurfaceInvalid == TOPO_SURFACE_INVALID, "surface kinds");
+static_assert(sizeof(VisObserver) == sizeof(topo_observer) && sizeof(topo_observer) == 32, "observer layout");
+static_assert(kVisNone == TOPO_VIS_NONE && kVisVisible == TOPO_VIS_VISIBLE && kVisAway == TOPO_VIS_AWAY && kVisHidden == TOPO_VIS_HIDDEN && kVisNoObserver == TOPO_VIS_NO_OBSERVER &&
+                  kObserverAboveTerrain == TOPO_OBSERVER_ABOVE_TERRAIN, "visibility classes");
 static_assert(kTileSphereDoubles == kLosSphereDoubles, "the cull prefilter and the rays read the same spheres: one gather, one layout");
 
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
@@ -492,6 +496,78 @@ int TerrainRenderer::profile_read(uint32_t n, const topo_ray* segs, uint32_t m, 
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
     if (samples) TOPO_HIP_TRY(hipMemcpy(samples, query_.d_profile_samples.p, row * n, hipMemcpyDeviceToHost));
     TOPO_HIP_TRY(hipMemcpy(summary, query_.d_surface_out.p, sum_bytes, hipMemcpyDeviceToHost));
+    return query_fold_check();
+}
+
+// ---- visibility ----------------------------------------------------------------------------------------------------------------
+
+// What every visibility call does first: its checks, the tables, and the observers -- host memory -- resolved into the context's
+// table by k_visibility_observers on stream_ (behind the kernels of an earlier call that still read it).
+int TerrainRenderer::visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m) {
+    if (!observers) return fail(TOPO_ERR_INVALID, "null argument");
+    if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
+    if (!(std::isfinite(target_height_m) && target_height_m >= 0.0 && target_height_m <= kVisMaxTargetHeight))
+        return fail(TOPO_ERR_INVALID, "target_height_m must be finite and lie in 0 .. 1e5");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    if (int rc = ensure(stream_, query_.d_vis_observers, kVisMaxObservers * sizeof(VisObserver))) return rc;
+    if (int rc = ensure(stream_, query_.d_vis_eyes, kVisMaxObservers * sizeof(VisEye))) return rc;
+    TOPO_HIP_TRY(hipMemcpyAsync(query_.d_vis_observers.p, observers, (size_t)n_observers * sizeof(VisObserver), hipMemcpyHostToDevice, stream_));
+    launch_visibility_observers(ray_params(), query_.d_vis_observers.as<const VisObserver>(), query_.d_vis_eyes.as<VisEye>(), n_observers, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Device variants: queued on stream_, in order.
+int TerrainRenderer::visibility_grid_device(uint32_t n_observers, const topo_observer* observers, double lon0, double lat0, double dlon, double dlat, uint32_t nx,
+                                            uint32_t ny, double target_height_m, uint8_t* out_dev, size_t layer_stride_bytes, size_t pitch_bytes) {
+    if (n_observers == 0) return TOPO_OK;
+    if (!out_dev || !observers) return fail(TOPO_ERR_INVALID, "null argument");
+    if (nx == 0 || ny == 0) return fail(TOPO_ERR_INVALID, "an empty grid");
+    if (!std::isfinite(lon0) || !std::isfinite(lat0) || !std::isfinite(dlon) || !std::isfinite(dlat)) return fail(TOPO_ERR_INVALID, "grid parameters must be finite");
+    if (pitch_bytes < nx) return fail(TOPO_ERR_INVALID, "pitch smaller than a row");
+    if (layer_stride_bytes / ny < pitch_bytes || layer_stride_bytes < (size_t)ny * pitch_bytes) return fail(TOPO_ERR_INVALID, "layer stride smaller than a layer");
+    if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
+    if ((((uint64_t)nx + 63) / 64) * ny * n_observers > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "grid too large");
+    if (int rc = visibility_begin(n_observers, observers, target_height_m)) return rc;
+    launch_visibility_grid(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, lon0, lat0, dlon, dlat, nx, ny, target_height_m, out_dev, layer_stride_bytes,
+                           pitch_bytes, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+int TerrainRenderer::visibility_device(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_dev, double target_height_m,
+                                       uint8_t* out_dev, size_t list_stride_bytes) {
+    if (n == 0 || n_observers == 0) return TOPO_OK;
+    if (!lonlat_dev || !out_dev || !observers) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)lonlat_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "lonlat_dev must be 16-byte aligned");
+    if (list_stride_bytes < n) return fail(TOPO_ERR_INVALID, "list stride smaller than the list");
+    if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
+    if ((((uint64_t)n + 63) / 64) * n_observers > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "list too large");
+    if (int rc = visibility_begin(n_observers, observers, target_height_m)) return rc;
+    launch_visibility_list(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, lonlat_dev, n, target_height_m, out_dev, list_stride_bytes, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Host read: observer o's classes at out + o * n.  The caller's memory is pageable, so nothing is staged (as topo_profile_read):
+// the stream is drained, the list goes up and the classes come down with blocking copies.
+int TerrainRenderer::visibility_read(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out) {
+    if (n == 0 || n_observers == 0) return TOPO_OK;
+    if (!lonlat_deg || !out || !observers) return fail(TOPO_ERR_INVALID, "null argument");
+    if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
+    if ((((uint64_t)n + 63) / 64) * n_observers > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "list too large");
+    if (int rc = visibility_begin(n_observers, observers, target_height_m)) return rc;
+    const size_t in_bytes = (size_t)n * 2 * sizeof(double), out_bytes = (size_t)n * n_observers;
+    if (int rc = ensure(stream_, query_.d_surface_in, in_bytes)) return rc;
+    if (int rc = ensure(stream_, query_.d_vis_out, out_bytes)) return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    TOPO_HIP_TRY(hipMemcpy(query_.d_surface_in.p, lonlat_deg, in_bytes, hipMemcpyHostToDevice));
+    launch_visibility_list(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, query_.d_surface_in.as<const double>(), n, target_height_m,
+                           query_.d_vis_out.as<uint8_t>(), n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    TOPO_HIP_TRY(hipMemcpy(out, query_.d_vis_out.p, out_bytes, hipMemcpyDeviceToHost));
     return query_fold_check();
 }
 

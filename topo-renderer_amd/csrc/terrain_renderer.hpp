@@ -177,6 +177,13 @@ class TerrainRenderer {
     int profile_device(uint32_t n, const topo_ray* segs_dev, uint32_t m, float* samples_dev, size_t segment_stride_bytes, topo_profile_summary* summary_dev);
     int profile_read(uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary);
 
+    // visibility: what observers see of the drawn terrain -- maps and lists (topo_visibility_*): no submission needed
+    int visibility_grid_device(uint32_t n_observers, const topo_observer* observers, double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny,
+                               double target_height_m, uint8_t* out_dev, size_t layer_stride_bytes, size_t pitch_bytes);
+    int visibility_device(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_dev, double target_height_m, uint8_t* out_dev,
+                          size_t list_stride_bytes);
+    int visibility_read(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out);
+
     // unwrap: finished views that share an eye as one azimuth / elevation image (topo_unwrap_device)
     int unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h, const OutputParams& src,
                       const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch);
@@ -356,11 +363,13 @@ class TerrainRenderer {
     int prepare_tables(TableLevel level, hipStream_t s);      // what a query kernel on s reads, up to `level`: once per public query
     // The queries' own buffers: the bounds record of every query kernel (TOPO_BOUNDS_CHECK build, folded into topo_frame_status), the
     // host reads' device buffers (horizon rows; ground queries, records; rays in, records out, their pinned staging; surface points in,
-    // records or profile summaries out, their pinned staging, a profile read's samples), and the device
+    // records or profile summaries out, their pinned staging, a profile read's samples; the visibility calls' observers as given and
+    // as resolved, a visibility read's classes), and the device
     // copy of k_unwrap's f64 tables (topo_unwrap.h), kept for what they were built from -- the call's parameters, the views'
     // direction blocks and the eye (unwrap_key) -- with their host copy, the source of the upload
     struct QueryBuffers {
-        DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_surface_in, d_surface_out, d_profile_samples, d_unwrap_tab;
+        DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_surface_in, d_surface_out, d_profile_samples, d_vis_observers, d_vis_eyes, d_vis_out,
+            d_unwrap_tab;
         PinnedBuffer h_ray_stage, h_surface_stage;
         std::vector<double> unwrap_tab;
         std::vector<uint8_t> unwrap_key;
@@ -377,6 +386,7 @@ class TerrainRenderer {
     int ground_prepare(const LatestSubmission& q);      // geometry tables + the submission's views on the device
     GroundParams ground_params(const LatestSubmission& q, uint32_t first_view, uint32_t n_views) const;
     RayParams ray_params() const;
+    int visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m);      // checks, tables, the observers resolved on stream_
 
     std::string err_;
 };

@@ -10,6 +10,7 @@
 #include "../../include/topo_hip_test.h"      // the test hooks are defined here too (their own header: not part of the boundary)
 #include "geotiff.hpp"
 #include "terrain_renderer.hpp"
+#include "topo_surface.h"
 
 struct topo_ctx {
     topo::TerrainRenderer* r = nullptr;
@@ -447,6 +448,31 @@ int topo_profile_device(topo_ctx* ctx, uint32_t n, const topo_ray* segs_dev, uin
 int topo_profile_read(topo_ctx* ctx, uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary) {
     TOPO_GUARD(ctx);
     TOPO_CALL(ctx->r->profile_read(n, segs, m, samples, summary));
+}
+
+int topo_visibility_grid_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double lon0_deg, double lat0_deg, double dlon_deg, double dlat_deg,
+                                uint32_t nx, uint32_t ny, double target_height_m, uint8_t* out_dev, size_t layer_stride_bytes, size_t pitch_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->visibility_grid_device(n_observers, observers, lon0_deg, lat0_deg, dlon_deg, dlat_deg, nx, ny, target_height_m, out_dev, layer_stride_bytes, pitch_bytes));
+}
+
+int topo_visibility_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_dev, double target_height_m,
+                           uint8_t* out_dev, size_t list_stride_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->visibility_device(n_observers, observers, n, lonlat_dev, target_height_m, out_dev, list_stride_bytes));
+}
+
+int topo_visibility_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->visibility_read(n_observers, observers, n, lonlat_deg, target_height_m, out));
+}
+
+void topo_ecef_from_lonlat(double lon_deg, double lat_deg, double height_m, double out[3]) {
+    if (!out) return;
+    double u[3];
+    topo::surface_direction(lon_deg, lat_deg, u);
+    const double r = topo::kGroundR0 + height_m;
+    for (int k = 0; k < 3; ++k) out[k] = r * u[k];
 }
 
 int topo_unwrap_device(topo_ctx* ctx, const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h,

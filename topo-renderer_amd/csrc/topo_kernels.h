@@ -265,6 +265,19 @@ void launch_surface_grid(const RayParams& p, double lon0, double lat0, double dl
 // m samples (terrain, line) of each of n segments at samples + i * stride bytes (samples null: none), and the segments' summaries
 void launch_profile(const RayParams& p, const LosRay* segs, uint32_t n, uint32_t m, float* samples, size_t stride, ProfileSummary* summary, hipStream_t s);
 
+// visibility (topo_visibility_*): what observers see of the drawn terrain (topo_visibility.h); needs no submission.  Reads what the
+// rays read (RayParams); writes only the observer table and its outputs.
+struct VisObserver;      // = topo_observer (topo_visibility.h)
+struct VisEye;           // a resolved observer: an entry of the context's table
+void launch_visibility_observers(const RayParams& p, const VisObserver* obs, VisEye* eyes, uint32_t n, hipStream_t s);      // n <= 64
+// one byte (kVis*) per (observer o, row r, column c) at out + o * layer_stride + r * pitch + c for the targets lon0 + c dlon,
+// lat0 + r dlat at target_height; ceil(nx / 64) * ny * n_observers < 2^32
+void launch_visibility_grid(const RayParams& p, const VisEye* eyes, uint32_t n_observers, double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny,
+                            double target_height, uint8_t* out, size_t layer_stride, size_t pitch, hipStream_t s);
+// the same for n (lon, lat) pairs: out[o * list_stride + i]
+void launch_visibility_list(const RayParams& p, const VisEye* eyes, uint32_t n_observers, const double* lonlat, uint32_t n, double target_height, uint8_t* out,
+                            size_t list_stride, hipStream_t s);
+
 // unwrap (topo_unwrap_*): n_views views of src_w x src_h that share an eye, resampled into one out_w x out_h azimuth / elevation
 // image (topo_unwrap.h).  Reads the tables and the source images; writes only the outputs given (each nullable; rgba_out needs
 // rgba_src, depth_out needs depth_src).
