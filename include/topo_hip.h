@@ -537,6 +537,47 @@ int topo_visibility_read(topo_ctx* ctx, uint32_t n_observers, const topo_observe
  * topo_ray, or the O and T above. */
 void topo_ecef_from_lonlat(double lon_deg, double lat_deg, double height_m, double out[3]);
 
+/* ---- skyline: the terrain horizon by azimuth from any point ----------------------------------------------------------------------
+ * "How high does the terrain stand above the horizontal in each direction from here, and which ridge forms that line?" -- solar
+ * access, radio horizon, ridge labels, the vertical extent of a panorama -- without a rendered frame, its rows or its field of view.
+ * Observer.  A topo_observer, resolved exactly as for the visibility queries: O, rho = |O|.  The frame at O is that of
+ * topo_pixel_angles and topo_unwrap_device: up = O / rho, east = z x up normalised, north = up x east.  An unusable observer, and one
+ * whose east does not come out finite and non-zero (on the polar axis), is TOPO_SKY_NO_OBSERVER for all its azimuths.
+ * Azimuth k of n_az is a_k = az0_deg + k * daz_deg (one rounded product, one rounded sum), clockwise from north;
+ * h = cos a north + sin a east, m = h x up (to the observer's right).  daz may be negative or zero.
+ * Crossing.  The mesh is that of the rays, with their rule of existence: a triangle exists iff its three vertex heights are finite.
+ * For each edge of each existing triangle -- edge e joins vertices e and (e + 1) % 3 in index-buffer order -- with the endpoints in
+ * canonical order (the lower vertex index y * w + x first) and translated by O: da = m . a, db = m . b; the edge crosses the plane iff
+ * (da < 0) != (db < 0); X = a + (da / (da - db)) (b - a), s = h . X, z = up . X; the crossing counts iff min_range_m <= s <= max_range_m.
+ * Winner.  The largest z / s; then the smaller s, the tile that comes first in draw order, the lower triangle index, the lower edge.
+ * The answer is a function of the observer, the azimuth and the tile set.  Along a straight segment the elevation angle is monotone, so
+ * the crossings carry the highest point of every triangle's cut: elevation_deg IS the terrain's horizon within the range limits.
+ * No crossing: TOPO_SKY_NONE.  Both TOPO_SKY_NONE and TOPO_SKY_NO_OBSERVER report a quiet NaN elevation and 0 in every other field.
+ * The calls read the resident tiles only and need no submission; they run on the context's stream (topo_set_stream) behind whatever
+ * was queued there, and write nothing but their outputs.  observers is HOST memory, read before the call returns; n_observers <= 64;
+ * zero observers or n_az = 0 is a no-op.  TOPO_ERR_INVALID for null or misaligned pointers, more than 64 observers, strides too small,
+ * a non-finite az0, daz or range, anything but 0 < min_range_m <= max_range_m <= 1e6, no output at all and n_az * n_observers >= 2^32. */
+typedef struct topo_skyline_sample {     /* 64 bytes; written as four 16-byte stores */
+    double elevation_deg, range_m;       /* atan2(z, s) in degrees; |X|.  s = range cos(elevation), z = range sin(elevation) */
+    double lon_deg, lat_deg;             /* of the crossing point O + X, as topo_ray_hit defines them */
+    float height_m; int32_t kind;        /* |O + X| - R0, the f64 value rounded once; TOPO_SKY_* */
+    int32_t tile_lat_deg, tile_lon_deg;  /* tile of the winning edge's triangle (named as in topo_ray_hit) */
+    uint32_t cell_x, cell_y;             /* its cell: viewshed / horizon / ground / ray numbering */
+    uint32_t tri, edge;                  /* tri = triangle & 1; edge 0, 1, 2 */
+} topo_skyline_sample;
+#define TOPO_SKY_NONE 0
+#define TOPO_SKY_TERRAIN 1
+#define TOPO_SKY_NO_OBSERVER 4           /* = TOPO_VIS_NO_OBSERVER */
+/* Device memory, each output nullable, at least one given: observer o's n_az f32 elevations -- (float) of the record's elevation_deg,
+ * bit for bit -- at elevation_dev + o * observer_stride_bytes (pointer and stride multiples of 4, stride >= 4 * n_az), its n_az records
+ * at samples_dev + o * samples_stride_bytes (multiples of 16, stride >= 64 * n_az); the bytes between n_az entries and a stride are
+ * left alone.  Asynchronous. */
+int topo_skyline_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,
+                        double max_range_m, float* elevation_dev, size_t observer_stride_bytes, topo_skyline_sample* samples_dev, size_t samples_stride_bytes);
+/* Host memory, each output nullable, at least one given: elevation[o * n_az + k], samples[o * n_az + k]; waits. */
+int topo_skyline_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,
+                      double max_range_m, float* elevation, topo_skyline_sample* samples);
+
 /* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
  * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
  * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --

@@ -60,6 +60,10 @@ VIS_NONE, VIS_VISIBLE, VIS_AWAY, VIS_HIDDEN, VIS_NO_OBSERVER = 0, 1, 2, 3, 4
 OBSERVER_ABOVE_TERRAIN = 1
 # topo_observer, 32 bytes
 OBSERVER_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f8"), ("flags", "<u4"), ("_reserved", "<u4")])
+SKY_NONE, SKY_TERRAIN, SKY_NO_OBSERVER = 0, 1, 4
+# topo_skyline_sample, 64 bytes
+SKYLINE_DTYPE = np.dtype([("elevation_deg", "<f8"), ("range_m", "<f8"), ("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f4"), ("kind", "<i4"),
+                          ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("edge", "<u4")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
 # topo_unwrap_params, 48 bytes
@@ -196,6 +200,8 @@ def lib():
             "topo_visibility_grid_device": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, C.c_double, C.c_double, u32, u32, C.c_double, vp, sz, sz]),
             "topo_visibility_device": (C.c_int, [vp, u32, vp, u32, vp, C.c_double, vp, sz]),
             "topo_visibility_read": (C.c_int, [vp, u32, vp, u32, vp, C.c_double, vp]),
+            "topo_skyline_device": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, u32, C.c_double, C.c_double, vp, sz, vp, sz]),
+            "topo_skyline_read": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, u32, C.c_double, C.c_double, vp, vp]),
             "topo_ecef_from_lonlat": (None, [C.c_double, C.c_double, C.c_double, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
@@ -897,6 +903,29 @@ class TerrainRenderer:
         self._check(lib().topo_visibility_read(self._h, len(o), _p(o) if len(o) else None, len(p), _p(p) if len(p) else None, target_height_m,
                                                _p(out) if out.size else None))
         return out
+
+    # skyline: the terrain horizon by azimuth from observers (include/topo_hip.h); no submission needed
+    def skyline_device(self, obs, az0_deg: float, daz_deg: float, n_az: int, elevation_ptr: int = 0, samples_ptr: int = 0, min_range_m: float = 1.0,
+                       max_range_m: float = 1.0e6, observer_stride_bytes: int = None, samples_stride_bytes: int = None):
+        """topo_skyline_device: for azimuth az0 + k * daz (degrees, clockwise from north) of observer o, the f32 elevation at
+        elevation_ptr + o * observer_stride_bytes + 4 * k and / or the SKYLINE_DTYPE record at samples_ptr + o * samples_stride_bytes +
+        64 * k (device memory, 0: not wanted; defaults: densely packed); obs: OBSERVER_DTYPE records (see observers()); queued on the
+        context's stream."""
+        o = np.ascontiguousarray(obs, dtype=OBSERVER_DTYPE).reshape(-1)
+        self._check(lib().topo_skyline_device(self._h, len(o), _p(o) if len(o) else None, az0_deg, daz_deg, n_az, min_range_m, max_range_m,
+                                              C.c_void_p(elevation_ptr) if elevation_ptr else None, 4 * n_az if observer_stride_bytes is None else observer_stride_bytes,
+                                              C.c_void_p(samples_ptr) if samples_ptr else None, 64 * n_az if samples_stride_bytes is None else samples_stride_bytes))
+
+    def skyline(self, obs, az0_deg: float, daz_deg: float, n_az: int, min_range_m: float = 1.0, max_range_m: float = 1.0e6, elevation: bool = True,
+                samples: bool = True):
+        """topo_skyline_read: OBSERVER_DTYPE records -> ((observers, n_az) f32 elevations in degrees, NaN where there is no terrain
+        in range or no observer; (observers, n_az) SKYLINE_DTYPE records), None for an output not wanted; waits."""
+        o = np.ascontiguousarray(obs, dtype=OBSERVER_DTYPE).reshape(-1)
+        el = np.full((len(o), n_az), np.nan, np.float32) if elevation else None
+        rec = np.zeros((len(o), n_az), SKYLINE_DTYPE) if samples else None
+        self._check(lib().topo_skyline_read(self._h, len(o), _p(o) if len(o) else None, az0_deg, daz_deg, n_az, min_range_m, max_range_m,
+                                            _p(el) if el is not None and el.size else None, _p(rec) if rec is not None and rec.size else None))
+        return el, rec
 
     # unwrap: finished views that share an eye as one azimuth / elevation image (include/topo_hip.h)
     def unwrap_device(self, params, uniforms_list, src_w: int, src_h: int, rgba_src_ptr: int = 0, rgba_view_stride: int = None, rgba_pitch: int = None,

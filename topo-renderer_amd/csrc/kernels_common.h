@@ -102,6 +102,13 @@ __device__ __forceinline__ float wave_lane(float v, int src_lane) { return __int
 __device__ __forceinline__ double shfl_f64(double v, int src) {
     return __hiloint2double(__shfl(__double2hiint(v), src), __shfl(__double2loint(v), src));
 }
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
+    return __hiloint2double(__shfl_xor(__double2hiint(v), mask), __shfl_xor(__double2loint(v), mask));
+}
+// lane `src`'s value for a wave-uniform src: scalar registers
+__device__ __forceinline__ double lane_f64(double v, int src) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
+}
 __device__ __forceinline__ uint32_t pop_bit(uint64_t& m) {      // wave-uniform mask: scalar instructions
     const uint32_t j = (uint32_t)__builtin_ctzll(m);
     m &= m - 1ull;

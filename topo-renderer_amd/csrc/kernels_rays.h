@@ -58,10 +58,6 @@ __global__ __launch_bounds__(256) void k_raycast_lane(RayParams P, const LosRay*
 // survivors are ballotted and taken one by one, a survivor's cells are dealt out to the lanes, every lane keeps its own best hit,
 // and t_max shrinks to the wave's minimum after each block; at the end the wave's best under (t, rank, triangle) is found with six
 // exchange steps.  The answer is los_cast's, byte for byte: the same rejections, the same triangle test, the same order.
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
-    return __hiloint2double(__shfl_xor(__double2hiint(v), mask), __shfl_xor(__double2loint(v), mask));
-}
-
 __global__ __launch_bounds__(256) void k_raycast(RayParams P, const LosRay* __restrict__ rays, RayHit* __restrict__ out, uint32_t n) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t i = wave_first(blockIdx.x * 4u + (threadIdx.x >> 6));

@@ -24,11 +24,6 @@
 namespace topo {
 namespace {
 
-// lane `src`'s value for a wave-uniform src: scalar registers
-__device__ __forceinline__ double lane_f64(double v, int src) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
-
 // One lane per observer (at most kVisMaxObservers: one wave).
 __global__ __launch_bounds__(64) void k_visibility_observers(RayParams P, const VisObserver* __restrict__ obs, VisEye* __restrict__ eyes, uint32_t n) {
     const uint32_t i = threadIdx.x;

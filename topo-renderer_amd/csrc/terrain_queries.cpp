@@ -1,7 +1,8 @@
-// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, visibility, unwrap), the tile-set
+// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, visibility, skyline, unwrap), the tile-set
 // tables they read and their handle on the latest submission.  The frame path is terrain_renderer.cpp (see terrain_renderer.hpp).
 #include "terrain_renderer.hpp"
 #include "topo_surface.h"
+#include "topo_skyline.h"
 #include "topo_visibility.h"
 
 #include <cmath>
@@ -20,6 +21,8 @@ static_assert(kSurfaceTerrain == TOPO_SURFACE_TERRAIN && kSurfaceNone == TOPO_SU
 static_assert(sizeof(VisObserver) == sizeof(topo_observer) && sizeof(topo_observer) == 32, "observer layout");
 static_assert(kVisNone == TOPO_VIS_NONE && kVisVisible == TOPO_VIS_VISIBLE && kVisAway == TOPO_VIS_AWAY && kVisHidden == TOPO_VIS_HIDDEN && kVisNoObserver == TOPO_VIS_NO_OBSERVER &&
                   kObserverAboveTerrain == TOPO_OBSERVER_ABOVE_TERRAIN, "visibility classes");
+static_assert(sizeof(SkySample) == sizeof(topo_skyline_sample) && sizeof(topo_skyline_sample) == 64, "skyline record layout");
+static_assert(kSkyNone == TOPO_SKY_NONE && kSkyTerrain == TOPO_SKY_TERRAIN && kSkyNoObserver == TOPO_SKY_NO_OBSERVER, "skyline kinds");
 static_assert(kTileSphereDoubles == kLosSphereDoubles, "the cull prefilter and the rays read the same spheres: one gather, one layout");
 
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
@@ -508,6 +511,11 @@ int TerrainRenderer::visibility_begin(uint32_t n_observers, const topo_observer*
     if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
     if (!(std::isfinite(target_height_m) && target_height_m >= 0.0 && target_height_m <= kVisMaxTargetHeight))
         return fail(TOPO_ERR_INVALID, "target_height_m must be finite and lie in 0 .. 1e5");
+    return resolve_observers(n_observers, observers);
+}
+
+// n_observers <= 64 observers (host memory) into the context's table, by k_visibility_observers: the visibility calls' and the skyline's.
+int TerrainRenderer::resolve_observers(uint32_t n_observers, const topo_observer* observers) {
     if (int rc = bind_device()) return rc;
     if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
     if (int rc = ensure(stream_, query_.d_vis_observers, kVisMaxObservers * sizeof(VisObserver))) return rc;
@@ -568,6 +576,63 @@ int TerrainRenderer::visibility_read(uint32_t n_observers, const topo_observer* 
     TOPO_HIP_TRY(hipGetLastError());
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
     TOPO_HIP_TRY(hipMemcpy(out, query_.d_vis_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return query_fold_check();
+}
+
+// ---- skyline --------------------------------------------------------------------------------------------------------------------
+
+// What both skyline calls refuse (their outputs apart).
+int TerrainRenderer::skyline_check(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,
+                                   double max_range_m) {
+    if (!observers) return fail(TOPO_ERR_INVALID, "null argument");
+    if (n_observers > kSkyMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
+    if (!std::isfinite(az0_deg) || !std::isfinite(daz_deg)) return fail(TOPO_ERR_INVALID, "az0_deg and daz_deg must be finite");
+    if (!(min_range_m > 0.0 && min_range_m <= max_range_m && max_range_m <= kSkyMaxRange))      // (false for a NaN)
+        return fail(TOPO_ERR_INVALID, "the ranges must satisfy 0 < min_range_m <= max_range_m <= 1e6");
+    if ((uint64_t)n_az * n_observers > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "n_az * n_observers must be below 2^32");
+    return TOPO_OK;
+}
+
+// Device variant: queued on stream_, in order.
+int TerrainRenderer::skyline_device(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,
+                                    double max_range_m, float* elevation_dev, size_t observer_stride_bytes, topo_skyline_sample* samples_dev, size_t samples_stride_bytes) {
+    if (n_observers == 0 || n_az == 0) return TOPO_OK;
+    if (int rc = skyline_check(n_observers, observers, az0_deg, daz_deg, n_az, min_range_m, max_range_m)) return rc;
+    if (!elevation_dev && !samples_dev) return fail(TOPO_ERR_INVALID, "at least one output must be given");
+    if (elevation_dev) {
+        if ((uintptr_t)elevation_dev % 4 != 0 || observer_stride_bytes % 4 != 0) return fail(TOPO_ERR_INVALID, "elevation_dev and the observer stride must be multiples of 4 bytes");
+        if (observer_stride_bytes / sizeof(float) < n_az) return fail(TOPO_ERR_INVALID, "observer stride smaller than an observer's elevations");
+    }
+    if (samples_dev) {
+        if ((uintptr_t)samples_dev % 16 != 0 || samples_stride_bytes % 16 != 0) return fail(TOPO_ERR_INVALID, "samples_dev and the samples stride must be multiples of 16 bytes");
+        if (samples_stride_bytes / sizeof(SkySample) < n_az) return fail(TOPO_ERR_INVALID, "samples stride smaller than an observer's records");
+    }
+    if (int rc = resolve_observers(n_observers, observers)) return rc;
+    launch_skyline(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, az0_deg, daz_deg, n_az, min_range_m, max_range_m,
+                   SkyOut{(uint8_t*)elevation_dev, observer_stride_bytes, (uint8_t*)samples_dev, samples_stride_bytes}, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Host read: observer o's entries at + o * n_az of either output.  The caller's memory is pageable, so nothing is staged (as
+// topo_visibility_read): the results come down with blocking copies once the stream has finished.
+int TerrainRenderer::skyline_read(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,
+                                  double max_range_m, float* elevation, topo_skyline_sample* samples) {
+    if (n_observers == 0 || n_az == 0) return TOPO_OK;
+    if (int rc = skyline_check(n_observers, observers, az0_deg, daz_deg, n_az, min_range_m, max_range_m)) return rc;
+    if (!elevation && !samples) return fail(TOPO_ERR_INVALID, "at least one output must be given");
+    if (int rc = resolve_observers(n_observers, observers)) return rc;
+    const size_t n = (size_t)n_observers * n_az, el_row = (size_t)n_az * sizeof(float), rec_row = (size_t)n_az * sizeof(SkySample);
+    if (elevation)
+        if (int rc = ensure(stream_, query_.d_sky_elevation, n * sizeof(float))) return rc;
+    if (samples)
+        if (int rc = ensure(stream_, query_.d_sky_samples, n * sizeof(SkySample))) return rc;
+    launch_skyline(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, az0_deg, daz_deg, n_az, min_range_m, max_range_m,
+                   SkyOut{elevation ? query_.d_sky_elevation.as<uint8_t>() : nullptr, el_row, samples ? query_.d_sky_samples.as<uint8_t>() : nullptr, rec_row}, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (elevation) TOPO_HIP_TRY(hipMemcpy(elevation, query_.d_sky_elevation.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (samples) TOPO_HIP_TRY(hipMemcpy(samples, query_.d_sky_samples.p, n * sizeof(SkySample), hipMemcpyDeviceToHost));
     return query_fold_check();
 }
 

@@ -184,6 +184,12 @@ class TerrainRenderer {
                           size_t list_stride_bytes);
     int visibility_read(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out);
 
+    // skyline: the terrain horizon by azimuth from observers (topo_skyline_*): no submission needed
+    int skyline_device(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m,
+                       float* elevation_dev, size_t observer_stride_bytes, topo_skyline_sample* samples_dev, size_t samples_stride_bytes);
+    int skyline_read(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m,
+                     float* elevation, topo_skyline_sample* samples);
+
     // unwrap: finished views that share an eye as one azimuth / elevation image (topo_unwrap_device)
     int unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h, const OutputParams& src,
                       const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch);
@@ -364,12 +370,12 @@ class TerrainRenderer {
     // The queries' own buffers: the bounds record of every query kernel (TOPO_BOUNDS_CHECK build, folded into topo_frame_status), the
     // host reads' device buffers (horizon rows; ground queries, records; rays in, records out, their pinned staging; surface points in,
     // records or profile summaries out, their pinned staging, a profile read's samples; the visibility calls' observers as given and
-    // as resolved, a visibility read's classes), and the device
+    // as resolved -- the skyline calls' too --, a visibility read's classes, a skyline read's elevations and records), and the device
     // copy of k_unwrap's f64 tables (topo_unwrap.h), kept for what they were built from -- the call's parameters, the views'
     // direction blocks and the eye (unwrap_key) -- with their host copy, the source of the upload
     struct QueryBuffers {
         DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_surface_in, d_surface_out, d_profile_samples, d_vis_observers, d_vis_eyes, d_vis_out,
-            d_unwrap_tab;
+            d_sky_elevation, d_sky_samples, d_unwrap_tab;
         PinnedBuffer h_ray_stage, h_surface_stage;
         std::vector<double> unwrap_tab;
         std::vector<uint8_t> unwrap_key;
@@ -386,7 +392,9 @@ class TerrainRenderer {
     int ground_prepare(const LatestSubmission& q);      // geometry tables + the submission's views on the device
     GroundParams ground_params(const LatestSubmission& q, uint32_t first_view, uint32_t n_views) const;
     RayParams ray_params() const;
-    int visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m);      // checks, tables, the observers resolved on stream_
+    int visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m);      // checks, then resolve_observers
+    int resolve_observers(uint32_t n_observers, const topo_observer* observers);      // the tables, and the observers resolved into d_vis_eyes on stream_
+    int skyline_check(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m);
 
     std::string err_;
 };

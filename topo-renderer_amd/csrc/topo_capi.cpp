@@ -467,6 +467,19 @@ int topo_visibility_read(topo_ctx* ctx, uint32_t n_observers, const topo_observe
     TOPO_CALL(ctx->r->visibility_read(n_observers, observers, n, lonlat_deg, target_height_m, out));
 }
 
+int topo_skyline_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,
+                        double max_range_m, float* elevation_dev, size_t observer_stride_bytes, topo_skyline_sample* samples_dev, size_t samples_stride_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->skyline_device(n_observers, observers, az0_deg, daz_deg, n_az, min_range_m, max_range_m, elevation_dev, observer_stride_bytes, samples_dev,
+                                     samples_stride_bytes));
+}
+
+int topo_skyline_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,
+                      double max_range_m, float* elevation, topo_skyline_sample* samples) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->skyline_read(n_observers, observers, az0_deg, daz_deg, n_az, min_range_m, max_range_m, elevation, samples));
+}
+
 void topo_ecef_from_lonlat(double lon_deg, double lat_deg, double height_m, double out[3]) {
     if (!out) return;
     double u[3];

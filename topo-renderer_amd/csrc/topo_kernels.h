@@ -278,6 +278,26 @@ void launch_visibility_grid(const RayParams& p, const VisEye* eyes, uint32_t n_o
 void launch_visibility_list(const RayParams& p, const VisEye* eyes, uint32_t n_observers, const double* lonlat, uint32_t n, double target_height, uint8_t* out,
                             size_t list_stride, hipStream_t s);
 
+// skyline (topo_skyline_*): per (observer, azimuth) the highest terrain crossing of the vertical half-plane from the observer
+// (topo_skyline.h); needs no submission.  Reads what the rays read (RayParams) and the table of resolved observers
+// (launch_visibility_observers); writes only its outputs.
+struct SkySample {         // = topo_skyline_sample (64 bytes)
+    double elevation_deg, range_m, lon_deg, lat_deg;
+    float height_m;
+    int32_t kind;
+    int32_t tile_lat, tile_lon;
+    uint32_t cell_x, cell_y, tri, edge;
+};
+struct SkyOut {            // each null or: observer o's n_az entries at + o * stride (bytes)
+    uint8_t* elevation;    // f32
+    size_t elevation_stride;
+    uint8_t* samples;      // SkySample
+    size_t samples_stride;
+};
+// azimuth k = az0 + k daz (degrees); n_observers * n_az < 2^32
+void launch_skyline(const RayParams& p, const VisEye* eyes, uint32_t n_observers, double az0, double daz, uint32_t n_az, double min_range, double max_range,
+                    const SkyOut& out, hipStream_t s);
+
 // unwrap (topo_unwrap_*): n_views views of src_w x src_h that share an eye, resampled into one out_w x out_h azimuth / elevation
 // image (topo_unwrap.h).  Reads the tables and the source images; writes only the outputs given (each nullable; rgba_out needs
 // rgba_src, depth_out needs depth_src).
