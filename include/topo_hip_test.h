@@ -39,6 +39,17 @@ int topo_debug_cull_pairs(topo_ctx* ctx, uint32_t out[2]);
  * every submission (by default only submissions of more than 2^25 pixels take it). */
 int topo_debug_cover_stats(topo_ctx* ctx, uint32_t out[3]);
 
+/* Test accessor: what the last submission's cull and occlusion test decided (waits for it).  Count, then fill: counts_out[0..2] =
+ * entries of the near work list, of the far candidates (the sub-lists one behind the other) and of the far survivors; [3], [4] = the
+ * frame's far_tested and far_survived counters.  near_out / survivors_out: 2 words per entry (view << 16 | tile rank, block | first
+ * cell row << 24 | rows << 28; rows 0 = the whole block); far_out: 5 words per entry (view << 16 | rank, block, x0 | x1 << 16,
+ * y0 | y1 << 16, the f32 bits of zmin).  Each list is filled up to its *_room entries; any pointer but counts_out may be null.
+ * The lists and the frame's counter set are left alone until the next submission (the counter sets alternate and a frame's clear
+ * zeroes the other one; the queries behind a frame only read).  TOPO_ERR_INVALID at a pipeline depth other than 1, and before the
+ * first submission (one that failed while it was queued, or was made before the pipeline depth last changed, does not count). */
+int topo_debug_read_cull_lists(topo_ctx* ctx, uint32_t* near_out, uint32_t near_room, uint32_t* far_out, uint32_t far_room, uint32_t* survivors_out,
+                               uint32_t survivors_room, uint32_t counts_out[5]);
+
 /* Test accessor: what k_viewshed did since accumulation was first enabled or last reset (waits for the frames in flight):
  * out[0] = terrain keys it read, out[1] = mask-word updates left after combining neighbouring lanes, out[2] = atomics issued
  * (updates that set at least one new bit).  All 0 before accumulation was ever enabled. */
@@ -49,8 +60,8 @@ int topo_read_normals(topo_ctx* ctx, int32_t lat_deg, int32_t lon_deg, uint8_t* 
 
 /* The load-time tables of a tile, read back (unit tests: the two load paths must leave the same tables).  minmax_out: 2 floats per
  * raster block (60 x 15 cells); trig_out: 2 (w + h) floats, the (sin, cos) pairs of the w vertex longitudes, then of the h vertex
- * latitudes; bounds_out: 17 doubles per raster block (4 sphere | 12 corner directions | 1 sagitta, each part contiguous over the
- * blocks).  Any pointer may be null.  n_blocks_out: the number of raster blocks. */
+ * latitudes; bounds_out: 18 doubles per raster block (4 sphere | 12 corner directions | 1 sagitta | 1 sideways bulge, each part
+ * contiguous over the blocks).  Any pointer may be null.  n_blocks_out: the number of raster blocks. */
 int topo_read_tile_tables(topo_ctx* ctx, int32_t lat_deg, int32_t lon_deg, float* minmax_out, float* trig_out, double* bounds_out, uint32_t* n_blocks_out);
 
 /* Synthetic COP90-shaped tile for tests and benches (integer-hash fBm): w*h floats. */

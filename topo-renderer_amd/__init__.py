@@ -66,6 +66,9 @@ SKYLINE_DTYPE = np.dtype([("elevation_deg", "<f8"), ("range_m", "<f8"), ("lon_de
                           ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("edge", "<u4")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
+# topo_debug_read_cull_lists (test hook): WorkItem and FarItem of csrc/topo_kernels.h
+WORK_ITEM_DTYPE = np.dtype([("view_rank", "<u4"), ("block", "<u4")])      # block | first cell row << 24 | rows << 28 (rows 0: the whole block)
+FAR_ITEM_DTYPE = np.dtype([("view_rank", "<u4"), ("block", "<u4"), ("x0", "<u2"), ("x1", "<u2"), ("y0", "<u2"), ("y1", "<u2"), ("zmin", "<f4")])
 # topo_unwrap_params, 48 bytes
 UNWRAP_PARAMS_DTYPE = np.dtype([("projection", "<u4"), ("filter", "<u4"), ("out_w", "<u4"), ("out_h", "<u4"), ("az0_deg", "<f8"), ("az_span_deg", "<f8"),
                                 ("el_top_deg", "<f8"), ("el_bottom_deg", "<f8")])
@@ -130,6 +133,7 @@ def lib():
             "topo_debug_set_tile_prefilter": (C.c_int, [vp, i32]),
             "topo_debug_cull_pairs": (C.c_int, [vp, vp]),
             "topo_debug_cover_stats": (C.c_int, [vp, vp]),
+            "topo_debug_read_cull_lists": (C.c_int, [vp, vp, u32, vp, u32, vp, u32, vp]),
             "topo_pin_host_buffer": (C.c_int, [vp, vp, sz]),
             "topo_unpin_host_buffer": (C.c_int, [vp, vp]),
             "topo_get_timings": (C.c_int, [vp, vp]),
@@ -686,6 +690,17 @@ class TerrainRenderer:
         self._check(lib().topo_debug_cover_stats(self._h, _p(out)))
         return {"candidates": int(out[0]), "won": int(out[1]), "lost": int(out[2])}
 
+    def debug_read_cull_lists(self) -> dict:
+        """What the last frame's cull and occlusion test decided (topo_debug_read_cull_lists, test hook; pipeline depth 1): the near
+        work items and the far survivors as WORK_ITEM_DTYPE records, the far candidates as FAR_ITEM_DTYPE records, and the frame's
+        far_tested / far_survived counters."""
+        n = np.zeros(5, np.uint32)
+        self._check(lib().topo_debug_read_cull_lists(self._h, None, 0, None, 0, None, 0, _p(n)))
+        near, far, surv = np.zeros(int(n[0]), WORK_ITEM_DTYPE), np.zeros(int(n[1]), FAR_ITEM_DTYPE), np.zeros(int(n[2]), WORK_ITEM_DTYPE)
+        self._check(lib().topo_debug_read_cull_lists(self._h, _p(near), near.size, _p(far), far.size, _p(surv), surv.size, _p(n)))
+        assert (int(n[0]), int(n[1]), int(n[2])) == (near.size, far.size, surv.size)
+        return {"near": near, "far": far, "survivors": surv, "far_tested": int(n[3]), "far_survived": int(n[4])}
+
     def timings(self) -> dict:
         out = np.zeros(TIMING_SLOTS, np.float32)
         self._check(lib().topo_get_timings(self._h, _p(out)))
@@ -719,7 +734,7 @@ class TerrainRenderer:
         w, h = self.tile_size
         n = C.c_uint32(0)
         self._check(lib().topo_read_tile_tables(self._h, lat_deg, lon_deg, None, None, None, C.byref(n)))
-        minmax, trig, bounds = np.empty((n.value, 2), np.float32), np.empty((w + h, 2), np.float32), np.empty(n.value * 17, np.float64)
+        minmax, trig, bounds = np.empty((n.value, 2), np.float32), np.empty((w + h, 2), np.float32), np.empty(n.value * 18, np.float64)
         self._check(lib().topo_read_tile_tables(self._h, lat_deg, lon_deg, _p(minmax), _p(trig), _p(bounds), C.byref(n)))
         return {"minmax": minmax, "trig": trig, "bounds": bounds}
 

@@ -74,10 +74,18 @@ __device__ __forceinline__ void clip_plane(const float* m, int pl, double out[5]
 //  * near/far split: blocks whose nearest possible view depth exceeds P.split_m become occlusion-test candidates
 //    (FarItem) instead of work items; for them the lane also projects the eight corners of the block's bounding
 //    slab -- the lat/lon rectangle of its vertices x [hmin - 1 m, hmax + 2 m + sagitta]: the flat-faced hull of those
-//    eight points contains every triangle of the block (k_block_minmax measures the sagitta; blocks where it exceeds
-//    1 m -- coarse tiles -- are never candidates) -- and records the pixel box (+-2 px; a sideways bulge of <= 1 m is
-//    < 0.001 px beyond the split distance) and a lower bound of the depths
-//    (z_ndc at the smallest corner w, minus 8/w: the f32 clip-space cancellation noise is ~1 clip unit).
+//    eight points holds the block's ideal surface radially (the load phase measures the sagitta of the patch over the flat top;
+//    blocks where it exceeds 1 m -- coarse tiles -- are never candidates) but not sideways: the equator-side edge follows a
+//    parallel, which bows out of the plane through the edge's ends by R (dlon^2 / 8) sin lat cos lat -- metres in the COP90 width
+//    bands, whatever the sagitta -- and the f32 vertex path adds its own noise.  So the lane records the pixel box of the eight
+//    corners with a margin of 2 px + (the block's bulge, a load-time table, + kFarNoiseM) in pixels at the slab's smallest w
+//    (2.3 to 2.4 px at the benchmark's sectors and split; whatever it takes at a longer focal length), and a lower bound of the depths
+//    (z_ndc at the smallest corner w, minus 8/w: the f32 clip-space cancellation noise is ~1 clip unit; bulge and noise move w by
+//    metres, z_ndc by 50 m / w^2 each, far inside the 8/w beyond the 1000 m a candidate needs).
+// kFarNoiseM: how far the real pipeline's vertex can lie from the ideal one, as a displacement.  The f32 longitude, latitude and
+// sin / cos put the position up to 1.8 m off (measured on the oracle's vertex path: tests/test_cull_cpu.py), the f32 product with
+// camera_proj adds four roundings of terms the size of |row| x 6.4e6, 1.5 m-equivalents in x, y and w: 3.3 m, taken as 8.
+constexpr double kFarNoiseM = 8.0;
 // Emit a block the raster must visit.  With the occlusion filter on, such blocks are few and heavy (large triangles),
 // so each is cut into strips of P.near_strip cell rows (the host picks 1, 2 or 4 by the size of the submission) to spread them over the resident waves:
 // block = id | first cell row << 24 | rows << 28 (rows 0 = the whole block).
@@ -208,9 +216,19 @@ __device__ __forceinline__ void cull_body(const FrameParams& P, uint32_t block, 
             emit_near(P, view, rank, blk);          // no usable bound: rasterise it with the near blocks
             continue;
         }
-        const int32_t ix0 = max((int32_t)floor(bxlo) - 2, 0), ix1 = min((int32_t)ceil(bxhi) + 2, P.W - 1);
-        const int32_t iy0 = max((int32_t)floor(bylo) - 2, 0), iy1 = min((int32_t)ceil(byhi) + 2, P.H - 1);
-        if (ix0 > ix1 || iy0 > iy1) continue;       // wholly outside the target even with the margin
+        // The margin.  A vertex of the real pipeline lies within `off` metres of the slab's hull: the block's sideways bulge (load
+        // phase) + kFarNoiseM.  A point p = q + d, q in the hull, |d| <= off, has x_clip and w within |x row| off and |w row| off of
+        // q's, so wherever p is on the target (|x / w| <= 1) its x / w lies within (|x row| + |w row|) off / w(q) of q's, and
+        // w(q) >= wmin; likewise y.  2 px on top, for the rounding of all this.
+        const double off = t.block_bounds[(size_t)blocks_per_tile * 17 + blk] + kFarNoiseM;
+        const double wrow = sqrt((double)m[3] * m[3] + (double)m[7] * m[7] + (double)m[11] * m[11]);
+        const double mx = 2.0 + 0.5 * (double)P.W * (sqrt((double)m[0] * m[0] + (double)m[4] * m[4] + (double)m[8] * m[8]) + wrow) * off / wmin;
+        const double my = 2.0 + 0.5 * (double)P.H * (sqrt((double)m[1] * m[1] + (double)m[5] * m[5] + (double)m[9] * m[9]) + wrow) * off / wmin;
+        // (clamped as doubles: at a long focal length the margin alone can exceed what an int32 holds)
+        const double fx0 = fmax(floor(bxlo - mx), 0.0), fx1 = fmin(ceil(bxhi + mx), (double)(P.W - 1));
+        const double fy0 = fmax(floor(bylo - my), 0.0), fy1 = fmin(ceil(byhi + my), (double)(P.H - 1));
+        if (!(fx0 <= fx1 && fy0 <= fy1)) continue;       // wholly outside the target even with the margin
+        const int32_t ix0 = (int32_t)fx0, ix1 = (int32_t)fx1, iy0 = (int32_t)fy0, iy1 = (int32_t)fy1;
         float zf = (float)zmin;
         if ((double)zf > zmin) zf = bits_f(f_bits(zf) - 1u);      // round down
         // 10^5 candidates appended through ONE counter cost this kernel 12 of its 43 us (atomics on one address are served one

@@ -1,6 +1,6 @@
 // kernels_load.h -- load phase: what add_terrain computes once per tile (compute_normals*.wgsl and the frame phase's tables).
 //
-//   k_block_tables                       block min/max, the f64 cull bounds and the per-tile sin/cos tables, reading the DEM
+//   k_block_tables                       block min/max, the f64 cull bounds (block_bounds_store: topo_cull.h) and the per-tile sin/cos tables, reading the DEM
 //   k_trig_tables, k_block_bounds<L>     the two halves of k_block_tables that do not read the DEM (the fused load path)
 //   k_normals_interior<ROWS>             interior normals through an LDS tile
 //   k_normals_rolling<R, WAVES, kTables> interior normals with the rows kept in registers; kTables: the block min/max as well
@@ -11,54 +11,13 @@
 #pragma once
 
 #include "kernels_common.h"
+#include "topo_cull.h"
 
 namespace topo {
 namespace {
 
-struct SinCos64 { double s, c; };
 __device__ __forceinline__ SinCos64 sincos64(double a) { SinCos64 r; r.s = sin(a); r.c = cos(a); return r; }
 
-// The view-independent half of the cull for one raster block, in f64: the bounding sphere of the block's patch, the unit
-// directions of its four corners and the sagitta of the patch over their flat hull.  lo / la: sin/cos of the block's first and
-// last longitude / latitude, loc / lac: of its centre.
-__device__ __forceinline__ void block_bounds_store(double* bounds, uint32_t blocks_per_tile, uint32_t blk, float bmn, float bmx, const SinCos64 lo[2],
-                                                   const SinCos64 la[2], const SinCos64& loc, const SinCos64& lac) {
-    const double hmin = (double)bmn, hmax = (double)bmx, hmid = 0.5 * (hmin + hmax);
-    double* bs = bounds + (size_t)blk * 4;                                              // sphere
-    double* bb = bounds + (size_t)blocks_per_tile * 4 + (size_t)blk * 12;               // corner directions
-    double u[4][3];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const SinCos64 &o = lo[k & 1], &a = la[k >> 1];
-        u[k][0] = a.c * o.c; u[k][1] = a.c * o.s; u[k][2] = a.s;
-        bb[3 * k] = u[k][0]; bb[3 * k + 1] = u[k][1]; bb[3 * k + 2] = u[k][2];
-    }
-    const double Rm = (double)kR0 + hmid;
-    const double c[3] = {Rm * lac.c * loc.c, Rm * lac.c * loc.s, Rm * lac.s};
-    double r2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double dx = Rm * u[k][0] - c[0], dy = Rm * u[k][1] - c[1], dz = Rm * u[k][2] - c[2];
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        r2 = d2 > r2 ? d2 : r2;
-    }
-    // every direction of the patch lies within the angular distance of the farthest corner from the centre direction,
-    // so the corners' chord distance bounds the sphere; + half the height range + margin
-    bs[0] = c[0]; bs[1] = c[1]; bs[2] = c[2];
-    bs[3] = sqrt(r2) + 0.5 * (hmax - hmin) + 8.0 + 64.0;
-    // How far the curved patch can stick out of the flat-faced hull of its eight slab corners (radially over the top
-    // face, sideways over the face along its equator-side parallel): at most the sagitta of the farthest corner's
-    // arc, R (1 - cos theta_max).  0.3 .. 0.7 m for a 60 x 15 cell block of a 1200-px tile, hundreds of metres for the
-    // blocks of a coarse tile: the occlusion filter pads its slab by this and only takes blocks where it is <= 1 m.
-    double dmin = 1.0;
-    const double uc[3] = {lac.c * loc.c, lac.c * loc.s, lac.s};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double d = u[k][0] * uc[0] + u[k][1] * uc[1] + u[k][2] * uc[2];
-        dmin = d < dmin ? d : dmin;
-    }
-    bounds[(size_t)blocks_per_tile * 16 + blk] = ((double)kR0 + (hmax > 0.0 ? hmax : 0.0) + 2.0) * (1.0 - dmin);
-}
 // The angles whose f64 sin/cos the bounds take: the latitude of vertex row vy / the longitude of vertex column vx (halves allowed).
 __device__ __forceinline__ double block_lat64(const TileDev& t, double vy) { return ((vy - (double)t.raster_y) * -(double)t.scale_y + (double)t.model_y) * 0.017453292519943295; }
 __device__ __forceinline__ double block_lon64(const TileDev& t, double vx) { return ((vx - (double)t.raster_x) * (double)t.scale_x + (double)t.model_x) * 0.017453292519943295; }

@@ -215,11 +215,11 @@ int TerrainRenderer::add_terrain(int32_t lat, int32_t lon, const float* heights,
     t.lon = lon;
     t.seq = next_seq_++;
     // ONE allocation per tile: heights, normals, then block min/max (2 floats per block), the sin/cos tables of the w columns
-    // and the h rows, and the f64 cull bounds (sphere 4 + corners 12 + sagitta 1 doubles per block); every part 256-byte aligned
+    // and the h rows, and the f64 cull bounds (sphere 4 + corners 12 + sagitta 1 + sideways bulge 1 doubles per block); every part 256-byte aligned
     const size_t tile_floats = (size_t)bxc * byc * 2 + 2 * ((size_t)w + h);
     auto up256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
     const size_t off_normals = up256(texels * 4), off_tables = off_normals + up256(texels * 4), off_bounds = off_tables + up256(tile_floats * sizeof(float));
-    if (int rc = ensure(stream_, t.pool, off_bounds + (size_t)bxc * byc * 17 * sizeof(double))) return rc;
+    if (int rc = ensure(stream_, t.pool, off_bounds + (size_t)bxc * byc * 18 * sizeof(double))) return rc;
     t.d_heights = t.pool.as<float>();
     t.d_normals = reinterpret_cast<uint32_t*>(t.pool.as<uint8_t>() + off_normals);
     t.d_minmax = reinterpret_cast<float*>(t.pool.as<uint8_t>() + off_tables);
@@ -449,6 +449,7 @@ int TerrainRenderer::set_pipeline_depth(int depth) {
         if (int rc = init_ctx(ctx_[i], depth > 1)) return rc;
     pipeline_depth_ = depth;
     next_ctx_ = last_ctx_ = 0;
+    for (FrameCtx& fc : ctx_) fc.lists_valid = false;      // (read_cull_lists: "the last submission" is one made at the current depth)
     return TOPO_OK;
 }
 
@@ -510,6 +511,7 @@ int TerrainRenderer::render_frame(FrameCtx& c, hipStream_t stream, uint32_t n, c
     if (n == 0) return fail(TOPO_ERR_INVALID, "null/empty argument");
     if (const char* e = submission_error(n, w, h)) return fail(TOPO_ERR_INVALID, e);
     latest_ctx_ = -1;      // (until this submission is queued whole: a failure half-way leaves nothing to query)
+    c.lists_valid = false;
     FrameParams p{};
     if (int rc = grow_frame_buffers(c, stream, n, w, h, p)) return rc;
     ViewPack pack{};
@@ -801,6 +803,9 @@ void TerrainRenderer::record_submission(FrameCtx& c, const FrameParams& p, const
         c.sub.views[i].pad_ = 0.0f;
     }
     c.sub.views_on_device = false;
+    c.lists_valid = true;
+    c.lists_near_cap = p.near_cap;
+    c.lists_far_sub_cap = p.far_sub_cap;
     HorizonParams& q = c.sub.query;
     q.vis = p.vis;
     q.dirty = p.dirty;
@@ -1193,6 +1198,43 @@ int TerrainRenderer::cover_stats(uint32_t out[3]) {
     return TOPO_OK;
 }
 
+// What the last frame's cull and occlusion test decided.  The lists and the counter set stay as the frame left them until the
+// context's next submission: a frame's clear zeroes the OTHER counter set (the next frame's), the status ring gets a copy of the
+// first kStatusWords words and never writes back, the queries behind a frame (horizon, ground, viewshed) only read the status word,
+// and d_work / d_far / d_work2 are written by k_cull and k_occlusion alone and reallocated by grow_frame_buffers alone, both inside
+// a submission.  With more than one frame in flight the "last" context is not well defined for a caller: depth 1 only.
+int TerrainRenderer::read_cull_lists(uint32_t* near_out, uint32_t near_room, uint32_t* far_out, uint32_t far_room, uint32_t* survivors_out,
+                                     uint32_t survivors_room, uint32_t counts_out[5]) {
+    static_assert(sizeof(WorkItem) == 8 && sizeof(FarItem) == 20, "the lists go out as 2 and 5 words per entry");
+    if (!counts_out) return fail(TOPO_ERR_INVALID, "null argument");
+    if (pipeline_depth_ != 1) return fail(TOPO_ERR_INVALID, "the cull lists can be read at pipeline depth 1 only");
+    FrameCtx& fc = ctx_[last_ctx_];
+    // (lists_valid: a submission that failed half-way, or one from before a change of the pipeline depth, has left nothing to read)
+    if (!fc.submitted || !fc.lists_valid || !fc.sub.query.counters) return fail(TOPO_ERR_INVALID, "no submission has been made");
+    if (int rc = bind_device()) return rc;
+    if (int rc = wait_all()) return rc;
+    std::vector<uint32_t> ctr(kCounterWords);
+    TOPO_HIP_TRY(hipMemcpy(ctr.data(), fc.sub.query.counters, kCounterWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t n_near = std::min(ctr[kCtrWork], fc.lists_near_cap), n_surv = std::min(ctr[kCtrFarSurvived], fc.lists_near_cap);
+    uint32_t n_far = 0;
+    for (uint32_t q = 0; q < kFarLists; ++q) n_far += std::min(ctr[far_list_counter(q)], fc.lists_far_sub_cap);
+    counts_out[0] = n_near; counts_out[1] = n_far; counts_out[2] = n_surv;
+    counts_out[3] = ctr[kCtrFarTested]; counts_out[4] = ctr[kCtrFarSurvived];
+    if (near_out && std::min(n_near, near_room))
+        TOPO_HIP_TRY(hipMemcpy(near_out, fc.d_work.p, (size_t)std::min(n_near, near_room) * sizeof(WorkItem), hipMemcpyDeviceToHost));
+    if (survivors_out && std::min(n_surv, survivors_room))
+        TOPO_HIP_TRY(hipMemcpy(survivors_out, fc.d_work2.p, (size_t)std::min(n_surv, survivors_room) * sizeof(WorkItem), hipMemcpyDeviceToHost));
+    if (far_out) {
+        uint32_t at = 0;      // the sub-lists one behind the other, in k_occlusion's order
+        for (uint32_t q = 0; q < kFarLists && at < far_room; ++q) {
+            const uint32_t n = std::min(std::min(ctr[far_list_counter(q)], fc.lists_far_sub_cap), far_room - at);
+            if (n) TOPO_HIP_TRY(hipMemcpy(far_out + (size_t)at * 5, fc.d_far.as<FarItem>() + (size_t)q * fc.lists_far_sub_cap, (size_t)n * sizeof(FarItem), hipMemcpyDeviceToHost));
+            at += n;
+        }
+    }
+    return TOPO_OK;
+}
+
 int TerrainRenderer::read_normals(int32_t lat, int32_t lon, uint8_t* out) {
     Tile* t = find(lat, lon);
     if (!t) return fail(TOPO_ERR_NOT_FOUND, "no such tile");
@@ -1212,7 +1254,7 @@ int TerrainRenderer::read_tile_tables(int32_t lat, int32_t lon, float* minmax_ou
     if (n_blocks_out) *n_blocks_out = (uint32_t)nb;
     if (minmax_out) TOPO_HIP_TRY(hipMemcpy(minmax_out, t->dev.block_minmax, nb * 2 * sizeof(float), hipMemcpyDeviceToHost));
     if (trig_out) TOPO_HIP_TRY(hipMemcpy(trig_out, t->dev.trig_lon, 2 * ((size_t)tile_w_ + tile_h_) * sizeof(float), hipMemcpyDeviceToHost));
-    if (bounds_out) TOPO_HIP_TRY(hipMemcpy(bounds_out, t->dev.block_bounds, nb * 17 * sizeof(double), hipMemcpyDeviceToHost));
+    if (bounds_out) TOPO_HIP_TRY(hipMemcpy(bounds_out, t->dev.block_bounds, nb * 18 * sizeof(double), hipMemcpyDeviceToHost));
     return TOPO_OK;
 }
 

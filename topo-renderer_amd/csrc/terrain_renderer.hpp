@@ -134,6 +134,8 @@ class TerrainRenderer {
     int get_timing_history(uint32_t n_frames, float* out_ms, uint32_t* n_out);
     int get_counters(uint32_t out[6]);
     int cover_stats(uint32_t out[3]);      // test hook: the last frame's covering items, regions claimed, claims lost
+    int read_cull_lists(uint32_t* near_out, uint32_t near_room, uint32_t* far_out, uint32_t far_room, uint32_t* survivors_out, uint32_t survivors_room,
+                        uint32_t counts_out[5]);      // test hook: the last frame's near items, far candidates, far survivors
     int frame_status(uint32_t out[4]);
     int set_occlusion_split(float metres);
     int set_timing_slots(uint32_t mask);
@@ -277,6 +279,8 @@ class TerrainRenderer {
         uint32_t cover_serial = 0;        // the serial the context's latest frame claimed regions with
         CoverParams cover{};              // this frame's; serial 0: the path is off
         uint32_t cover_big_cap = 0;       // ... and its big queue's capacity (the test hook reads the queue back)
+        bool lists_valid = false;         // the context's latest submission was queued whole, at the current pipeline depth
+        uint32_t lists_near_cap = 0, lists_far_sub_cap = 0;      // the latest frame's near_cap / far_sub_cap (read_cull_lists, test hook)
         DeviceBuffer d_pre_rgba, d_pre_depth;      // the pixelise branch: the render-target image k_post_pixelize samples, and a depth image when the caller wants none
         // the context's latest submission as the queries read it (its keys and marks are d_vis / d_dirty until the next one)
         struct Submission {

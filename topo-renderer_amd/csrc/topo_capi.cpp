@@ -154,6 +154,12 @@ int topo_debug_cover_stats(topo_ctx* ctx, uint32_t out[3]) {
     TOPO_CALL(ctx->r->cover_stats(out));
 }
 
+int topo_debug_read_cull_lists(topo_ctx* ctx, uint32_t* near_out, uint32_t near_room, uint32_t* far_out, uint32_t far_room, uint32_t* survivors_out,
+                               uint32_t survivors_room, uint32_t counts_out[5]) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->read_cull_lists(near_out, near_room, far_out, far_room, survivors_out, survivors_room, counts_out));
+}
+
 int topo_get_timings(topo_ctx* ctx, float out_ms[TOPO_TIMING_SLOTS]) {
     TOPO_GUARD(ctx);
     TOPO_CALL(ctx->r->get_timings(out_ms));
