@@ -578,6 +578,47 @@ int topo_skyline_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer
 int topo_skyline_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,
                       double max_range_m, float* elevation, topo_skyline_sample* samples);
 
+/* ---- sun exposure: a day of sun and shadow over points of the drawn terrain, as a map or over a list ---------------------------------
+ * "How many hours of sun does this slope get on 21 December?"  "When does the north face come out of the shade?" -- without a rendered
+ * frame: topo_sunlit_map_device covers one sun and the pixels of rendered views.  No new geometry: a point is found on the drawn terrain
+ * exactly as topo_surface_* finds it, and the shadow ray is tested exactly as that of topo_sunlit_map_device is.
+ * Suns.  Up to 64 per call, HOST memory, read before the call returns.  dir points TOWARDS the sun -- one ECEF direction for the whole
+ * call, the sun being at infinity, as sun_dir of topo_sunlit_map_device; topo_sun_direction makes one from an azimuth and an elevation --
+ * and is normalised in f64 as that call normalises sun_dir.  weight is finite and >= 0: minutes per sample, say, or minutes times
+ * direct-normal irradiance.
+ * Target.  A point (lon, lat), found as a visibility target with target_height_m == 0 is: an invalid point or one with no terrain under
+ * it is NONE; otherwise T = (R0 + t) u with t and the triangle from the surface rule, and N = (v1 - v0) x (v2 - v0) of that triangle,
+ * turned to the side of u.
+ * Class of (target, sun s), in this order.  (1) !(u . s > 0): TOPO_SUN_NIGHT -- the sun is on or below the point's own horizontal plane.
+ * The sphere is not geometry and a mosaic is finite: without this step a set sun would light every slope near the mosaic's edge.  The
+ * dip of the horizon is IGNORED: from a summit the sun is seen a degree or two below that plane, and is night here.  (2) !(N . s > 0):
+ * TOPO_SUN_AWAY.  (3) The ray from T along s against the triangles of the rays, a hit counting for 1e-3 m < t <= 1e6 m, the target's
+ * own triangle left out: any hit TOPO_SUN_SHADOW, none TOPO_SUN_LIT.
+ * Outputs per target, each nullable, at least one given.  lit: bit k is set iff sun k is LIT.  shadow: bit k is set iff sun k is SHADOW,
+ * that is, cast by other terrain; AWAY and NIGHT set neither bit.  exposure: the sum, in ascending k over the LIT suns, of
+ * weight_k * (N . s_k) / |N|, formed in f64 and rounded once to f32; 0 for terrain that is never lit, a quiet NaN for NONE, whose masks
+ * are both 0.  The answer is a function of the target, the sun and the tile set: a sun's bit does not depend on the other suns of the
+ * call or on its position among them.
+ * The calls read the resident tiles only and need no submission; they run on the context's stream (topo_set_stream) behind whatever
+ * was queued there, and write nothing but their outputs.  Zero suns (or n = 0) is a no-op.  TOPO_ERR_INVALID for a null suns, more than
+ * 64 suns, a zero or non-finite dir, a non-finite or negative weight, no output at all and misaligned pointers. */
+typedef struct topo_sun { double dir[3]; double weight; } topo_sun;      /* 32 bytes */
+#define TOPO_SUN_NIGHT 4         /* the sun is on or below the target's horizontal plane (after TOPO_SUN_NONE .. TOPO_SUN_SHADOW) */
+/* The dense form: the target at lon0 + c * dlon, lat0 + r * dlat (one rounded product, one rounded sum, as topo_visibility_grid_device)
+ * for c < nx, r < ny has its masks at lit_dev / shadow_dev + r * mask_pitch_bytes + 8 * c (pointers and pitch multiples of 8, the pitch
+ * >= 8 * nx) and its exposure at exposure_dev + r * exposure_pitch_bytes + 4 * c (multiples of 4, the pitch >= 4 * nx) -- what the list
+ * call gives for the same numbers.  Device memory; the bytes between nx and a pitch are left alone.  dlon and dlat may be negative or
+ * zero.  TOPO_ERR_INVALID also for a zero nx or ny, non-finite grid parameters, a pitch too small and ceil(nx / 64) * ny >= 2^32.
+ * Asynchronous. */
+int topo_sun_exposure_grid_device(topo_ctx* ctx, uint32_t n_suns, const topo_sun* suns, double lon0_deg, double lat0_deg, double dlon_deg, double dlat_deg, uint32_t nx,
+                                  uint32_t ny, uint64_t* lit_dev, uint64_t* shadow_dev, float* exposure_dev, size_t mask_pitch_bytes, size_t exposure_pitch_bytes);
+/* The list form: n (lon, lat) pairs in degrees at lonlat_dev (device memory, 16-byte aligned) -> lit_dev[i], shadow_dev[i] (8-byte
+ * aligned), exposure_dev[i] (4-byte aligned).  Asynchronous. */
+int topo_sun_exposure_device(topo_ctx* ctx, uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_dev, uint64_t* lit_dev, uint64_t* shadow_dev,
+                             float* exposure_dev);
+/* Host memory: n pairs in, lit[i], shadow[i], exposure[i]; waits. */
+int topo_sun_exposure_read(topo_ctx* ctx, uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_deg, uint64_t* lit, uint64_t* shadow, float* exposure);
+
 /* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
  * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
  * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --

@@ -64,6 +64,9 @@ SKY_NONE, SKY_TERRAIN, SKY_NO_OBSERVER = 0, 1, 4
 # topo_skyline_sample, 64 bytes
 SKYLINE_DTYPE = np.dtype([("elevation_deg", "<f8"), ("range_m", "<f8"), ("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f4"), ("kind", "<i4"),
                           ("tile_lat_deg", "<i4"), ("tile_lon_deg", "<i4"), ("cell_x", "<u4"), ("cell_y", "<u4"), ("tri", "<u4"), ("edge", "<u4")])
+SUN_NIGHT = 4
+# topo_sun, 32 bytes
+SUN_DTYPE = np.dtype([("dir", "<f8", 3), ("weight", "<f8")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
 # topo_debug_read_cull_lists (test hook): WorkItem and FarItem of csrc/topo_kernels.h
@@ -206,6 +209,9 @@ def lib():
             "topo_visibility_read": (C.c_int, [vp, u32, vp, u32, vp, C.c_double, vp]),
             "topo_skyline_device": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, u32, C.c_double, C.c_double, vp, sz, vp, sz]),
             "topo_skyline_read": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, u32, C.c_double, C.c_double, vp, vp]),
+            "topo_sun_exposure_grid_device": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, C.c_double, C.c_double, u32, u32, vp, vp, vp, sz, sz]),
+            "topo_sun_exposure_device": (C.c_int, [vp, u32, vp, u32, vp, vp, vp, vp]),
+            "topo_sun_exposure_read": (C.c_int, [vp, u32, vp, u32, vp, vp, vp, vp]),
             "topo_ecef_from_lonlat": (None, [C.c_double, C.c_double, C.c_double, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
@@ -364,6 +370,15 @@ def observers(lon_deg, lat_deg, height_m, above_terrain=True) -> np.ndarray:
                                        np.asarray(above_terrain, bool))
     out = np.zeros(len(lo), OBSERVER_DTYPE)
     out["lon_deg"], out["lat_deg"], out["height_m"], out["flags"] = lo, la, h, np.where(f, OBSERVER_ABOVE_TERRAIN, 0)
+    return out
+
+
+def suns(dirs, weights=1.0) -> np.ndarray:
+    """SUN_DTYPE records (topo_sun) from directions TOWARDS the sun (f64 ECEF, (3,) or (n, 3); they need not be unit, see
+    sun_direction) and weights (a scalar or (n,)): minutes per sample, say."""
+    d = np.atleast_2d(np.asarray(dirs, np.float64))
+    out = np.zeros(len(d), SUN_DTYPE)
+    out["dir"], out["weight"] = d, weights
     return out
 
 
@@ -941,6 +956,36 @@ class TerrainRenderer:
         self._check(lib().topo_skyline_read(self._h, len(o), _p(o) if len(o) else None, az0_deg, daz_deg, n_az, min_range_m, max_range_m,
                                             _p(el) if el is not None and el.size else None, _p(rec) if rec is not None and rec.size else None))
         return el, rec
+
+    # sun exposure: a day of sun and shadow over points of the drawn terrain (include/topo_hip.h); no submission needed
+    def sun_exposure_grid_device(self, suns, lon0: float, lat0: float, dlon: float, dlat: float, nx: int, ny: int, lit_ptr: int = 0, shadow_ptr: int = 0,
+                                 exposure_ptr: int = 0, mask_pitch_bytes: int = None, exposure_pitch_bytes: int = None):
+        """topo_sun_exposure_grid_device: for the target at lon0 + c * dlon, lat0 + r * dlat the uint64 masks (bit k: sun k LIT / in cast
+        SHADOW) at lit_ptr / shadow_ptr + r * mask_pitch_bytes + 8 * c and the f32 exposure at exposure_ptr + r * exposure_pitch_bytes +
+        4 * c (device memory, 0: not wanted; defaults: densely packed); suns: SUN_DTYPE records (see suns()); queued on the context's
+        stream."""
+        s = np.ascontiguousarray(suns, dtype=SUN_DTYPE).reshape(-1)
+        ptr = lambda v: C.c_void_p(v) if v else None
+        self._check(lib().topo_sun_exposure_grid_device(self._h, len(s), _p(s) if len(s) else None, lon0, lat0, dlon, dlat, nx, ny, ptr(lit_ptr), ptr(shadow_ptr),
+                                                        ptr(exposure_ptr), 8 * nx if mask_pitch_bytes is None else mask_pitch_bytes,
+                                                        4 * nx if exposure_pitch_bytes is None else exposure_pitch_bytes))
+
+    def sun_exposure_device(self, suns, lonlat_ptr: int, n: int, lit_ptr: int = 0, shadow_ptr: int = 0, exposure_ptr: int = 0):
+        """topo_sun_exposure_device: n (lon, lat) f64 pairs at lonlat_ptr (device memory, 16-byte aligned) -> the uint64 masks at
+        lit_ptr / shadow_ptr + 8 * i and the f32 exposure at exposure_ptr + 4 * i (0: not wanted); queued on the context's stream."""
+        s = np.ascontiguousarray(suns, dtype=SUN_DTYPE).reshape(-1)
+        ptr = lambda v: C.c_void_p(v) if v else None
+        self._check(lib().topo_sun_exposure_device(self._h, len(s), _p(s) if len(s) else None, n, ptr(lonlat_ptr), ptr(lit_ptr), ptr(shadow_ptr), ptr(exposure_ptr)))
+
+    def sun_exposure(self, suns, lonlat):
+        """topo_sun_exposure_read: SUN_DTYPE records and (n, 2) f64 (longitude, latitude) in degrees -> ((n,) uint64 lit masks, (n,) uint64
+        shadow masks, (n,) f32 exposures: NaN where there is no terrain); waits."""
+        s = np.ascontiguousarray(suns, dtype=SUN_DTYPE).reshape(-1)
+        p = np.ascontiguousarray(lonlat, dtype=np.float64).reshape(-1, 2)
+        lit, shadow, exposure = np.zeros(len(p), np.uint64), np.zeros(len(p), np.uint64), np.zeros(len(p), np.float32)
+        ptr = lambda a: _p(a) if a.size else None
+        self._check(lib().topo_sun_exposure_read(self._h, len(s), _p(s) if len(s) else None, len(p), ptr(p), ptr(lit), ptr(shadow), ptr(exposure)))
+        return lit, shadow, exposure
 
     # unwrap: finished views that share an eye as one azimuth / elevation image (include/topo_hip.h)
     def unwrap_device(self, params, uniforms_list, src_w: int, src_h: int, rgba_src_ptr: int = 0, rgba_view_stride: int = None, rgba_pitch: int = None,

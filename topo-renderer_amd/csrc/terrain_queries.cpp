@@ -1,8 +1,9 @@
-// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, visibility, skyline, unwrap), the tile-set
+// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, visibility, skyline, sun exposure, unwrap), the tile-set
 // tables they read and their handle on the latest submission.  The frame path is terrain_renderer.cpp (see terrain_renderer.hpp).
 #include "terrain_renderer.hpp"
 #include "topo_surface.h"
 #include "topo_skyline.h"
+#include "topo_sun.h"
 #include "topo_visibility.h"
 
 #include <cmath>
@@ -23,6 +24,8 @@ static_assert(kVisNone == TOPO_VIS_NONE && kVisVisible == TOPO_VIS_VISIBLE && kV
                   kObserverAboveTerrain == TOPO_OBSERVER_ABOVE_TERRAIN, "visibility classes");
 static_assert(sizeof(SkySample) == sizeof(topo_skyline_sample) && sizeof(topo_skyline_sample) == 64, "skyline record layout");
 static_assert(kSkyNone == TOPO_SKY_NONE && kSkyTerrain == TOPO_SKY_TERRAIN && kSkyNoObserver == TOPO_SKY_NO_OBSERVER, "skyline kinds");
+static_assert(sizeof(SunDir) == sizeof(topo_sun) && sizeof(topo_sun) == 32, "sun layout");
+static_assert(kSunNone == TOPO_SUN_NONE && kSunLit == TOPO_SUN_LIT && kSunAway == TOPO_SUN_AWAY && kSunShadow == TOPO_SUN_SHADOW && kSunNight == TOPO_SUN_NIGHT, "sun classes");
 static_assert(kTileSphereDoubles == kLosSphereDoubles, "the cull prefilter and the rays read the same spheres: one gather, one layout");
 
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
@@ -633,6 +636,100 @@ int TerrainRenderer::skyline_read(uint32_t n_observers, const topo_observer* obs
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
     if (elevation) TOPO_HIP_TRY(hipMemcpy(elevation, query_.d_sky_elevation.p, n * sizeof(float), hipMemcpyDeviceToHost));
     if (samples) TOPO_HIP_TRY(hipMemcpy(samples, query_.d_sky_samples.p, n * sizeof(SkySample), hipMemcpyDeviceToHost));
+    return query_fold_check();
+}
+
+// ---- sun exposure ---------------------------------------------------------------------------------------------------------------
+
+// What every sun exposure call does first: its checks of the suns, the tables, and the suns -- host memory -- normalised as
+// sunlit_map_device normalises its one and copied into the context's table on stream_ (behind the kernels of an earlier call that still
+// read it).  Null lonlat and outputs are the callers' to refuse.
+int TerrainRenderer::sun_begin(uint32_t n_suns, const topo_sun* suns) {
+    if (!suns) return fail(TOPO_ERR_INVALID, "null argument");
+    if (n_suns > kSunMaxSuns) return fail(TOPO_ERR_INVALID, "at most 64 suns");
+    SunDir unit[kSunMaxSuns];
+    for (uint32_t k = 0; k < n_suns; ++k) {
+        const double* const d = suns[k].dir;
+        const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        if (!(len > 0.0) || !std::isfinite(len)) return fail(TOPO_ERR_INVALID, "a sun's dir must be finite and non-zero");
+        if (!(std::isfinite(suns[k].weight) && suns[k].weight >= 0.0)) return fail(TOPO_ERR_INVALID, "a sun's weight must be finite and not negative");
+        unit[k] = SunDir{{d[0] / len, d[1] / len, d[2] / len}, suns[k].weight};
+    }
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    if (int rc = ensure(stream_, query_.d_suns, kSunMaxSuns * sizeof(SunDir))) return rc;
+    TOPO_HIP_TRY(hipMemcpyAsync(query_.d_suns.p, unit, (size_t)n_suns * sizeof(SunDir), hipMemcpyHostToDevice, stream_));      // (pageable: read before it returns)
+    return TOPO_OK;
+}
+
+// What is wrong with a sun exposure call's outputs (device or host: three nullable pointers), or null.
+static const char* sun_outputs_error(const uint64_t* lit, const uint64_t* shadow, const float* exposure) {
+    if (!lit && !shadow && !exposure) return "at least one output must be given";
+    if ((uintptr_t)lit % 8 != 0 || (uintptr_t)shadow % 8 != 0) return "the masks must be 8-byte aligned";
+    if ((uintptr_t)exposure % 4 != 0) return "the exposure must be 4-byte aligned";
+    return nullptr;
+}
+
+// Device variants: queued on stream_, in order.
+int TerrainRenderer::sun_exposure_grid_device(uint32_t n_suns, const topo_sun* suns, double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny,
+                                              uint64_t* lit_dev, uint64_t* shadow_dev, float* exposure_dev, size_t mask_pitch_bytes, size_t exposure_pitch_bytes) {
+    if (n_suns == 0) return TOPO_OK;
+    if (const char* why = sun_outputs_error(lit_dev, shadow_dev, exposure_dev)) return fail(TOPO_ERR_INVALID, why);
+    if (nx == 0 || ny == 0) return fail(TOPO_ERR_INVALID, "an empty grid");
+    if (!std::isfinite(lon0) || !std::isfinite(lat0) || !std::isfinite(dlon) || !std::isfinite(dlat)) return fail(TOPO_ERR_INVALID, "grid parameters must be finite");
+    if (lit_dev || shadow_dev) {
+        if (mask_pitch_bytes % 8 != 0) return fail(TOPO_ERR_INVALID, "the mask pitch must be a multiple of 8 bytes");
+        if (mask_pitch_bytes / sizeof(uint64_t) < nx) return fail(TOPO_ERR_INVALID, "mask pitch smaller than a row");
+    }
+    if (exposure_dev) {
+        if (exposure_pitch_bytes % 4 != 0) return fail(TOPO_ERR_INVALID, "the exposure pitch must be a multiple of 4 bytes");
+        if (exposure_pitch_bytes / sizeof(float) < nx) return fail(TOPO_ERR_INVALID, "exposure pitch smaller than a row");
+    }
+    if ((((uint64_t)nx + 63) / 64) * ny > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "grid too large");
+    if (int rc = sun_begin(n_suns, suns)) return rc;
+    launch_sun_exposure_grid(ray_params(), query_.d_suns.as<const SunDir>(), n_suns, lon0, lat0, dlon, dlat, nx, ny, lit_dev, shadow_dev, exposure_dev, mask_pitch_bytes,
+                             exposure_pitch_bytes, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+int TerrainRenderer::sun_exposure_device(uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_dev, uint64_t* lit_dev, uint64_t* shadow_dev,
+                                         float* exposure_dev) {
+    if (n == 0 || n_suns == 0) return TOPO_OK;
+    if (!lonlat_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)lonlat_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "lonlat_dev must be 16-byte aligned");
+    if (const char* why = sun_outputs_error(lit_dev, shadow_dev, exposure_dev)) return fail(TOPO_ERR_INVALID, why);
+    if (int rc = sun_begin(n_suns, suns)) return rc;
+    launch_sun_exposure_list(ray_params(), query_.d_suns.as<const SunDir>(), n_suns, lonlat_dev, n, lit_dev, shadow_dev, exposure_dev, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Host read.  The caller's memory is pageable, so nothing is staged (as topo_visibility_read): the stream is drained, the list goes up
+// and the outputs that were asked for come down with blocking copies.
+int TerrainRenderer::sun_exposure_read(uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_deg, uint64_t* lit, uint64_t* shadow, float* exposure) {
+    if (n == 0 || n_suns == 0) return TOPO_OK;
+    if (!lonlat_deg) return fail(TOPO_ERR_INVALID, "null argument");
+    if (const char* why = sun_outputs_error(lit, shadow, exposure)) return fail(TOPO_ERR_INVALID, why);
+    if (int rc = sun_begin(n_suns, suns)) return rc;
+    const size_t in_bytes = (size_t)n * 2 * sizeof(double), mask_bytes = (size_t)n * sizeof(uint64_t), exp_bytes = (size_t)n * sizeof(float);
+    if (int rc = ensure(stream_, query_.d_surface_in, in_bytes)) return rc;
+    if (lit)
+        if (int rc = ensure(stream_, query_.d_sun_lit, mask_bytes)) return rc;
+    if (shadow)
+        if (int rc = ensure(stream_, query_.d_sun_shadow, mask_bytes)) return rc;
+    if (exposure)
+        if (int rc = ensure(stream_, query_.d_sun_exposure, exp_bytes)) return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    TOPO_HIP_TRY(hipMemcpy(query_.d_surface_in.p, lonlat_deg, in_bytes, hipMemcpyHostToDevice));
+    launch_sun_exposure_list(ray_params(), query_.d_suns.as<const SunDir>(), n_suns, query_.d_surface_in.as<const double>(), n,
+                             lit ? query_.d_sun_lit.as<uint64_t>() : nullptr, shadow ? query_.d_sun_shadow.as<uint64_t>() : nullptr,
+                             exposure ? query_.d_sun_exposure.as<float>() : nullptr, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (lit) TOPO_HIP_TRY(hipMemcpy(lit, query_.d_sun_lit.p, mask_bytes, hipMemcpyDeviceToHost));
+    if (shadow) TOPO_HIP_TRY(hipMemcpy(shadow, query_.d_sun_shadow.p, mask_bytes, hipMemcpyDeviceToHost));
+    if (exposure) TOPO_HIP_TRY(hipMemcpy(exposure, query_.d_sun_exposure.p, exp_bytes, hipMemcpyDeviceToHost));
     return query_fold_check();
 }
 

@@ -192,6 +192,12 @@ class TerrainRenderer {
     int skyline_read(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m,
                      float* elevation, topo_skyline_sample* samples);
 
+    // sun exposure: a day of sun and shadow over points of the drawn terrain -- maps and lists (topo_sun_exposure_*): no submission needed
+    int sun_exposure_grid_device(uint32_t n_suns, const topo_sun* suns, double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny, uint64_t* lit_dev,
+                                 uint64_t* shadow_dev, float* exposure_dev, size_t mask_pitch_bytes, size_t exposure_pitch_bytes);
+    int sun_exposure_device(uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_dev, uint64_t* lit_dev, uint64_t* shadow_dev, float* exposure_dev);
+    int sun_exposure_read(uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_deg, uint64_t* lit, uint64_t* shadow, float* exposure);
+
     // unwrap: finished views that share an eye as one azimuth / elevation image (topo_unwrap_device)
     int unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h, const OutputParams& src,
                       const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch);
@@ -374,12 +380,12 @@ class TerrainRenderer {
     // The queries' own buffers: the bounds record of every query kernel (TOPO_BOUNDS_CHECK build, folded into topo_frame_status), the
     // host reads' device buffers (horizon rows; ground queries, records; rays in, records out, their pinned staging; surface points in,
     // records or profile summaries out, their pinned staging, a profile read's samples; the visibility calls' observers as given and
-    // as resolved -- the skyline calls' too --, a visibility read's classes, a skyline read's elevations and records), and the device
+    // as resolved -- the skyline calls' too --, a visibility read's classes, a skyline read's elevations and records, the sun exposure calls' suns and a sun exposure read's masks and exposures), and the device
     // copy of k_unwrap's f64 tables (topo_unwrap.h), kept for what they were built from -- the call's parameters, the views'
     // direction blocks and the eye (unwrap_key) -- with their host copy, the source of the upload
     struct QueryBuffers {
         DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_surface_in, d_surface_out, d_profile_samples, d_vis_observers, d_vis_eyes, d_vis_out,
-            d_sky_elevation, d_sky_samples, d_unwrap_tab;
+            d_sky_elevation, d_sky_samples, d_suns, d_sun_lit, d_sun_shadow, d_sun_exposure, d_unwrap_tab;
         PinnedBuffer h_ray_stage, h_surface_stage;
         std::vector<double> unwrap_tab;
         std::vector<uint8_t> unwrap_key;
@@ -399,6 +405,7 @@ class TerrainRenderer {
     int visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m);      // checks, then resolve_observers
     int resolve_observers(uint32_t n_observers, const topo_observer* observers);      // the tables, and the observers resolved into d_vis_eyes on stream_
     int skyline_check(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m);
+    int sun_begin(uint32_t n_suns, const topo_sun* suns);      // checks, the tables, and the suns normalised into d_suns on stream_
 
     std::string err_;
 };

@@ -486,6 +486,24 @@ int topo_skyline_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* 
     TOPO_CALL(ctx->r->skyline_read(n_observers, observers, az0_deg, daz_deg, n_az, min_range_m, max_range_m, elevation, samples));
 }
 
+int topo_sun_exposure_grid_device(topo_ctx* ctx, uint32_t n_suns, const topo_sun* suns, double lon0_deg, double lat0_deg, double dlon_deg, double dlat_deg, uint32_t nx,
+                                  uint32_t ny, uint64_t* lit_dev, uint64_t* shadow_dev, float* exposure_dev, size_t mask_pitch_bytes, size_t exposure_pitch_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->sun_exposure_grid_device(n_suns, suns, lon0_deg, lat0_deg, dlon_deg, dlat_deg, nx, ny, lit_dev, shadow_dev, exposure_dev, mask_pitch_bytes,
+                                               exposure_pitch_bytes));
+}
+
+int topo_sun_exposure_device(topo_ctx* ctx, uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_dev, uint64_t* lit_dev, uint64_t* shadow_dev,
+                             float* exposure_dev) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->sun_exposure_device(n_suns, suns, n, lonlat_dev, lit_dev, shadow_dev, exposure_dev));
+}
+
+int topo_sun_exposure_read(topo_ctx* ctx, uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_deg, uint64_t* lit, uint64_t* shadow, float* exposure) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->sun_exposure_read(n_suns, suns, n, lonlat_deg, lit, shadow, exposure));
+}
+
 void topo_ecef_from_lonlat(double lon_deg, double lat_deg, double height_m, double out[3]) {
     if (!out) return;
     double u[3];

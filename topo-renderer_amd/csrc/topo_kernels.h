@@ -298,6 +298,18 @@ struct SkyOut {            // each null or: observer o's n_az entries at + o * s
 void launch_skyline(const RayParams& p, const VisEye* eyes, uint32_t n_observers, double az0, double daz, uint32_t n_az, double min_range, double max_range,
                     const SkyOut& out, hipStream_t s);
 
+// sun exposure (topo_sun_exposure_*): per target the LIT and SHADOW masks over the call's suns and the weighted exposure (topo_sun.h);
+// needs no submission.  Reads what the rays read (RayParams) and the suns (device memory, n_suns <= 64 normalised records); writes
+// only its outputs, each nullable.
+struct SunDir;           // = topo_sun with a unit direction (topo_sun.h)
+// row r, column c: masks at + r * mask_pitch + 8 c, exposure at + r * exposure_pitch + 4 c (bytes) for the targets lon0 + c dlon,
+// lat0 + r dlat; ceil(nx / 64) * ny < 2^32
+void launch_sun_exposure_grid(const RayParams& p, const SunDir* suns, uint32_t n_suns, double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny,
+                              uint64_t* lit, uint64_t* shadow, float* exposure, size_t mask_pitch, size_t exposure_pitch, hipStream_t s);
+// the same for n (lon, lat) pairs: entry i at [i] of each output
+void launch_sun_exposure_list(const RayParams& p, const SunDir* suns, uint32_t n_suns, const double* lonlat, uint32_t n, uint64_t* lit, uint64_t* shadow, float* exposure,
+                              hipStream_t s);
+
 // unwrap (topo_unwrap_*): n_views views of src_w x src_h that share an eye, resampled into one out_w x out_h azimuth / elevation
 // image (topo_unwrap.h).  Reads the tables and the source images; writes only the outputs given (each nullable; rgba_out needs
 // rgba_src, depth_out needs depth_src).
