@@ -619,6 +619,51 @@ int topo_sun_exposure_device(topo_ctx* ctx, uint32_t n_suns, const topo_sun* sun
 /* Host memory: n pairs in, lit[i], shadow[i], exposure[i]; waits. */
 int topo_sun_exposure_read(topo_ctx* ctx, uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_deg, uint64_t* lit, uint64_t* shadow, float* exposure);
 
+/* ---- peak labels: the peaks an image shows, laid out in rows -- per view or per strip, a whole submission in one call -----------------
+ * Steps 1 and 2 of the reference's labelled panorama: get_visible_labels (render_engine.rs:338-396) and layout_labels /
+ * process_label_layout (text_renderer.rs:300-372).  Tessellating leader lines and backgrounds and shaping text stay the host's; the
+ * lines and glyphs are drawn by topo_overlay_lines* / topo_overlay_glyphs*.
+ * Image.  views_per_image consecutive views of width x height, side by side: columns 0 .. Wi - 1, Wi = views_per_image * width.  1 is
+ * the reference's single frame, 8 a panorama strip, laid out as the one image the viewer sees: labels do not collide across a sector
+ * seam.  There is no wrap-around at 360 degrees.
+ * Candidate.  For image i and peak p (ECEF f32 xyz) the image's views are taken in ascending order; the first view v in which the peak
+ * passes the test of topo_visible_peaks -- through that view's camera_proj, against that view's depth -- makes it a candidate at
+ * peak_x = v * width + x_pos, peak_y = y_pos.
+ * Layout.  Candidates are taken in ascending peak index: the caller's array order is the priority order (the reference iterates a
+ * BTreeMap, then each location's peaks).  w = widths[p]; a w that is not finite or < 0 is never labelled.  Else l = peak_x,
+ * r = min(sat_u32(ceil((float)peak_x + w)), Wi - 1) -- f32 sum and ceil, sat_u32 Rust's `as u32` -- and the label takes the lowest
+ * row k < max_rows in which no column of the closed range [l, r] is taken, and takes those columns there; touching counts as overlap.
+ * No free row: visible but unlabelled.  label_x = (float)peak_x, label_y = row_height * (0.5f + (float)k) (the reference passes
+ * LINE_HEIGHT + LINE_PADDING = 20), label_width = w.  csrc/topo_labels.h argues why this grid decides as the reference's sorted edge
+ * sets do.
+ * Limits.  TOPO_ERR_UNSUPPORTED for max_rows > 64 or Wi * max_rows > 524288: the occupancy grid of one image is at most 64 KiB of
+ * bits (a 16384-column strip with the reference's 8 rows takes 16 KiB). */
+typedef struct topo_label { uint32_t peak, view, row; float label_x, label_y, label_width, peak_x, peak_y; } topo_label; /* 32 bytes = LabelLayout */
+typedef struct topo_label_params { float row_height; uint32_t max_rows; uint32_t views_per_image; uint32_t cap; } topo_label_params; /* 16 bytes */
+/* The layout rule alone, on the host, for positions already known: n labels at columns x[j] < image_width with widths[j].  row_out[j]
+ * is the row, -1 for no row free, -2 for an unusable width; out (nullable, room for n) receives the placed labels in order with
+ * peak = j, view = 0, peak_y = 0.  Returns the number placed, or TOPO_ERR_INVALID (a null pointer with n > 0, image_width or max_rows
+ * of 0, an x[j] >= image_width) or TOPO_ERR_UNSUPPORTED (the limits above).  Pure: no context, no GPU. */
+int topo_label_layout(uint32_t n, const uint32_t* x, const float* widths, uint32_t image_width, float row_height, uint32_t max_rows, int32_t* row_out, topo_label* out);
+/* Over whole submissions, on the device: n_views views (HOST memory, read before the call returns; only camera_proj is read) of
+ * width x height whose depth is at depth_dev + v * depth_view_stride, rows depth_pitch apart (bytes) -- for example the arguments of
+ * the topo_render_views_device, topo_render_panorama or topo_render_batch call before it (topo_render_batch: n_views = 8 n,
+ * views_per_image = 8).  n_views must be a multiple of params->views_per_image; the images number n_views / views_per_image.  Peaks
+ * (3 n_peaks floats) and widths (n_peaks floats) are device memory.  Image i writes its labels in placement order to labels_dev +
+ * i * cap, only the first cap of them; counts_dev[i] is the number placed, whether or not they fitted in cap; state_dev (nullable)
+ * [i * n_peaks + p] is 0 not visible, 1 labelled, 2 visible without a free row, 3 visible with an unusable width.
+ * Asynchronous on the context's stream (topo_set_stream), in order behind whatever was queued there, as topo_visible_peaks_device;
+ * touches no frame state and needs no tile.  TOPO_ERR_INVALID for null pointers, max_rows == 0, views_per_image == 0, n_views %
+ * views_per_image != 0, a width or height of 0, a pitch smaller than a row or a view stride smaller than a view, and misaligned
+ * pointers, pitches or strides (4 bytes). */
+int topo_labels_device(topo_ctx* ctx, const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t width, uint32_t height,
+                       const float* depth_dev, size_t depth_view_stride, size_t depth_pitch, uint32_t n_peaks, const float* peaks_xyz_dev, const float* widths_dev,
+                       topo_label* labels_dev, uint32_t* counts_dev, uint8_t* state_dev);
+/* The same with host memory for the peaks, the widths and the outputs; the depth stays a device pointer.  Waits. */
+int topo_labels_read(topo_ctx* ctx, const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t width, uint32_t height,
+                     const float* depth_dev, size_t depth_view_stride, size_t depth_pitch, uint32_t n_peaks, const float* peaks_xyz, const float* widths,
+                     topo_label* labels, uint32_t* counts, uint8_t* state);
+
 /* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
  * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
  * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --

@@ -67,6 +67,11 @@ SKYLINE_DTYPE = np.dtype([("elevation_deg", "<f8"), ("range_m", "<f8"), ("lon_de
 SUN_NIGHT = 4
 # topo_sun, 32 bytes
 SUN_DTYPE = np.dtype([("dir", "<f8", 3), ("weight", "<f8")])
+LABEL_HIDDEN, LABEL_PLACED, LABEL_NO_ROW, LABEL_BAD_WIDTH = 0, 1, 2, 3      # the state bytes of topo_labels_*
+# topo_label, 32 bytes, and topo_label_params, 16 bytes
+LABEL_DTYPE = np.dtype([("peak", "<u4"), ("view", "<u4"), ("row", "<u4"), ("label_x", "<f4"), ("label_y", "<f4"), ("label_width", "<f4"), ("peak_x", "<f4"),
+                        ("peak_y", "<f4")])
+LABEL_PARAMS_DTYPE = np.dtype([("row_height", "<f4"), ("max_rows", "<u4"), ("views_per_image", "<u4"), ("cap", "<u4")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
 # topo_debug_read_cull_lists (test hook): WorkItem and FarItem of csrc/topo_kernels.h
@@ -212,6 +217,9 @@ def lib():
             "topo_sun_exposure_grid_device": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, C.c_double, C.c_double, u32, u32, vp, vp, vp, sz, sz]),
             "topo_sun_exposure_device": (C.c_int, [vp, u32, vp, u32, vp, vp, vp, vp]),
             "topo_sun_exposure_read": (C.c_int, [vp, u32, vp, u32, vp, vp, vp, vp]),
+            "topo_label_layout": (C.c_int, [u32, vp, vp, u32, f32, u32, vp, vp]),
+            "topo_labels_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, u32, vp, vp, vp, vp, vp]),
+            "topo_labels_read": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, u32, vp, vp, vp, vp, vp]),
             "topo_ecef_from_lonlat": (None, [C.c_double, C.c_double, C.c_double, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
@@ -420,6 +428,28 @@ def unwrap_xy(params, az_el) -> np.ndarray:
     out = np.full((len(a), 2), np.nan, np.float64)
     lib().topo_unwrap_xy(_p(p), len(a), _p(a), _p(out))
     return out
+
+
+def label_params(row_height: float = 20.0, max_rows: int = 8, views_per_image: int = 1, cap: int = 0) -> np.ndarray:
+    """A topo_label_params record (the reference: row_height = LINE_HEIGHT + LINE_PADDING = 20, MAX_ROWS = 8, one view per image)."""
+    p = np.zeros(1, LABEL_PARAMS_DTYPE)
+    p["row_height"], p["max_rows"], p["views_per_image"], p["cap"] = row_height, max_rows, views_per_image, cap
+    return p
+
+
+def label_layout(x, widths, image_width: int, row_height: float = 20.0, max_rows: int = 8):
+    """topo_label_layout: the layout rule on the host for labels at columns x (n,) with widths (n,) f32 in an image of image_width
+    columns -> ((n,) int32 rows: -1 no row free, -2 unusable width; the placed labels, LABEL_DTYPE, in order, peak = the index).  No GPU."""
+    xs = np.ascontiguousarray(x, dtype=np.uint32).reshape(-1)
+    ws = np.ascontiguousarray(widths, dtype=np.float32).reshape(-1)
+    if len(xs) != len(ws):
+        raise ValueError("x and widths differ in length")
+    rows, out = np.zeros(len(xs), np.int32), np.zeros(len(xs), LABEL_DTYPE)
+    ptr = lambda a: _p(a) if a.size else None
+    n = lib().topo_label_layout(len(xs), ptr(xs), ptr(ws), image_width, row_height, max_rows, ptr(rows), ptr(out))
+    if n < 0:
+        raise TopoError(n, "topo_label_layout: bad arguments" if n == TOPO_ERR_INVALID else "topo_label_layout: grid too large (max_rows <= 64, columns x max_rows <= 524288)")
+    return rows, out[:n]
 
 
 def post_uniforms(width, height, pixelize_n=100.0) -> np.ndarray:
@@ -773,6 +803,50 @@ class TerrainRenderer:
         u = np.ascontiguousarray(uniforms).view(np.uint8)
         self._check(lib().topo_visible_peaks_device(self._h, _p(u), width, height, C.c_void_p(depth_ptr), depth_pitch, n,
                                                     C.c_void_p(peaks_ptr), C.c_void_p(visible_ptr), C.c_void_p(xy_ptr)))
+
+    # peak labels: the peaks depth images show, laid out in rows, per image of views_per_image views (include/topo_hip.h)
+    def labels_device(self, params, uniforms_list, width: int, height: int, depth_ptr: int, n_peaks: int, peaks_ptr: int, widths_ptr: int, labels_ptr: int,
+                      counts_ptr: int, state_ptr: int = 0, depth_view_stride: int = None, depth_pitch: int = None):
+        """topo_labels_device: the views (uniforms_list: their 160-byte uniforms, or packed (n, 160) bytes) whose depth is at depth_ptr
+        (defaults: densely packed) -> per image of params["views_per_image"] views its first params["cap"] labels (LABEL_DTYPE) at
+        labels_ptr + image * cap, the number placed at counts_ptr + 4 * image and, if wanted, the state bytes at state_ptr + image *
+        n_peaks + peak; everything device memory; queued on the context's stream."""
+        p, us = self._label_args(params, uniforms_list)
+        ptr = lambda v: C.c_void_p(v) if v else None
+        dp = 4 * width if depth_pitch is None else depth_pitch
+        self._check(lib().topo_labels_device(self._h, _p(p), len(us), _p(us) if len(us) else None, width, height, ptr(depth_ptr),
+                                             dp * height if depth_view_stride is None else depth_view_stride, dp, n_peaks, ptr(peaks_ptr), ptr(widths_ptr),
+                                             ptr(labels_ptr), ptr(counts_ptr), ptr(state_ptr)))
+
+    def labels_read(self, params, uniforms_list, width: int, height: int, depth_ptr: int, peaks_xyz, widths, depth_view_stride: int = None, depth_pitch: int = None):
+        """topo_labels_read: peaks (n, 3) f32 and widths (n,) f32 from the host against the depth at depth_ptr (device memory) ->
+        ((images, cap) LABEL_DTYPE, zero behind each image's labels; (images,) uint32 counts; (images, n) uint8 states); waits."""
+        p, us = self._label_args(params, uniforms_list)
+        pk = np.ascontiguousarray(peaks_xyz, dtype=np.float32).reshape(-1, 3)
+        ws = np.ascontiguousarray(widths, dtype=np.float32).reshape(-1)
+        if len(pk) != len(ws):
+            raise ValueError("peaks and widths differ in length")
+        vpi, cap = int(p["views_per_image"][0]), int(p["cap"][0])
+        images = len(us) // vpi if vpi else 0
+        labels, counts, state = np.zeros((images, cap), LABEL_DTYPE), np.zeros(images, np.uint32), np.zeros((images, len(pk)), np.uint8)
+        ptr = lambda a: _p(a) if a.size else None
+        dp = 4 * width if depth_pitch is None else depth_pitch
+        self._check(lib().topo_labels_read(self._h, _p(p), len(us), _p(us) if len(us) else None, width, height, C.c_void_p(depth_ptr) if depth_ptr else None,
+                                           dp * height if depth_view_stride is None else depth_view_stride, dp, len(pk), ptr(pk), ptr(ws), ptr(labels),
+                                           _p(counts) if images else _p(np.zeros(1, np.uint32)), ptr(state)))
+        return labels, counts, state
+
+    @staticmethod
+    def _label_args(params, uniforms_list):
+        p = np.ascontiguousarray(params, dtype=LABEL_PARAMS_DTYPE).reshape(-1)[:1]
+        if isinstance(uniforms_list, np.ndarray) and uniforms_list.dtype == np.uint8 and uniforms_list.ndim == 2:
+            us = np.ascontiguousarray(uniforms_list)
+            assert us.shape[1] == 160
+        elif len(uniforms_list) == 0:
+            us = np.zeros((0, 160), np.uint8)
+        else:
+            us = np.ascontiguousarray(np.stack([np.ascontiguousarray(u).view(np.uint8).reshape(160) for u in uniforms_list]))
+        return p, us
 
     # viewshed: the DEM cells the frames rendered while accumulation is on show (include/topo_hip.h)
     def viewshed_enable(self, on: bool = True):

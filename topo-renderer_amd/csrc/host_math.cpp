@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "topo_labels.h"
 #include "topo_math.h"
 #include "topo_unwrap.h"
 
@@ -172,6 +173,46 @@ void unwrap_xy(const topo_unwrap_params* p, uint32_t n, const double* az_el, dou
         xy[2 * i] = a / p->az_span_deg * (double)p->out_w;
         xy[2 * i + 1] = (cyl ? (tt - std::tan(el * kUnwrapRad)) / (tt - tb) : (p->el_top_deg - el) / (p->el_top_deg - p->el_bottom_deg)) * (double)p->out_h;
     }
+}
+
+// ---- peak labels: the layout rule on the host (topo_labels.h) ----------------------------------------------------------------------
+
+static_assert(sizeof(LabelRec) == sizeof(topo_label) && sizeof(topo_label) == 32 && sizeof(topo_label_params) == 16, "label layouts");
+
+const char* label_grid_error(uint64_t image_width, uint32_t max_rows, int* code) {
+    *code = TOPO_ERR_INVALID;
+    if (image_width == 0) return "an image without columns";
+    if (max_rows == 0) return "max_rows must not be 0";
+    *code = TOPO_ERR_UNSUPPORTED;
+    if (max_rows > kLabelMaxRows) return "at most 64 label rows";
+    if (image_width * max_rows > kLabelMaxGridBits) return "image columns x max_rows must not exceed 524288 (64 KiB of occupancy bits)";
+    return nullptr;
+}
+
+int label_layout(uint32_t n, const uint32_t* x, const float* widths, uint32_t image_width, float row_height, uint32_t max_rows, int32_t* row_out, topo_label* out) {
+    int code;
+    if (label_grid_error(image_width, max_rows, &code)) return code;
+    if (n && (!x || !widths || !row_out)) return TOPO_ERR_INVALID;
+    for (uint32_t j = 0; j < n; ++j)
+        if (x[j] >= image_width) return TOPO_ERR_INVALID;
+    std::vector<uint32_t> grid(label_grid_words(image_width, max_rows), 0u);
+    uint32_t count = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+        const float w = widths[j];
+        if (!label_width_usable(w)) {
+            row_out[j] = -2;
+            continue;
+        }
+        const int32_t k = label_place(grid.data(), image_width, max_rows, x[j], label_right(x[j], w, image_width));
+        row_out[j] = k;
+        if (k < 0) continue;
+        if (out) {
+            const LabelRec rec{j, 0u, (uint32_t)k, (float)x[j], label_y(row_height, (uint32_t)k), w, (float)x[j], 0.0f};
+            memcpy(&out[count], &rec, sizeof rec);
+        }
+        ++count;
+    }
+    return (int)count;
 }
 
 // Uniforms::new (render/data.rs:44-58) over Camera::{up,direction,get_view,build_view_proj_matrix}

@@ -26,6 +26,10 @@ const char* unwrap_params_error(const topo_unwrap_params* p);
 const char* unwrap_views_error(uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h);
 void unwrap_tables(const topo_unwrap_params* p, uint32_t n_views, const topo_uniforms* views, std::vector<double>& out);
 void unwrap_xy(const topo_unwrap_params* p, uint32_t n, const double* az_el, double* xy_out);
+// topo_label_layout: the label rows of positions already known (topo_labels.h: label_place); the number placed or a TOPO_ERR_* code
+int label_layout(uint32_t n, const uint32_t* x, const float* widths, uint32_t image_width, float row_height, uint32_t max_rows, int32_t* row_out, topo_label* out);
+// why a label grid of image_width columns and max_rows rows cannot be had (null: it can), and the code that goes with it
+const char* label_grid_error(uint64_t image_width, uint32_t max_rows, int* code);
 void terrain_rotation(float model_lon_deg, float model_lat_deg, float rot3x3_colmajor[9]);
 uint32_t locations_range(float latitude, float longitude, float range_dist, int32_t* out_lat_lon, uint32_t cap);
 void change_location_plan(float latitude, float longitude, float range_dist, const int32_t* loaded, uint32_t n_loaded,

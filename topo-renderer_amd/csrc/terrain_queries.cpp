@@ -1,6 +1,7 @@
-// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, visibility, skyline, sun exposure, unwrap), the tile-set
+// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, visibility, skyline, sun exposure, peak labels, unwrap), the tile-set
 // tables they read and their handle on the latest submission.  The frame path is terrain_renderer.cpp (see terrain_renderer.hpp).
 #include "terrain_renderer.hpp"
+#include "topo_labels.h"
 #include "topo_surface.h"
 #include "topo_skyline.h"
 #include "topo_sun.h"
@@ -26,6 +27,7 @@ static_assert(sizeof(SkySample) == sizeof(topo_skyline_sample) && sizeof(topo_sk
 static_assert(kSkyNone == TOPO_SKY_NONE && kSkyTerrain == TOPO_SKY_TERRAIN && kSkyNoObserver == TOPO_SKY_NO_OBSERVER, "skyline kinds");
 static_assert(sizeof(SunDir) == sizeof(topo_sun) && sizeof(topo_sun) == 32, "sun layout");
 static_assert(kSunNone == TOPO_SUN_NONE && kSunLit == TOPO_SUN_LIT && kSunAway == TOPO_SUN_AWAY && kSunShadow == TOPO_SUN_SHADOW && kSunNight == TOPO_SUN_NIGHT, "sun classes");
+static_assert(sizeof(LabelRec) == sizeof(topo_label) && sizeof(topo_label) == 32 && sizeof(topo_label_params) == 16, "label layouts");
 static_assert(kTileSphereDoubles == kLosSphereDoubles, "the cull prefilter and the rays read the same spheres: one gather, one layout");
 
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
@@ -730,6 +732,117 @@ int TerrainRenderer::sun_exposure_read(uint32_t n_suns, const topo_sun* suns, ui
     if (lit) TOPO_HIP_TRY(hipMemcpy(lit, query_.d_sun_lit.p, mask_bytes, hipMemcpyDeviceToHost));
     if (shadow) TOPO_HIP_TRY(hipMemcpy(shadow, query_.d_sun_shadow.p, mask_bytes, hipMemcpyDeviceToHost));
     if (exposure) TOPO_HIP_TRY(hipMemcpy(exposure, query_.d_sun_exposure.p, exp_bytes, hipMemcpyDeviceToHost));
+    return query_fold_check();
+}
+
+// ---- peak labels ------------------------------------------------------------------------------------------------------------------
+
+// What both label calls refuse (null outputs are the callers' to refuse), before anything is queued.
+int TerrainRenderer::labels_check(const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t w, uint32_t h, const float* depth_dev,
+                                  size_t depth_view_stride, size_t depth_pitch) {
+    if (!params || !depth_dev || (n_views && !views)) return fail(TOPO_ERR_INVALID, "null argument");
+    if (params->views_per_image == 0) return fail(TOPO_ERR_INVALID, "views_per_image must not be 0");
+    if (params->max_rows == 0) return fail(TOPO_ERR_INVALID, "max_rows must not be 0");
+    if (n_views % params->views_per_image != 0) return fail(TOPO_ERR_INVALID, "n_views must be a multiple of views_per_image");
+    if (w == 0 || h == 0) return fail(TOPO_ERR_INVALID, "view size must be non-zero");
+    if ((uintptr_t)depth_dev % 4 != 0 || depth_pitch % 4 != 0 || depth_view_stride % 4 != 0)
+        return fail(TOPO_ERR_INVALID, "depth pointer, pitch and view stride must be multiples of 4 bytes");
+    if (const char* why = view_image_error(n_views, w, h, 4, depth_view_stride, depth_pitch)) return fail(TOPO_ERR_INVALID, why);
+    int code;
+    if (const char* why = label_grid_error((uint64_t)params->views_per_image * w, params->max_rows, &code)) return fail(code, why);
+    return TOPO_OK;
+}
+
+// Queued on stream_, in order, like topo_visible_peaks_device: the depth is the caller's, whatever wrote it.  The views' matrices go
+// into the context's device table on stream_ (behind the kernels of an earlier call that still read it) only when they differ from
+// the last call's; their host copy is the key.
+int TerrainRenderer::labels_device(const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t w, uint32_t h, const float* depth_dev,
+                                   size_t depth_view_stride, size_t depth_pitch, uint32_t n_peaks, const float* peaks_dev, const float* widths_dev, topo_label* labels_dev,
+                                   uint32_t* counts_dev, uint8_t* state_dev) {
+    if (int rc = labels_check(params, n_views, views, w, h, depth_dev, depth_view_stride, depth_pitch)) return rc;
+    if (!counts_dev || (params->cap && !labels_dev) || (n_peaks && (!peaks_dev || !widths_dev))) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)peaks_dev % 4 != 0 || (uintptr_t)widths_dev % 4 != 0 || (uintptr_t)labels_dev % 4 != 0 || (uintptr_t)counts_dev % 4 != 0)
+        return fail(TOPO_ERR_INVALID, "peaks, widths, labels and counts must be 4-byte aligned");
+    if (n_views == 0) return TOPO_OK;
+    if (int rc = bind_device()) return rc;
+    const size_t n_floats = (size_t)n_views * 16;
+    const bool same = query_.d_label_projs.p && query_.label_projs.size() == n_floats &&
+                      [&] {
+                          for (uint32_t v = 0; v < n_views; ++v)
+                              if (memcmp(&query_.label_projs[16 * (size_t)v], views[v].camera_proj, 16 * sizeof(float)) != 0) return false;
+                          return true;
+                      }();
+    if (!same) {
+        query_.label_projs.clear();      // (a failure below leaves no key behind)
+        if (int rc = ensure(stream_, query_.d_label_projs, n_floats * sizeof(float))) return rc;
+        std::vector<float> projs(n_floats);
+        for (uint32_t v = 0; v < n_views; ++v) memcpy(&projs[16 * (size_t)v], views[v].camera_proj, 16 * sizeof(float));
+        TOPO_HIP_TRY(hipMemcpyAsync(query_.d_label_projs.p, projs.data(), n_floats * sizeof(float), hipMemcpyHostToDevice, stream_));      // (pageable: read before it returns)
+        query_.label_projs = std::move(projs);
+    }
+    if (int rc = ensure_query_check(stream_)) return rc;
+    LabelParams p{};
+    p.projs = query_.d_label_projs.as<const float>();
+    p.depth = reinterpret_cast<const uint8_t*>(depth_dev);
+    p.depth_view_stride = depth_view_stride;
+    p.depth_pitch = depth_pitch;
+    p.peaks = peaks_dev;
+    p.widths = widths_dev;
+    p.labels = reinterpret_cast<LabelRec*>(labels_dev);
+    p.counts = counts_dev;
+    p.state = state_dev;
+    p.check = query_.d_check.as<uint32_t>();
+    p.n_views = n_views;
+    p.n_images = n_views / params->views_per_image;
+    p.views_per_image = params->views_per_image;
+    p.width = w;
+    p.height = h;
+    p.n_peaks = n_peaks;
+    p.max_rows = params->max_rows;
+    p.cap = params->cap;
+    p.row_height = params->row_height;
+    launch_labels(p, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Host read.  The caller's memory is pageable, so nothing is staged (as topo_sun_exposure_read): the stream is drained, the peaks and
+// widths go up and the outputs come down with blocking copies.
+int TerrainRenderer::labels_read(const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t w, uint32_t h, const float* depth_dev,
+                                 size_t depth_view_stride, size_t depth_pitch, uint32_t n_peaks, const float* peaks, const float* widths, topo_label* labels, uint32_t* counts,
+                                 uint8_t* state) {
+    if (int rc = labels_check(params, n_views, views, w, h, depth_dev, depth_view_stride, depth_pitch)) return rc;
+    if (!counts || (params->cap && !labels) || (n_peaks && (!peaks || !widths))) return fail(TOPO_ERR_INVALID, "null argument");
+    if (n_views == 0) return TOPO_OK;
+    if (int rc = bind_device()) return rc;
+    const size_t n_images = n_views / params->views_per_image;
+    const size_t peak_bytes = (size_t)n_peaks * 12, width_bytes = (size_t)n_peaks * 4, label_bytes = n_images * params->cap * sizeof(topo_label),
+                 count_bytes = n_images * sizeof(uint32_t), state_bytes = state ? n_images * n_peaks : 0;
+    if (int rc = ensure(stream_, query_.d_label_in, peak_bytes + width_bytes + 16)) return rc;
+    if (int rc = ensure(stream_, query_.d_label_out, label_bytes + count_bytes + state_bytes + 16)) return rc;
+    uint8_t* const in = query_.d_label_in.as<uint8_t>();
+    uint8_t* const out = query_.d_label_out.as<uint8_t>();
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    if (n_peaks) {
+        TOPO_HIP_TRY(hipMemcpy(in, peaks, peak_bytes, hipMemcpyHostToDevice));
+        TOPO_HIP_TRY(hipMemcpy(in + peak_bytes, widths, width_bytes, hipMemcpyHostToDevice));
+    }
+    if (int rc = labels_device(params, n_views, views, w, h, depth_dev, depth_view_stride, depth_pitch, n_peaks, reinterpret_cast<const float*>(in),
+                               reinterpret_cast<const float*>(in + peak_bytes), reinterpret_cast<topo_label*>(out), reinterpret_cast<uint32_t*>(out + label_bytes),
+                               state ? out + label_bytes + count_bytes : nullptr))
+        return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    TOPO_HIP_TRY(hipMemcpy(counts, out + label_bytes, count_bytes, hipMemcpyDeviceToHost));
+    // only what the kernel wrote comes down: the first min(count, cap) records of each image
+    if (label_bytes) {
+        std::vector<topo_label> got(n_images * params->cap);
+        TOPO_HIP_TRY(hipMemcpy(got.data(), out, label_bytes, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n_images; ++i) {
+            const size_t n = counts[i] < params->cap ? counts[i] : params->cap;
+            if (n) memcpy(labels + i * params->cap, &got[i * params->cap], n * sizeof(topo_label));
+        }
+    }
+    if (state_bytes) TOPO_HIP_TRY(hipMemcpy(state, out + label_bytes + count_bytes, state_bytes, hipMemcpyDeviceToHost));
     return query_fold_check();
 }
 

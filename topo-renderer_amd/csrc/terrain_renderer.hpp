@@ -198,6 +198,12 @@ class TerrainRenderer {
     int sun_exposure_device(uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_dev, uint64_t* lit_dev, uint64_t* shadow_dev, float* exposure_dev);
     int sun_exposure_read(uint32_t n_suns, const topo_sun* suns, uint32_t n, const double* lonlat_deg, uint64_t* lit, uint64_t* shadow, float* exposure);
 
+    // peak labels: the peaks the caller's depth images show, laid out in rows, per image of views_per_image views (topo_labels_*): no submission needed
+    int labels_device(const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t w, uint32_t h, const float* depth_dev, size_t depth_view_stride,
+                      size_t depth_pitch, uint32_t n_peaks, const float* peaks_dev, const float* widths_dev, topo_label* labels_dev, uint32_t* counts_dev, uint8_t* state_dev);
+    int labels_read(const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t w, uint32_t h, const float* depth_dev, size_t depth_view_stride,
+                    size_t depth_pitch, uint32_t n_peaks, const float* peaks, const float* widths, topo_label* labels, uint32_t* counts, uint8_t* state);
+
     // unwrap: finished views that share an eye as one azimuth / elevation image (topo_unwrap_device)
     int unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h, const OutputParams& src,
                       const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch);
@@ -382,13 +388,15 @@ class TerrainRenderer {
     // records or profile summaries out, their pinned staging, a profile read's samples; the visibility calls' observers as given and
     // as resolved -- the skyline calls' too --, a visibility read's classes, a skyline read's elevations and records, the sun exposure calls' suns and a sun exposure read's masks and exposures), and the device
     // copy of k_unwrap's f64 tables (topo_unwrap.h), kept for what they were built from -- the call's parameters, the views'
-    // direction blocks and the eye (unwrap_key) -- with their host copy, the source of the upload
+    // direction blocks and the eye (unwrap_key) -- with their host copy, the source of the upload; likewise the device table of the
+    // label calls' view matrices with its host copy (label_projs: key and source of the upload), and a label read's inputs and outputs
     struct QueryBuffers {
         DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_surface_in, d_surface_out, d_profile_samples, d_vis_observers, d_vis_eyes, d_vis_out,
-            d_sky_elevation, d_sky_samples, d_suns, d_sun_lit, d_sun_shadow, d_sun_exposure, d_unwrap_tab;
+            d_sky_elevation, d_sky_samples, d_suns, d_sun_lit, d_sun_shadow, d_sun_exposure, d_unwrap_tab, d_label_projs, d_label_in, d_label_out;
         PinnedBuffer h_ray_stage, h_surface_stage;
         std::vector<double> unwrap_tab;
         std::vector<uint8_t> unwrap_key;
+        std::vector<float> label_projs;
     } query_;
     int ensure_query_check(hipStream_t s);      // the check build's bounds record (the product build: nothing)
     int query_fold_check();
@@ -406,6 +414,8 @@ class TerrainRenderer {
     int resolve_observers(uint32_t n_observers, const topo_observer* observers);      // the tables, and the observers resolved into d_vis_eyes on stream_
     int skyline_check(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m);
     int sun_begin(uint32_t n_suns, const topo_sun* suns);      // checks, the tables, and the suns normalised into d_suns on stream_
+    int labels_check(const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t w, uint32_t h, const float* depth_dev, size_t depth_view_stride,
+                     size_t depth_pitch);      // what both label calls refuse, before anything is queued
 
     std::string err_;
 };

@@ -504,6 +504,25 @@ int topo_sun_exposure_read(topo_ctx* ctx, uint32_t n_suns, const topo_sun* suns,
     TOPO_CALL(ctx->r->sun_exposure_read(n_suns, suns, n, lonlat_deg, lit, shadow, exposure));
 }
 
+int topo_label_layout(uint32_t n, const uint32_t* x, const float* widths, uint32_t image_width, float row_height, uint32_t max_rows, int32_t* row_out, topo_label* out) {
+    TOPO_CALL(topo::label_layout(n, x, widths, image_width, row_height, max_rows, row_out, out));
+}
+
+int topo_labels_device(topo_ctx* ctx, const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t width, uint32_t height,
+                       const float* depth_dev, size_t depth_view_stride, size_t depth_pitch, uint32_t n_peaks, const float* peaks_xyz_dev, const float* widths_dev,
+                       topo_label* labels_dev, uint32_t* counts_dev, uint8_t* state_dev) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->labels_device(params, n_views, views, width, height, depth_dev, depth_view_stride, depth_pitch, n_peaks, peaks_xyz_dev, widths_dev, labels_dev,
+                                    counts_dev, state_dev));
+}
+
+int topo_labels_read(topo_ctx* ctx, const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t width, uint32_t height,
+                     const float* depth_dev, size_t depth_view_stride, size_t depth_pitch, uint32_t n_peaks, const float* peaks_xyz, const float* widths,
+                     topo_label* labels, uint32_t* counts, uint8_t* state) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->labels_read(params, n_views, views, width, height, depth_dev, depth_view_stride, depth_pitch, n_peaks, peaks_xyz, widths, labels, counts, state));
+}
+
 void topo_ecef_from_lonlat(double lon_deg, double lat_deg, double height_m, double out[3]) {
     if (!out) return;
     double u[3];

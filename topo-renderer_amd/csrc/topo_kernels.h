@@ -310,6 +310,27 @@ void launch_sun_exposure_grid(const RayParams& p, const SunDir* suns, uint32_t n
 void launch_sun_exposure_list(const RayParams& p, const SunDir* suns, uint32_t n_suns, const double* lonlat, uint32_t n, uint64_t* lit, uint64_t* shadow, float* exposure,
                               hipStream_t s);
 
+// peak labels (topo_labels_*): per image of views_per_image consecutive views the peaks its depth shows and the label row of each
+// (topo_labels.h); needs no submission and no tile.  Reads the views' matrices, the depth images, the peaks and the widths; writes only
+// its outputs (state nullable).
+struct LabelRec;         // = topo_label (topo_labels.h)
+struct LabelParams {
+    const float* projs;           // n_views matrices of 16 floats (camera_proj), device memory written before the launch
+    const uint8_t* depth;         // view k at + k * depth_view_stride, rows depth_pitch apart (bytes)
+    size_t depth_view_stride, depth_pitch;
+    const float* peaks;           // n_peaks ECEF xyz
+    const float* widths;          // n_peaks
+    LabelRec* labels;             // image i: the first `cap` placed at + i * cap
+    uint32_t* counts;             // image i: the number placed
+    uint8_t* state;               // image i, peak p: at [i * n_peaks + p]
+    uint32_t* check;              // TOPO_BOUNDS_CHECK build: the queries' status record; else unused
+    uint32_t n_views, n_images, views_per_image, width, height, n_peaks, max_rows, cap;
+    uint32_t waves;               // images per workgroup (set by the launcher)
+    float row_height;
+};
+// max_rows <= 64 and views_per_image * width * max_rows <= 524288 (else nothing is launched)
+void launch_labels(LabelParams p, hipStream_t s);
+
 // unwrap (topo_unwrap_*): n_views views of src_w x src_h that share an eye, resampled into one out_w x out_h azimuth / elevation
 // image (topo_unwrap.h).  Reads the tables and the source images; writes only the outputs given (each nullable; rgba_out needs
 // rgba_src, depth_out needs depth_src).
