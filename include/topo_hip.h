@@ -664,6 +664,52 @@ int topo_labels_read(topo_ctx* ctx, const topo_label_params* params, uint32_t n_
                      const float* depth_dev, size_t depth_view_stride, size_t depth_pitch, uint32_t n_peaks, const float* peaks_xyz, const float* widths,
                      topo_label* labels, uint32_t* counts, uint8_t* state);
 
+/* ---- summits: the peaks of the drawn mesh by isolation, and snapping given peaks to them ----------------------------------------------
+ * "Which peaks does this DEM hold?" -- a peak list for topo_visibility_*, topo_labels_* and topo_visible_peaks with nothing fetched --
+ * and "where is this database peak on the mesh that is drawn?": surveyed peaks sit a few posts off the DEM's own summit and tens of
+ * metres above or below it.  csrc/topo_summits.h states the rule and argues the search; in short:
+ * Posts.  A post is vertex (vx, vy) of a resident tile; it exists iff its tile's pixel scale is finite and not zero both ways and its
+ * height is finite, < 1e9 and > -R0 (topo_surface_*'s rule).  lon_deg / lat_deg are where the mesh puts the vertex.  The distance of two
+ * posts is the chord R0 |u_a - u_b| of their directions.  Q DOMINATES P iff it is higher, or equally high and earlier in (tile draw
+ * order, vy * w + vx).  The ISOLATION of P is the distance to the nearest post that dominates it among the resident posts within
+ * radius_m, +inf if there is none; P is a summit iff height_m >= min_height_m and isolation >= min_isolation_m.  Only resident posts
+ * count: near the mosaic's border an isolation is an upper bound.  A plateau has one summit, its first post; of posts duplicated by
+ * overlapping tiles only the earlier tile's is one (min_isolation_m > 0).
+ * radius_m is finite, > 0 and <= 1e6; 0 <= min_isolation_m <= radius_m; min_height_m is not NaN (-inf: no limit); anything else, a
+ * null or misaligned pointer (16 bytes for records and points, 4 for the count) and an unknown order are TOPO_ERR_INVALID with nothing
+ * written.  The calls need no submission; they run on the context's stream (topo_set_stream) behind whatever was queued there.  A context
+ * with no tiles is a successful no-op: the count is 0. */
+typedef struct topo_summit_params { double radius_m, min_isolation_m; float min_height_m; uint32_t order; } topo_summit_params;   /* 24 bytes */
+#define TOPO_SUMMIT_ORDER_TILE 0u       /* ascending (tile rank, vy * w + vx): the device order */
+#define TOPO_SUMMIT_ORDER_HEIGHT 1u     /* height descending, ties in tile order            (read only) */
+#define TOPO_SUMMIT_ORDER_ISOLATION 2u  /* isolation descending (+inf first), then height   (read only) */
+typedef struct topo_summit {            /* 64 bytes; written as four 16-byte stores */
+    double lon_deg, lat_deg, isolation_m;            /* isolation +inf: nothing higher within radius_m */
+    float height_m, higher_height_m;                 /* higher_*: the nearest dominator; all 0 when there is none */
+    int32_t tile_lat_deg, tile_lon_deg; uint32_t vx, vy;
+    int32_t higher_tile_lat_deg, higher_tile_lon_deg; uint32_t higher_vx, higher_vy;
+} topo_summit;
+typedef struct topo_summit_snap {       /* 48 bytes; written as three 16-byte stores */
+    double lon_deg, lat_deg, distance_m; float height_m; int32_t status;   /* 1 found, 0 none, -1 invalid; every other field 0 unless found */
+    int32_t tile_lat_deg, tile_lon_deg; uint32_t vx, vy;
+} topo_summit_snap;
+#define TOPO_SNAP_FOUND 1
+#define TOPO_SNAP_NONE 0
+#define TOPO_SNAP_INVALID (-1)
+/* Device memory.  *count_dev receives the number of summits found, which may exceed capacity; out_dev the first min(count, capacity) in
+ * tile order (TOPO_SUMMIT_ORDER_TILE, the only order accepted here); nothing is written past that.  The bytes are a function of the
+ * tile set and the parameters alone.  Asynchronous. */
+int topo_summits_device(topo_ctx* ctx, const topo_summit_params* params, topo_summit* out_dev, uint32_t capacity, uint32_t* count_dev);
+/* Host memory; waits.  The full set is ordered as params->order says, then the first min(count, capacity) are written; *count is the
+ * full number.  TOPO_ERR_CAPACITY when count > capacity (the records that fit and *count are still written: size a second call by it). */
+int topo_summits_read(topo_ctx* ctx, const topo_summit_params* params, topo_summit* out, uint32_t capacity, uint32_t* count);
+/* Snap: for each of n (lon, lat) pairs in degrees the best existing post within radius_m of the point's direction -- the highest; on
+ * equal height the nearer, then the earlier in (tile draw order, vy * w + vx).  TOPO_SNAP_NONE: no post in range; TOPO_SNAP_INVALID: a
+ * non-finite longitude or a latitude outside +-90.  n == 0 is a no-op.  Device memory, 16-byte aligned; asynchronous. */
+int topo_summit_snap_device(topo_ctx* ctx, uint32_t n, const double* lonlat_dev, double radius_m, topo_summit_snap* out_dev);
+/* Host memory; waits. */
+int topo_summit_snap_read(topo_ctx* ctx, uint32_t n, const double* lonlat_deg, double radius_m, topo_summit_snap* out);
+
 /* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
  * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
  * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --

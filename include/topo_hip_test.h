@@ -55,6 +55,15 @@ int topo_debug_read_cull_lists(topo_ctx* ctx, uint32_t* near_out, uint32_t near_
  * (updates that set at least one new bit).  All 0 before accumulation was ever enabled. */
 int topo_debug_viewshed_stats(topo_ctx* ctx, uint64_t out[3]);
 
+/* Test hook: the band height of the summit calls -- they work through each tile in bands of this many vertex rows, and a small scene
+ * crosses several bands only with a small value.  0 restores the default (as many rows as hold at most 2^22 posts).  The results do
+ * not depend on it. */
+int topo_debug_set_summit_band_rows(topo_ctx* ctx, uint32_t rows);
+
+/* Test accessor: what the last topo_summits_* call of the context counted (waits for the stream): out[0] = posts that passed
+ * k_summit_candidates, out[1] = those that also passed k_summit_reject (the summits), summed over the bands. */
+int topo_debug_summit_counts(topo_ctx* ctx, uint64_t out[2]);
+
 /* Test accessor: the tile's Rgba8Unorm normal texture, w*h*4 bytes, host pointer. */
 int topo_read_normals(topo_ctx* ctx, int32_t lat_deg, int32_t lon_deg, uint8_t* out);
 

@@ -72,6 +72,15 @@ LABEL_HIDDEN, LABEL_PLACED, LABEL_NO_ROW, LABEL_BAD_WIDTH = 0, 1, 2, 3      # th
 LABEL_DTYPE = np.dtype([("peak", "<u4"), ("view", "<u4"), ("row", "<u4"), ("label_x", "<f4"), ("label_y", "<f4"), ("label_width", "<f4"), ("peak_x", "<f4"),
                         ("peak_y", "<f4")])
 LABEL_PARAMS_DTYPE = np.dtype([("row_height", "<f4"), ("max_rows", "<u4"), ("views_per_image", "<u4"), ("cap", "<u4")])
+SUMMIT_ORDER_TILE, SUMMIT_ORDER_HEIGHT, SUMMIT_ORDER_ISOLATION = 0, 1, 2
+SNAP_FOUND, SNAP_NONE, SNAP_INVALID = 1, 0, -1
+# topo_summit_params, 24 bytes, topo_summit, 64 bytes, and topo_summit_snap, 48 bytes
+SUMMIT_PARAMS_DTYPE = np.dtype([("radius_m", "<f8"), ("min_isolation_m", "<f8"), ("min_height_m", "<f4"), ("order", "<u4")])
+SUMMIT_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("isolation_m", "<f8"), ("height_m", "<f4"), ("higher_height_m", "<f4"), ("tile_lat_deg", "<i4"),
+                         ("tile_lon_deg", "<i4"), ("vx", "<u4"), ("vy", "<u4"), ("higher_tile_lat_deg", "<i4"), ("higher_tile_lon_deg", "<i4"), ("higher_vx", "<u4"),
+                         ("higher_vy", "<u4")])
+SUMMIT_SNAP_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("distance_m", "<f8"), ("height_m", "<f4"), ("status", "<i4"), ("tile_lat_deg", "<i4"),
+                              ("tile_lon_deg", "<i4"), ("vx", "<u4"), ("vy", "<u4")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
 # topo_debug_read_cull_lists (test hook): WorkItem and FarItem of csrc/topo_kernels.h
@@ -220,6 +229,12 @@ def lib():
             "topo_label_layout": (C.c_int, [u32, vp, vp, u32, f32, u32, vp, vp]),
             "topo_labels_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, u32, vp, vp, vp, vp, vp]),
             "topo_labels_read": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, u32, vp, vp, vp, vp, vp]),
+            "topo_summits_device": (C.c_int, [vp, vp, vp, u32, vp]),
+            "topo_summits_read": (C.c_int, [vp, vp, vp, u32, vp]),
+            "topo_summit_snap_device": (C.c_int, [vp, u32, vp, C.c_double, vp]),
+            "topo_summit_snap_read": (C.c_int, [vp, u32, vp, C.c_double, vp]),
+            "topo_debug_set_summit_band_rows": (C.c_int, [vp, u32]),
+            "topo_debug_summit_counts": (C.c_int, [vp, vp]),
             "topo_ecef_from_lonlat": (None, [C.c_double, C.c_double, C.c_double, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
@@ -231,6 +246,27 @@ def lib():
         L._topo_symbols = tuple(sigs)
         _lib = L
     return _lib
+
+
+def summit_params(radius_m: float, min_isolation_m: float = 0.0, min_height_m: float = -np.inf, order: int = SUMMIT_ORDER_TILE):
+    """One SUMMIT_PARAMS_DTYPE record (topo_summit_params)."""
+    p = np.zeros(1, SUMMIT_PARAMS_DTYPE)
+    p["radius_m"], p["min_isolation_m"], p["min_height_m"], p["order"] = radius_m, min_isolation_m, min_height_m, order
+    return p
+
+
+def order_summits(records, order: int):
+    """Records in tile order (any dtype with height_m and isolation_m) as topo_summits_read orders them: TILE as they are; HEIGHT by
+    height descending; ISOLATION by isolation descending (+inf first), then height descending; ties stay in tile order."""
+    r = np.asarray(records)
+    if order == SUMMIT_ORDER_TILE:
+        return r.copy()
+    k = np.arange(len(r))
+    if order == SUMMIT_ORDER_HEIGHT:
+        return r[np.lexsort((k, -r["height_m"].astype(np.float64)))]
+    if order == SUMMIT_ORDER_ISOLATION:
+        return r[np.lexsort((k, -r["height_m"].astype(np.float64), -r["isolation_m"]))]
+    raise ValueError("unknown order")
 
 
 def _p(a):
@@ -1030,6 +1066,53 @@ class TerrainRenderer:
         self._check(lib().topo_skyline_read(self._h, len(o), _p(o) if len(o) else None, az0_deg, daz_deg, n_az, min_range_m, max_range_m,
                                             _p(el) if el is not None and el.size else None, _p(rec) if rec is not None and rec.size else None))
         return el, rec
+
+    # summits: the peaks of the drawn mesh by isolation, and snapping peaks to them (include/topo_hip.h); no submission needed
+    def summits_device(self, out_ptr: int, capacity: int, count_ptr: int, radius_m: float, min_isolation_m: float = 0.0, min_height_m: float = -np.inf,
+                       order: int = SUMMIT_ORDER_TILE):
+        """topo_summits_device: the first min(count, capacity) SUMMIT_DTYPE records in tile order at out_ptr and the uint32 count at
+        count_ptr (device memory); queued on the context's stream."""
+        p = summit_params(radius_m, min_isolation_m, min_height_m, order)
+        self._check(lib().topo_summits_device(self._h, _p(p), C.c_void_p(out_ptr) if out_ptr else None, capacity, C.c_void_p(count_ptr) if count_ptr else None))
+
+    def summits(self, radius_m: float, min_isolation_m: float = 0.0, min_height_m: float = -np.inf, order: int = SUMMIT_ORDER_TILE, capacity: int = None):
+        """topo_summits_read -> (SUMMIT_DTYPE records in `order`, the full count); waits.  capacity None: every summit (a second call
+        sized by the first one's count when 65536 records do not hold them); else at most `capacity` records, and the count says
+        whether there are more."""
+        p = summit_params(radius_m, min_isolation_m, min_height_m, order)
+        n = C.c_uint32(0)
+        cap = 65536 if capacity is None else capacity
+        out = np.zeros(cap, SUMMIT_DTYPE)
+        rc = lib().topo_summits_read(self._h, _p(p), _p(out) if cap else None, cap, C.byref(n))
+        if rc == TOPO_ERR_CAPACITY and capacity is None:
+            cap = n.value
+            out = np.zeros(cap, SUMMIT_DTYPE)
+            rc = lib().topo_summits_read(self._h, _p(p), _p(out), cap, C.byref(n))
+        if rc != TOPO_ERR_CAPACITY:
+            self._check(rc)
+        return out[:min(cap, n.value)], int(n.value)
+
+    def summit_snap_device(self, lonlat_ptr: int, n: int, radius_m: float, out_ptr: int):
+        """topo_summit_snap_device: n (lon, lat) pairs in degrees at lonlat_ptr -> n SUMMIT_SNAP_DTYPE records at out_ptr (device
+        memory, 16-byte aligned); queued on the context's stream."""
+        self._check(lib().topo_summit_snap_device(self._h, n, C.c_void_p(lonlat_ptr) if lonlat_ptr else None, radius_m, C.c_void_p(out_ptr) if out_ptr else None))
+
+    def summit_snap(self, lonlat, radius_m: float):
+        """topo_summit_snap_read: (n, 2) lon / lat degrees -> SUMMIT_SNAP_DTYPE records; waits."""
+        p = np.ascontiguousarray(lonlat, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros(len(p), SUMMIT_SNAP_DTYPE)
+        self._check(lib().topo_summit_snap_read(self._h, len(p), _p(p) if len(p) else None, radius_m, _p(out) if len(p) else None))
+        return out
+
+    def debug_set_summit_band_rows(self, rows: int):
+        """Test hook: the band height of the summit calls in vertex rows; 0: the default."""
+        self._check(lib().topo_debug_set_summit_band_rows(self._h, rows))
+
+    def debug_summit_counts(self):
+        """Test accessor: {"candidates", "summits"} of the last summit call; waits."""
+        out = np.zeros(2, np.uint64)
+        self._check(lib().topo_debug_summit_counts(self._h, _p(out)))
+        return {"candidates": int(out[0]), "summits": int(out[1])}
 
     # sun exposure: a day of sun and shadow over points of the drawn terrain (include/topo_hip.h); no submission needed
     def sun_exposure_grid_device(self, suns, lon0: float, lat0: float, dlon: float, dlat: float, nx: int, ny: int, lit_ptr: int = 0, shadow_ptr: int = 0,

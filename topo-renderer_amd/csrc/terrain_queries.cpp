@@ -4,9 +4,11 @@
 #include "topo_labels.h"
 #include "topo_surface.h"
 #include "topo_skyline.h"
+#include "topo_summits.h"
 #include "topo_sun.h"
 #include "topo_visibility.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -28,6 +30,10 @@ static_assert(kSkyNone == TOPO_SKY_NONE && kSkyTerrain == TOPO_SKY_TERRAIN && kS
 static_assert(sizeof(SunDir) == sizeof(topo_sun) && sizeof(topo_sun) == 32, "sun layout");
 static_assert(kSunNone == TOPO_SUN_NONE && kSunLit == TOPO_SUN_LIT && kSunAway == TOPO_SUN_AWAY && kSunShadow == TOPO_SUN_SHADOW && kSunNight == TOPO_SUN_NIGHT, "sun classes");
 static_assert(sizeof(LabelRec) == sizeof(topo_label) && sizeof(topo_label) == 32 && sizeof(topo_label_params) == 16, "label layouts");
+static_assert(sizeof(SummitRec) == sizeof(topo_summit) && sizeof(topo_summit) == 64 && sizeof(SummitSnapRec) == sizeof(topo_summit_snap) && sizeof(topo_summit_snap) == 48 &&
+                  sizeof(topo_summit_params) == 24, "summit layouts");
+static_assert(kSnapFound == TOPO_SNAP_FOUND && kSnapNone == TOPO_SNAP_NONE && kSnapInvalid == TOPO_SNAP_INVALID && kSummitOrderTile == TOPO_SUMMIT_ORDER_TILE &&
+                  kSummitOrderHeight == TOPO_SUMMIT_ORDER_HEIGHT && kSummitOrderIsolation == TOPO_SUMMIT_ORDER_ISOLATION, "summit constants");
 static_assert(kTileSphereDoubles == kLosSphereDoubles, "the cull prefilter and the rays read the same spheres: one gather, one layout");
 
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
@@ -638,6 +644,141 @@ int TerrainRenderer::skyline_read(uint32_t n_observers, const topo_observer* obs
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
     if (elevation) TOPO_HIP_TRY(hipMemcpy(elevation, query_.d_sky_elevation.p, n * sizeof(float), hipMemcpyDeviceToHost));
     if (samples) TOPO_HIP_TRY(hipMemcpy(samples, query_.d_sky_samples.p, n * sizeof(SkySample), hipMemcpyDeviceToHost));
+    return query_fold_check();
+}
+
+// ---- summits --------------------------------------------------------------------------------------------------------------------
+
+int TerrainRenderer::summits_check(const topo_summit_params* params, bool device) {
+    if (!params) return fail(TOPO_ERR_INVALID, "null argument");
+    if (!(std::isfinite(params->radius_m) && params->radius_m > 0.0 && params->radius_m <= kSummitMaxRadius)) return fail(TOPO_ERR_INVALID, "radius_m must be finite and lie in (0, 1e6]");
+    if (!(params->min_isolation_m >= 0.0 && params->min_isolation_m <= params->radius_m)) return fail(TOPO_ERR_INVALID, "min_isolation_m must lie in 0 .. radius_m");
+    if (std::isnan(params->min_height_m)) return fail(TOPO_ERR_INVALID, "min_height_m must not be NaN");
+    if (params->order > kSummitOrderIsolation) return fail(TOPO_ERR_INVALID, "unknown order");
+    if (device && params->order != kSummitOrderTile) return fail(TOPO_ERR_INVALID, "the device variant writes tile order only");
+    return TOPO_OK;
+}
+
+// The bands of every tile, in tile order, on stream_: the first min(count, capacity) records to out_dev, the count to count_dev.  The
+// scratch is one band's (topo_kernels.h: SummitScratch), carved out of one buffer; the state record lies in front of it.
+int TerrainRenderer::summits_launch(const topo_summit_params& params, SummitRec* out_dev, uint32_t capacity, uint32_t* count_dev) {
+    const uint32_t n_tiles = (uint32_t)tiles_.size();
+    const uint32_t fit = std::max(1u, kSummitBandPosts / std::max(1u, tile_w_));
+    const uint32_t band = std::min(tile_h_, summit_band_rows_ ? summit_band_rows_ : fit);
+    const size_t posts = (size_t)band * tile_w_, waves = (size_t)band * ((tile_w_ + 63) / 64);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_mask = up(kSummitStateWords * sizeof(uint32_t)), o_count = o_mask + up(waves * 8), o_cand = o_count + up(waves * 4), o_keep = o_cand + up(posts * 4),
+                 total = o_keep + up(posts);
+    if (int rc = ensure(stream_, query_.d_summit_scratch, total)) return rc;
+    uint8_t* const base = query_.d_summit_scratch.as<uint8_t>();
+    const SummitScratch x{(uint64_t*)(base + o_mask), (uint32_t*)(base + o_count), (uint32_t*)(base + o_cand), base + o_keep, (uint32_t*)base, (uint32_t)posts, (uint32_t)waves};
+    TOPO_HIP_TRY(hipMemsetAsync(x.state, 0, kSummitStateWords * sizeof(uint32_t), stream_));
+    const RayParams p = ray_params();
+    const SummitCall c{params.radius_m, params.min_isolation_m, params.min_height_m};
+    for (uint32_t rank = 0; rank < n_tiles; ++rank)
+        for (uint32_t y0 = 0; y0 < tile_h_; y0 += band) launch_summits_band(p, c, rank, y0, std::min(band, tile_h_ - y0), x, out_dev, capacity, stream_);
+    launch_summits_finish(p, c, x, out_dev, capacity, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipMemcpyAsync(count_dev, x.state + kSummitStateTotal, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream_));      // (the summits so far: all of them)
+    return TOPO_OK;
+}
+
+// Device variant: queued on stream_, in order.
+int TerrainRenderer::summits_device(const topo_summit_params* params, topo_summit* out_dev, uint32_t capacity, uint32_t* count_dev) {
+    if (int rc = summits_check(params, true)) return rc;
+    if (!count_dev || (!out_dev && capacity)) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)out_dev % 16 != 0 || (uintptr_t)count_dev % 4 != 0) return fail(TOPO_ERR_INVALID, "out_dev must be 16-byte and count_dev 4-byte aligned");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    if (tiles_.empty()) {
+        TOPO_HIP_TRY(hipMemsetAsync(count_dev, 0, sizeof(uint32_t), stream_));
+        return TOPO_OK;
+    }
+    return summits_launch(*params, (SummitRec*)out_dev, capacity, count_dev);
+}
+
+// Host read.  The caller's memory is pageable, so nothing is staged (as topo_skyline_read): the records come down with a blocking copy
+// once the stream has finished.  The full set is needed to order it, so the call runs into a buffer of its own, sized by a first run's
+// count when the records of that run did not fit.
+int TerrainRenderer::summits_read(const topo_summit_params* params, topo_summit* out, uint32_t capacity, uint32_t* count) {
+    if (int rc = summits_check(params, false)) return rc;
+    if (!count || (!out && capacity)) return fail(TOPO_ERR_INVALID, "null argument");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    *count = 0;
+    if (tiles_.empty()) return TOPO_OK;
+    if (int rc = ensure(stream_, query_.d_summit_count, 16)) return rc;
+    uint32_t room = std::max(capacity, 1u << 16), found = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (int rc = ensure(stream_, query_.d_summit_out, (size_t)room * sizeof(SummitRec))) return rc;
+        if (int rc = summits_launch(*params, query_.d_summit_out.as<SummitRec>(), room, query_.d_summit_count.as<uint32_t>())) return rc;
+        TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+        TOPO_HIP_TRY(hipMemcpy(&found, query_.d_summit_count.p, sizeof found, hipMemcpyDeviceToHost));
+        if (found <= room) break;
+        room = found;
+    }
+    std::vector<topo_summit> all(found);
+    if (found) TOPO_HIP_TRY(hipMemcpy(all.data(), query_.d_summit_out.p, (size_t)found * sizeof(topo_summit), hipMemcpyDeviceToHost));
+    if (int rc = query_fold_check()) return rc;
+    // (stable: ties stay in tile order)
+    if (params->order == kSummitOrderHeight)
+        std::stable_sort(all.begin(), all.end(), [](const topo_summit& a, const topo_summit& b) { return a.height_m > b.height_m; });
+    else if (params->order == kSummitOrderIsolation)
+        std::stable_sort(all.begin(), all.end(), [](const topo_summit& a, const topo_summit& b) {
+            return a.isolation_m > b.isolation_m || (a.isolation_m == b.isolation_m && a.height_m > b.height_m);
+        });
+    *count = found;
+    if (std::min(found, capacity)) std::memcpy(out, all.data(), (size_t)std::min(found, capacity) * sizeof(topo_summit));
+    if (found > capacity) return fail(TOPO_ERR_CAPACITY, "more summits than capacity: *count says how many");
+    return TOPO_OK;
+}
+
+// What the last summit call counted (summits_launch's state record): candidates after the prefilter, summits.
+int TerrainRenderer::summit_counts(uint64_t out[2]) {
+    if (!out) return fail(TOPO_ERR_INVALID, "null argument");
+    out[0] = out[1] = 0;
+    if (!query_.d_summit_scratch.p) return TOPO_OK;
+    if (int rc = bind_device()) return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    uint32_t w[kSummitStateWords];
+    TOPO_HIP_TRY(hipMemcpy(w, query_.d_summit_scratch.p, sizeof w, hipMemcpyDeviceToHost));
+    out[0] = w[kSummitStateSeen];
+    out[1] = w[kSummitStateTotal];
+    return TOPO_OK;
+}
+
+static const char* snap_radius_error(double radius_m) {
+    return std::isfinite(radius_m) && radius_m > 0.0 && radius_m <= kSummitMaxRadius ? nullptr : "radius_m must be finite and lie in (0, 1e6]";
+}
+
+int TerrainRenderer::summit_snap_device(uint32_t n, const double* lonlat_dev, double radius_m, topo_summit_snap* out_dev) {
+    if (const char* why = snap_radius_error(radius_m)) return fail(TOPO_ERR_INVALID, why);
+    if (n == 0) return TOPO_OK;
+    if (!lonlat_dev || !out_dev) return fail(TOPO_ERR_INVALID, "null argument");
+    if ((uintptr_t)lonlat_dev % 16 != 0 || (uintptr_t)out_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "lonlat_dev and out_dev must be 16-byte aligned");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    launch_summit_snap(ray_params(), lonlat_dev, radius_m, (SummitSnapRec*)out_dev, n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Host read: nothing is staged (as topo_visibility_read): blocking copies around the kernel.
+int TerrainRenderer::summit_snap_read(uint32_t n, const double* lonlat_deg, double radius_m, topo_summit_snap* out) {
+    if (const char* why = snap_radius_error(radius_m)) return fail(TOPO_ERR_INVALID, why);
+    if (n == 0) return TOPO_OK;
+    if (!lonlat_deg || !out) return fail(TOPO_ERR_INVALID, "null argument");
+    if (int rc = bind_device()) return rc;
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    const size_t in_bytes = (size_t)n * 2 * sizeof(double), out_bytes = (size_t)n * sizeof(SummitSnapRec);
+    if (int rc = ensure(stream_, query_.d_surface_in, in_bytes)) return rc;
+    if (int rc = ensure(stream_, query_.d_summit_out, out_bytes)) return rc;
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    TOPO_HIP_TRY(hipMemcpy(query_.d_surface_in.p, lonlat_deg, in_bytes, hipMemcpyHostToDevice));
+    launch_summit_snap(ray_params(), query_.d_surface_in.as<const double>(), radius_m, query_.d_summit_out.as<SummitSnapRec>(), n, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    TOPO_HIP_TRY(hipMemcpy(out, query_.d_summit_out.p, out_bytes, hipMemcpyDeviceToHost));
     return query_fold_check();
 }
 

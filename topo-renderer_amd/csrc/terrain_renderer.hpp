@@ -204,6 +204,14 @@ class TerrainRenderer {
     int labels_read(const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t w, uint32_t h, const float* depth_dev, size_t depth_view_stride,
                     size_t depth_pitch, uint32_t n_peaks, const float* peaks, const float* widths, topo_label* labels, uint32_t* counts, uint8_t* state);
 
+    // summits: the posts of the resident DEMs no higher post stands near, and the best post around a point (topo_summits_*, topo_summit_snap_*): no submission needed
+    int summits_device(const topo_summit_params* params, topo_summit* out_dev, uint32_t capacity, uint32_t* count_dev);
+    int summits_read(const topo_summit_params* params, topo_summit* out, uint32_t capacity, uint32_t* count);
+    int summit_snap_device(uint32_t n, const double* lonlat_dev, double radius_m, topo_summit_snap* out_dev);
+    int summit_snap_read(uint32_t n, const double* lonlat_deg, double radius_m, topo_summit_snap* out);
+    int set_summit_band_rows(uint32_t rows) { summit_band_rows_ = rows; return TOPO_OK; }      // test hook: 0 = the default
+    int summit_counts(uint64_t out[2]);                                                         // test accessor
+
     // unwrap: finished views that share an eye as one azimuth / elevation image (topo_unwrap_device)
     int unwrap_device(const topo_unwrap_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t src_w, uint32_t src_h, const OutputParams& src,
                       const OutputParams& out, int32_t* src_out_dev, size_t src_out_pitch);
@@ -389,10 +397,11 @@ class TerrainRenderer {
     // as resolved -- the skyline calls' too --, a visibility read's classes, a skyline read's elevations and records, the sun exposure calls' suns and a sun exposure read's masks and exposures), and the device
     // copy of k_unwrap's f64 tables (topo_unwrap.h), kept for what they were built from -- the call's parameters, the views'
     // direction blocks and the eye (unwrap_key) -- with their host copy, the source of the upload; likewise the device table of the
-    // label calls' view matrices with its host copy (label_projs: key and source of the upload), and a label read's inputs and outputs
+    // label calls' view matrices with its host copy (label_projs: key and source of the upload), and a label read's inputs and outputs;
+    // the summit calls' scratch (one band: topo_kernels.h) with their state record, and a summit read's records and count
     struct QueryBuffers {
         DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_surface_in, d_surface_out, d_profile_samples, d_vis_observers, d_vis_eyes, d_vis_out,
-            d_sky_elevation, d_sky_samples, d_suns, d_sun_lit, d_sun_shadow, d_sun_exposure, d_unwrap_tab, d_label_projs, d_label_in, d_label_out;
+            d_sky_elevation, d_sky_samples, d_suns, d_sun_lit, d_sun_shadow, d_sun_exposure, d_unwrap_tab, d_label_projs, d_label_in, d_label_out, d_summit_scratch, d_summit_out, d_summit_count;
         PinnedBuffer h_ray_stage, h_surface_stage;
         std::vector<double> unwrap_tab;
         std::vector<uint8_t> unwrap_key;
@@ -414,6 +423,9 @@ class TerrainRenderer {
     int resolve_observers(uint32_t n_observers, const topo_observer* observers);      // the tables, and the observers resolved into d_vis_eyes on stream_
     int skyline_check(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m);
     int sun_begin(uint32_t n_suns, const topo_sun* suns);      // checks, the tables, and the suns normalised into d_suns on stream_
+    int summits_check(const topo_summit_params* params, bool device);      // what both summit calls refuse (their outputs apart)
+    int summits_launch(const topo_summit_params& params, SummitRec* out_dev, uint32_t capacity, uint32_t* count_dev);      // the tables are prepared; queues the bands on stream_
+    uint32_t summit_band_rows_ = 0;
     int labels_check(const topo_label_params* params, uint32_t n_views, const topo_uniforms* views, uint32_t w, uint32_t h, const float* depth_dev, size_t depth_view_stride,
                      size_t depth_pitch);      // what both label calls refuse, before anything is queued
 

@@ -523,6 +523,36 @@ int topo_labels_read(topo_ctx* ctx, const topo_label_params* params, uint32_t n_
     TOPO_CALL(ctx->r->labels_read(params, n_views, views, width, height, depth_dev, depth_view_stride, depth_pitch, n_peaks, peaks_xyz, widths, labels, counts, state));
 }
 
+int topo_summits_device(topo_ctx* ctx, const topo_summit_params* params, topo_summit* out_dev, uint32_t capacity, uint32_t* count_dev) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->summits_device(params, out_dev, capacity, count_dev));
+}
+
+int topo_summits_read(topo_ctx* ctx, const topo_summit_params* params, topo_summit* out, uint32_t capacity, uint32_t* count) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->summits_read(params, out, capacity, count));
+}
+
+int topo_summit_snap_device(topo_ctx* ctx, uint32_t n, const double* lonlat_dev, double radius_m, topo_summit_snap* out_dev) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->summit_snap_device(n, lonlat_dev, radius_m, out_dev));
+}
+
+int topo_summit_snap_read(topo_ctx* ctx, uint32_t n, const double* lonlat_deg, double radius_m, topo_summit_snap* out) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->summit_snap_read(n, lonlat_deg, radius_m, out));
+}
+
+int topo_debug_set_summit_band_rows(topo_ctx* ctx, uint32_t rows) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->set_summit_band_rows(rows));
+}
+
+int topo_debug_summit_counts(topo_ctx* ctx, uint64_t out[2]) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->summit_counts(out));
+}
+
 void topo_ecef_from_lonlat(double lon_deg, double lat_deg, double height_m, double out[3]) {
     if (!out) return;
     double u[3];

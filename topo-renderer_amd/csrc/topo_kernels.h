@@ -353,6 +353,46 @@ struct UnwrapParams {
 };
 void launch_unwrap(const UnwrapParams& p, bool bilinear, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
+// summits (topo_summits_*, topo_summit_snap_*): the posts of the resident DEMs no higher post stands near, and the best post around a
+// point (topo_summits.h); needs no submission.  Reads what the rays read (RayParams); writes only its scratch and its outputs.
+struct SummitRec {         // = topo_summit (64 bytes)
+    double lon_deg, lat_deg, isolation_m;
+    float height_m, higher_height_m;
+    int32_t tile_lat, tile_lon;
+    uint32_t vx, vy;
+    int32_t higher_tile_lat, higher_tile_lon;
+    uint32_t higher_vx, higher_vy;
+};
+struct SummitSnapRec {     // = topo_summit_snap (48 bytes)
+    double lon_deg, lat_deg, distance_m;
+    float height_m;
+    int32_t status;
+    int32_t tile_lat, tile_lon;
+    uint32_t vx, vy;
+};
+struct SummitCall {
+    double radius, min_isolation;
+    float min_height;
+};
+// The scratch of one band of at most `posts` posts in `waves` waves (rows * ceil(tile_w / 64)): 5 bytes per post, 12 per wave.
+constexpr uint32_t kSummitBandPosts = 1u << 22;      // the default band: as many whole rows as hold at most this many posts (one row at least) -- 20 MiB + 1.5 MiB of scratch
+// the words of the state record: the band's candidates and survivors, the call's summits so far, the number of the band's first
+// summit, the call's candidates so far (topo_debug_summit_counts)
+constexpr uint32_t kSummitStateCandidates = 0, kSummitStateSurvivors = 1, kSummitStateTotal = 2, kSummitStateBase = 3, kSummitStateSeen = 4;
+constexpr uint32_t kSummitStateWords = 8;            // candidates and survivors of the band, summits so far, the band's first record, candidates so far
+struct SummitScratch {
+    uint64_t* wave_mask;     // waves
+    uint32_t* wave_count;    // waves
+    uint32_t* candidates;    // posts: post indices of the band's tile, ascending
+    uint8_t* keep;           // posts
+    uint32_t* state;         // kSummitStateWords, zero at the start of a call
+    uint32_t posts, waves;   // what the lists above have room for: the kernels' index checks are against these
+};
+void launch_summits_band(const RayParams& p, const SummitCall& c, uint32_t rank, uint32_t y0, uint32_t rows, const SummitScratch& x, SummitRec* out, uint32_t capacity,
+                         hipStream_t s);
+void launch_summits_finish(const RayParams& p, const SummitCall& c, const SummitScratch& x, SummitRec* out, uint32_t capacity, hipStream_t s);      // once, behind the last band
+void launch_summit_snap(const RayParams& p, const double* lonlat, double radius, SummitSnapRec* out, uint32_t n, hipStream_t s);      // a wave per point
+
 // overlay pass (line_shader.wgsl over the post pass's image): keys = W*H overlay keys, (re-)initialised when keys_fresh
 void launch_overlay(const OverlayVertex* verts, const uint32_t* idx, uint32_t n_tris, uint32_t n_verts, float width, int32_t W, int32_t H, uint64_t* keys,
                     bool keys_fresh, uint8_t* rgba, size_t pitch, uint32_t linear_target, uint32_t bgra, hipStream_t s);
