@@ -39,6 +39,16 @@ int topo_debug_cull_pairs(topo_ctx* ctx, uint32_t out[2]);
  * every submission (by default only submissions of more than 2^25 pixels take it). */
 int topo_debug_cover_stats(topo_ctx* ctx, uint32_t out[3]);
 
+/* Test hooks of the owned strips.  k_raster_cover leaves a record for each of the eight 64 x 8 px strips of a region it draws; k_resolve
+ * takes a strip whose record is this frame's and all of whose pixels inside the target the region's owner has won straight from that
+ * record (no listing of winners, no record pass).  The path follows the covered regions' switch (TOPO_COVER);
+ * TOPO_RESOLVE_OWNED=0 in the environment switches it alone off, as does on = 0 here, from the next submission on.
+ * topo_debug_owned_strips (waits for the last frame, counts on the host from its keys and the table): out[0] = strips that pass the
+ * ownership test, out[1] = strips with a record of this frame (8 per claimed region, fewer where the target's lower edge cuts it).
+ * Both 0 when the path is off. */
+int topo_debug_set_resolve_owned(topo_ctx* ctx, int32_t on);
+int topo_debug_owned_strips(topo_ctx* ctx, uint32_t out[2]);
+
 /* Test accessor: what the last submission's cull and occlusion test decided (waits for it).  Count, then fill: counts_out[0..2] =
  * entries of the near work list, of the far candidates (the sub-lists one behind the other) and of the far survivors; [3], [4] = the
  * frame's far_tested and far_survived counters.  near_out / survivors_out: 2 words per entry (view << 16 | tile rank, block | first

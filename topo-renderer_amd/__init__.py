@@ -150,6 +150,8 @@ def lib():
             "topo_debug_set_tile_prefilter": (C.c_int, [vp, i32]),
             "topo_debug_cull_pairs": (C.c_int, [vp, vp]),
             "topo_debug_cover_stats": (C.c_int, [vp, vp]),
+            "topo_debug_set_resolve_owned": (C.c_int, [vp, i32]),
+            "topo_debug_owned_strips": (C.c_int, [vp, vp]),
             "topo_debug_read_cull_lists": (C.c_int, [vp, vp, u32, vp, u32, vp, u32, vp]),
             "topo_pin_host_buffer": (C.c_int, [vp, vp, sz]),
             "topo_unpin_host_buffer": (C.c_int, [vp, vp]),
@@ -770,6 +772,16 @@ class TerrainRenderer:
         out = np.zeros(3, np.uint32)
         self._check(lib().topo_debug_cover_stats(self._h, _p(out)))
         return {"candidates": int(out[0]), "won": int(out[1]), "lost": int(out[2])}
+
+    def debug_set_resolve_owned(self, on: bool):
+        """k_resolve's owned-strip path on / off, from the next submission on (include/topo_hip_test.h)."""
+        self._check(lib().topo_debug_set_resolve_owned(self._h, 1 if on else 0))
+
+    def debug_owned_strips(self) -> dict:
+        """The last frame's strips that pass k_resolve's ownership test, and its strips with a record of the frame (include/topo_hip_test.h)."""
+        out = np.zeros(2, np.uint32)
+        self._check(lib().topo_debug_owned_strips(self._h, _p(out)))
+        return {"owned": int(out[0]), "marked": int(out[1])}
 
     def debug_read_cull_lists(self) -> dict:
         """What the last frame's cull and occlusion test decided (topo_debug_read_cull_lists, test hook; pipeline depth 1): the near

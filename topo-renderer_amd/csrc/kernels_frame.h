@@ -795,6 +795,35 @@ __global__ __launch_bounds__(256) void k_raster_rare(FrameParams P, CoverParams 
 // flight before the walk uses the first.  (A neighbouring region's workgroup may be marking a shared segment meanwhile: read as 0 or
 // as 1, the result is the same -- the neighbour writes none of this region's pixels.)  Plain stores, not non-temporal ones: k_raster_big
 // and k_resolve read the keys again soon.  The walk is big_cover_lane (topo_pipeline.h), run lane by lane on the CPU in the tests.
+//
+// The region's first wave also leaves k_resolve the records of the region's strips (CoverParams::recs): lane s < 8 takes the strip of
+// rows 8 s .. 8 s + 7, if it starts inside the target, and evaluates resolve_setup for the owner at the strip's origin -- the function
+// and the arguments of k_resolve's record pass for that strip (without its LDS table of the normal decode: normal_channel itself,
+// which is what fills the table), so the 34 words are the ones that pass would compute -- and stores them with the owner's id and the
+// frame's serial.  It does so in front of everything that can end the wave early; the other three waves go straight to their rows.
+// (Kept here, not among k_raster_big's waves that skip a won item: DESIGN 5, "Owned strips".)
+__device__ __forceinline__ void cover_strip_record(const FrameParams& P, const CoverParams& C, uint32_t id, uint32_t view, int32_t rx, int32_t ry, uint32_t strip) {
+    const int32_t x = rx * 64, y = ry * 64 + (int32_t)(strip * kOwnedStripRows);
+    if (strip >= kOwnedStrips || y >= P.H) return;
+    const uint32_t draw = id >> 1, fan = id & 1u;
+    const uint32_t rank = fastdiv(draw, P.div_tris), tri = draw - rank * P.tris_per_tile;
+    const size_t at = owned_record_index(C.regions_x, C.regions_y, view, x, y);
+    if (!TOPO_CHK(P.counters, rank < P.n_tiles && at < (size_t)C.cap * kOwnedStrips, 37u, at)) return;
+    TriRecord rec;
+    resolve_setup<false>(P.tiles[rank], P.tile_w, P.div_hm1, P.tile_h - 1, P.views[view], P.W, P.H, tri, fan, nullptr, x, y, rec);
+    uint32_t w[kOwnedRecWords];
+    int k = 0;
+#define TOPO_X(f) w[k++] = rec.f;
+    TOPO_TRIREC_WORDS(TOPO_X)
+#undef TOPO_X
+    static_assert(kTriRecordWords == (int)kOwnedIdWord && kOwnedSerialWord + 1 == kOwnedRecWords && kOwnedRecWords % 4 == 0, "a record is the TriRecord, the id, the serial");
+    w[kOwnedIdWord] = id;
+    w[kOwnedSerialWord] = C.serial;
+    uint4* const dst = reinterpret_cast<uint4*>(C.recs + at * kOwnedRecWords);
+#pragma unroll
+    for (int q = 0; q < (int)kOwnedRecWords / 4; ++q) dst[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+}
+
 constexpr int kCoverRows = 16;
 __global__ __launch_bounds__(256) void k_raster_cover(FrameParams P, CoverParams C) {
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -816,6 +845,7 @@ __global__ __launch_bounds__(256) void k_raster_cover(FrameParams P, CoverParams
         const int32_t rx = (int32_t)(bi.region & 0xFFFFu), ry = (int32_t)(bi.region >> 16);
         if (!TOPO_CHK(P.counters, (bi.view & kBigCovered) && bi.id != kNoTri && view < P.n_views && rx * 64 < P.W && ry * 64 < P.H &&
                                       cover_region_index(C, view, rx, ry) == region, 33u, bi.region)) continue;
+        if (C.recs && wave == 0u) cover_strip_record(P, C, bi.id, view, rx, ry, lane);
         SVert s[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) { s[k].X = bi.X[k]; s[k].Y = bi.Y[k]; s[k].z = bi.z[k]; s[k].flag = kVtxOk; }

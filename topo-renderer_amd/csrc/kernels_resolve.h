@@ -156,6 +156,7 @@ __device__ __forceinline__ void resolve_fill_sky(const FrameParams& P, const Out
 struct ResolveArgs {             // k_resolve's parameter list as the argument segment lays it out
     FrameParams P;
     OutputParams O;
+    CoverParams C;
 };
 // A wave-uniform constant-address-space object behind a pointer the compiler cannot prove to be the same from one call to the
 // next: fields read through it are loaded (s_load, scalar cache) where they are used, instead of being loaded once and held in
@@ -170,7 +171,7 @@ __device__ __forceinline__ const ResolveArgs& resolve_args() {
 }
 
 template <bool kSrgb, bool kBgra>
-__global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P, OutputParams O) {
+__global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P, OutputParams O, CoverParams C) {
     __shared__ float s_thresh[258];    // sRGB code boundaries; [255..257] = NaN: never <= anything (srgb_encode_lut probes up to 256)
     __shared__ float s_decode[256];
     __shared__ float s_ndec[256];      // normal channel decode 2c/255 - 1
@@ -180,6 +181,7 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
     // LDS operations instead of the 34 / 17 four- and eight-byte ones of the round-2 layout (word-major)
     constexpr int kRecStride = (kTriRecordWords + 3) & ~3;
     __shared__ __attribute__((aligned(16))) uint32_t s_rec[4][kRecCap][kRecStride];
+    static_assert(kRecStride == (int)kOwnedRecWords && kRPW == (int)kOwnedStripRows, "a record of CoverParams::recs is a strip's record as it lies here");
     __shared__ uint32_t s_uid[4][kRecCap];                   // per wave: the distinct winner ids of a group of rows
     __shared__ uint8_t s_slot[4][kRPW][64];                  // per wave and pixel: the number of its entry among the strip's table entries (0xFF: none)
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -244,6 +246,20 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
             const FrameParams& P = resolve_args().P;
             const OutputParams& O = resolve_args().O;
             resolve_load_keys(P, block_of(P, j_cur), lane, wave, K);
+            // Owned strips.  A strip of a region that one near-field giant has claimed (k_raster_cover) has a record in the frame's
+            // table (CoverParams::recs): the owner's TriRecord at this strip's origin, its id, the frame's serial.  Lanes 0 .. 8 read
+            // one 16-byte chunk of it each, under the keys' trip; if it carries this frame's serial and every pixel of the strip
+            // inside the target has the owner's id, the strip has ONE winner and its record is at hand: no listing, no record pass.
+            // (No table or serial 0: the path is off, at the price of this wave-uniform test.)
+            const bool recs_on = resolve_args().C.recs != nullptr && resolve_args().C.serial != 0u;
+            uint4 own = make_uint4(0u, 0u, 0u, 0u);
+            if (recs_on) {
+                const CoverParams& C = resolve_args().C;
+                const ResolveBlock Bo = block_of(P, j_cur);
+                const size_t at = owned_record_index(C.regions_x, C.regions_y, Bo.view, Bo.bx, Bo.by + sy0);
+                if (TOPO_CHK(P.counters, at < (size_t)C.cap * kOwnedStrips, 38u, at))
+                    own = reinterpret_cast<const uint4*>(C.recs + at * kOwnedRecWords)[lane < kOwnedRecWords / 4 ? lane : kOwnedRecWords / 4 - 1u];
+            }
             // (this strip's share of the untouched strips -- pure stores -- goes out under the keys' trip to memory)
             for (uint32_t f = 0; f < fills_per_iter && mc; ++f) resolve_fill_sky<kBgra>(P, O, block_of(P, pop_bit(mc)), lane, wave);
             const ResolveBlock B = block_of(P, j_cur);
@@ -276,6 +292,25 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
                     TOPO_ROWS(TOPO_X)
 #undef TOPO_X
                 }
+                bool owned = false;
+                if (recs_on) {       // words 34 and 35 are in lane 8's chunk
+                    const uint32_t o_id = (uint32_t)__builtin_amdgcn_readlane((int)own.z, (int)kOwnedRecWords / 4 - 1);
+                    const uint32_t o_serial = (uint32_t)__builtin_amdgcn_readlane((int)own.w, (int)kOwnedRecWords / 4 - 1);
+                    bool other = false;
+#define TOPO_X(r, m) other |= r < n_rows && K.id.m != o_id;
+                    TOPO_ROWS(TOPO_X)
+#undef TOPO_X
+                    owned = o_serial == resolve_args().C.serial && __ballot(in_x && other) == 0ull;
+                }
+                if (owned) {
+                    // entry 0 for every pixel, the table's record 0 = the strip's record as it came; n_all stays 0, so the group loop
+                    // below takes all rows as one group from the table and finds no record to compute (cnt = 0)
+                    const uint8_t sl = in_x ? (uint8_t)0u : (uint8_t)0xFFu;
+#define TOPO_X(r, m) slot_tile[r][tx] = sl;
+                    TOPO_ROWS(TOPO_X)
+#undef TOPO_X
+                    if (lane < kOwnedRecWords / 4) *reinterpret_cast<uint4*>(&s_rec[wave][0][4 * lane]) = own;
+                } else {
                 // ---- the distinct winners of this wave's pixels: a lane opens an entry where its id differs from its left
                 // neighbour's.  Entries are numbered over the strip's rows that are shaded from the table (rows with at most kRecCap
                 // entries, while the numbers fit a byte); n_row = entries of a row.  A pixel's entry number waits in LDS.
@@ -296,6 +331,7 @@ __global__ __launch_bounds__(256, TOPO_RESOLVE_WGS) void k_resolve(FrameParams P
     }
                 TOPO_ROWS(TOPO_X)
 #undef TOPO_X
+                }
                 wave_lds_fence();
             }
             // ---- this strip's keys are consumed: the next strip's turn

@@ -26,6 +26,7 @@ struct Switches {
     const bool tile_prefilter = env("TOPO_TILE_PREFILTER", 1) != 0;
     const int near_strip = env("TOPO_NEAR_STRIP", 0);      // 1..15; anything else: the default
     const int cover = env("TOPO_COVER", -1);      // 0: off, 1: on for every submission; unset: on for the large ones (kCoverMinPixels)
+    const bool resolve_owned = env("TOPO_RESOLVE_OWNED", 1) != 0;      // the claimed regions' strip records (CoverParams::recs): follows the cover path; 0: off
 };
 const Switches& switches() { static const Switches s; return s; }
 
@@ -590,11 +591,19 @@ int TerrainRenderer::grow_frame_buffers(FrameCtx& c, hipStream_t stream, uint32_
         const size_t regions = (size_t)n * regions_x * regions_y;      // < 2^32 / 4096 words
         const bool fresh = regions * sizeof(uint64_t) > c.d_cover.cap;
         if (int rc = ensure(stream, c.d_cover, regions * sizeof(uint64_t))) return rc;
+        // the strip records of the claimed regions, for k_resolve: the owner words' lifetime, growth and discipline -- zeroed when
+        // fresh and when the serial wraps (a record of serial 0 never matches), never reset between frames (c4: 19 MB per context)
+        const size_t recs_bytes = regions * kOwnedStrips * kOwnedRecWords * sizeof(uint32_t);
+        const bool owned = resolve_owned_ && switches().resolve_owned;
+        const bool recs_fresh = owned && recs_bytes > c.d_cover_recs.cap;
+        if (owned)
+            if (int rc = ensure(stream, c.d_cover_recs, recs_bytes)) return rc;
+        if (recs_fresh || (c.d_cover_recs.p && c.cover_serial == 0xFFFFFFFFu)) TOPO_HIP_TRY(hipMemsetAsync(c.d_cover_recs.p, 0, c.d_cover_recs.cap, stream));
         if (fresh || c.cover_serial == 0xFFFFFFFFu) {
             TOPO_HIP_TRY(hipMemsetAsync(c.d_cover.p, 0, c.d_cover.cap, stream));
             c.cover_serial = 0;
         }
-        c.cover = CoverParams{c.d_cover.as<uint64_t>(), ++c.cover_serial, (uint32_t)regions, regions_x, regions_y};
+        c.cover = CoverParams{c.d_cover.as<uint64_t>(), ++c.cover_serial, (uint32_t)regions, regions_x, regions_y, owned ? c.d_cover_recs.as<uint32_t>() : nullptr};
         c.cover_big_cap = p.big_cap;
     }
     if (!c.d_counters.p) {
@@ -769,7 +778,7 @@ int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p
     if (n_slots == 0) {
         p.rblock_first = 0;
         p.rblock_count = p.rblocks_view * n;
-        launch_resolve(p, kout, stream, ev_rstart, ev_rstop);
+        launch_resolve(p, kout, c.cover, stream, ev_rstart, ev_rstop);
         if (pixelize)
             launch_post_pixelize(n, (int32_t)w, (int32_t)h, post_.viewport[0] >= 1.0f ? post_.viewport[0] : (float)w, post_.viewport[1] >= 1.0f ? post_.viewport[1] : (float)h,
                                  post_.pixelize_n, c.d_pre_rgba.as<const uint8_t>(), out, kout.depth, kout.depth_view_stride, kout.depth_pitch, p.linear_target, p.bgra, stream);
@@ -778,7 +787,7 @@ int TerrainRenderer::queue_frame(FrameCtx& c, hipStream_t stream, FrameParams& p
             if ((uint64_t)slots[i].block_first + slots[i].block_count > (uint64_t)p.rblocks_view * n) return fail(TOPO_ERR_INVALID, "resolve slot outside the frame");
             p.rblock_first = slots[i].block_first;
             p.rblock_count = slots[i].block_count;
-            launch_resolve(p, out, stream, i == 0 ? ev_rstart : nullptr, i + 1 == n_slots ? ev_rstop : nullptr);
+            launch_resolve(p, out, c.cover, stream, i == 0 ? ev_rstart : nullptr, i + 1 == n_slots ? ev_rstop : nullptr);
             if (after_slot)
                 if (int rc = (*after_slot)(i, stream)) return rc;
         }
@@ -1195,6 +1204,39 @@ int TerrainRenderer::cover_stats(uint32_t out[3]) {
     for (const BigItem& it : items) out[0] += it.id != kNoTri && (it.view & kBigCovered) ? 1u : 0u;
     for (uint64_t w : owner) out[1] += (uint32_t)(w >> 32) == cv.serial ? 1u : 0u;
     out[2] = out[0] - out[1];      // every covering item either wins its region or loses it to another one
+    return TOPO_OK;
+}
+
+// The strips of the last frame that k_resolve's ownership test accepts, and the strips whose record carries the frame's serial,
+// counted here from the keys and the table as the frame left them (the frame keeps no statistics).
+int TerrainRenderer::owned_strips(uint32_t out[2]) {
+    out[0] = out[1] = 0;
+    FrameCtx& fc = ctx_[last_ctx_];
+    if (!fc.h_status.p || !fc.submitted) return TOPO_OK;
+    if (int rc = bind_device()) return rc;
+    if (fc.last_stream) TOPO_HIP_TRY(hipStreamSynchronize(fc.last_stream));
+    const CoverParams& cv = fc.cover;
+    const HorizonParams& q = fc.sub.query;
+    if (!cv.serial || !cv.recs || !q.vis) return TOPO_OK;
+    const uint32_t W = q.W, H = q.H, n_views = fc.sub.n_views;
+    std::vector<uint32_t> recs((size_t)cv.cap * kOwnedStrips * kOwnedRecWords);
+    std::vector<uint64_t> keys((size_t)W * H);
+    if (!recs.empty()) TOPO_HIP_TRY(hipMemcpy(recs.data(), cv.recs, recs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t v = 0; v < n_views; ++v) {
+        TOPO_HIP_TRY(hipMemcpy(keys.data(), q.vis + (size_t)v * W * H, keys.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint32_t y = 0; y < H; y += kOwnedStripRows)
+            for (uint32_t x = 0; x < W; x += 64) {
+                const size_t at = owned_record_index(cv.regions_x, cv.regions_y, v, (int32_t)x, (int32_t)y);
+                if (at >= (size_t)cv.cap * kOwnedStrips) return fail(TOPO_ERR_INVALID, "a strip of the frame has no record in the table");
+                const uint32_t* rec = recs.data() + at * kOwnedRecWords;
+                if (rec[kOwnedSerialWord] != cv.serial) continue;
+                ++out[1];
+                bool same = true;
+                for (uint32_t py = y; py < std::min(y + kOwnedStripRows, H) && same; ++py)
+                    for (uint32_t px = x; px < std::min(x + 64u, W) && same; ++px) same = (uint32_t)keys[(size_t)py * W + px] == rec[kOwnedIdWord];
+                out[0] += same ? 1u : 0u;
+            }
+    }
     return TOPO_OK;
 }
 

@@ -134,6 +134,8 @@ class TerrainRenderer {
     int get_timing_history(uint32_t n_frames, float* out_ms, uint32_t* n_out);
     int get_counters(uint32_t out[6]);
     int cover_stats(uint32_t out[3]);      // test hook: the last frame's covering items, regions claimed, claims lost
+    void set_resolve_owned(bool on) { resolve_owned_ = on; }      // test hook: the claimed regions' strip records, from the next submission on
+    int owned_strips(uint32_t out[2]);     // test hook: the last frame's strips that pass k_resolve's ownership test, strips with a record of the frame
     int read_cull_lists(uint32_t* near_out, uint32_t near_room, uint32_t* far_out, uint32_t far_room, uint32_t* survivors_out, uint32_t survivors_room,
                         uint32_t counts_out[5]);      // test hook: the last frame's near items, far candidates, far survivors
     int frame_status(uint32_t out[4]);
@@ -296,6 +298,7 @@ class TerrainRenderer {
         DeviceBuffer d_vis, d_dirty;      // d_dirty: one mark per 64 visibility keys (kernels_common.h: struct Vis)
         DeviceBuffer d_work, d_work2, d_far, d_big, d_rare, d_counters;
         DeviceBuffer d_cover;             // the regions' owner words (topo_kernels.h: CoverParams)
+        DeviceBuffer d_cover_recs;        // ... and the records of the claimed regions' strips (CoverParams::recs)
         uint32_t cover_serial = 0;        // the serial the context's latest frame claimed regions with
         CoverParams cover{};              // this frame's; serial 0: the path is off
         uint32_t cover_big_cap = 0;       // ... and its big queue's capacity (the test hook reads the queue back)
@@ -362,6 +365,7 @@ class TerrainRenderer {
     // the cull's tile prefilter: on / off (the tiles' spheres: tile_spheres), the last submission's kept pairs (the launch copies
     // them) and its counts (pairs launched, pairs in all: test hook)
     bool tile_prefilter_ = true;
+    bool resolve_owned_ = true;      // topo_debug_set_resolve_owned
     uint16_t cull_codes_[kMaxCullPairs] = {};
     uint32_t last_cull_pairs_[2] = {0, 0};
     // viewshed: render_frame launches k_viewshed while vs_on_; the masks exist (every tile has one) once vs_ever_.  The masks are shared

@@ -154,6 +154,18 @@ int topo_debug_cover_stats(topo_ctx* ctx, uint32_t out[3]) {
     TOPO_CALL(ctx->r->cover_stats(out));
 }
 
+int topo_debug_set_resolve_owned(topo_ctx* ctx, int32_t on) {
+    TOPO_GUARD(ctx);
+    ctx->r->set_resolve_owned(on != 0);
+    return TOPO_OK;
+}
+
+int topo_debug_owned_strips(topo_ctx* ctx, uint32_t out[2]) {
+    TOPO_GUARD(ctx);
+    if (!out) return TOPO_ERR_INVALID;
+    TOPO_CALL(ctx->r->owned_strips(out));
+}
+
 int topo_debug_read_cull_lists(topo_ctx* ctx, uint32_t* near_out, uint32_t near_room, uint32_t* far_out, uint32_t far_room, uint32_t* survivors_out,
                                uint32_t survivors_room, uint32_t counts_out[5]) {
     TOPO_GUARD(ctx);

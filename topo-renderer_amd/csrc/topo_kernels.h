@@ -86,11 +86,17 @@ struct FrameParams {
 // context: `owner`, one 64-bit word per (view, 64 x 64 px region) of the submission -- the largest bid so far, serial of the frame
 // << 32 | big-queue index of the bidding item (atomicMax: a word of an older frame loses against any bid, so nothing has to be
 // reset between frames).  serial == 0: the path is off.
+// `recs`, beside them: the records of the claimed regions' strips (topo_pipeline.h: owned_record_index), 8 per region of
+// kOwnedRecWords words each, written by k_raster_cover for the regions this frame's serial won and read by k_resolve, which then
+// neither lists the winners of a strip all of whose pixels the owner has won nor computes its record again.  The same discipline:
+// zeroed once, a record carries its frame's serial and one of an older frame never matches.  Null: k_resolve takes every strip
+// the long way (TOPO_RESOLVE_OWNED=0).
 struct CoverParams {
     uint64_t* owner;
     uint32_t serial;
     uint32_t cap;              // words of owner: n_views * regions_x * regions_y
     uint32_t regions_x, regions_y;
+    uint32_t* recs;            // cap * 8 records, or null
 };
 
 struct OutputParams {
@@ -167,7 +173,8 @@ void launch_occlusion(const FrameParams& p, hipStream_t s);
 void launch_raster_rare(const FrameParams& p, const CoverParams& cover, hipStream_t s);      // cover.serial != 0 (the near phase only): covering items bid for their regions
 void launch_raster_cover(const FrameParams& p, const CoverParams& cover, hipStream_t s);     // between the near phase's launch_raster_rare and launch_raster_big
 void launch_raster_big(const FrameParams& p, const CoverParams& cover, hipStream_t s);          // cover: the near phase's, as passed to launch_raster_rare
-void launch_resolve(const FrameParams& p, const OutputParams& o, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// cover: the frame's (the strip records k_raster_cover left: CoverParams::recs); CoverParams{}: every strip the long way
+void launch_resolve(const FrameParams& p, const OutputParams& o, const CoverParams& cover, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // viewshed (topo_viewshed_*), behind the frame's last k_resolve: the DEM cells that won a pixel, OR-ed into per-tile bit masks.
 // masks: device table, rank -> the tile's mask (bit = cell = x (h-1) + y); stats: kViewshedStatSlots x 4 counters (k_viewshed).

@@ -221,7 +221,7 @@ void launch_raster_big(const FrameParams& p, const CoverParams& cover, hipStream
     hipLaunchKernelGGL(k_raster_big, dim3(grid), dim3(256), 0, s, p, cover);
 }
 
-void launch_resolve(const FrameParams& p, const OutputParams& o, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+void launch_resolve(const FrameParams& p, const OutputParams& o, const CoverParams& cover, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     const unsigned n_blocks = p.rblock_count;
     if (n_blocks == 0) return;
     // four times the resident workgroups: the hardware then hands out workgroups as others finish, which evens out what the
@@ -231,7 +231,7 @@ void launch_resolve(const FrameParams& p, const OutputParams& o, hipStream_t s, 
     if (const char* e = getenv("TOPO_RESOLVE_GRID")) resident = (unsigned)atoi(e) ? (unsigned)atoi(e) : n_blocks;      // experiments: 0 = one block per workgroup
     const dim3 grid(n_blocks < resident ? n_blocks : resident), block(256);
     const bool bgra = p.bgra && !p.post_off;      // (the render-target image of the pixelise path is always R G B A)
-    auto launch = [&](auto kernel) { launch_timed(kernel, grid, block, s, start, stop, p, o); };
+    auto launch = [&](auto kernel) { launch_timed(kernel, grid, block, s, start, stop, p, o, cover); };
     if (!p.linear_target && !bgra) launch(k_resolve<true, false>);
     else if (!p.linear_target) launch(k_resolve<true, true>);
     else if (!bgra) launch(k_resolve<false, false>);

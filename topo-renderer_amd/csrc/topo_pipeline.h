@@ -480,6 +480,18 @@ TOPO_HD bool item_covers_region(const int32_t X[3], const int32_t Y[3], int32_t 
     return triangle_setup(s[0], s[1], s[2], W, H, ts) && setup_covers_region(ts, W, H, rx, ry);
 }
 
+// The strip records of the claimed regions (topo_kernels.h: CoverParams::recs): a region is eight of k_resolve's 64 x 8 px strips
+// one below the other, and each has a record of kOwnedRecWords words in the table -- words 0 .. 33 the TriRecord of the region's
+// owner with the strip's origin as its reference pixel, word 34 the owner's id, word 35 the serial of the frame that wrote it.
+// owned_record_index: the record of the strip whose origin is pixel (x, y) of `view` (x a multiple of 64, y of 8), for
+// k_raster_cover, which writes it (x = 64 rx, y = 64 ry + 8 strip), and for k_resolve, which reads it (its block's column and the
+// wave's first row): region-major in cover_region_index's order, the strips of a region side by side.
+constexpr uint32_t kOwnedStrips = 8, kOwnedStripRows = 8, kOwnedRecWords = 36, kOwnedIdWord = 34, kOwnedSerialWord = 35;
+TOPO_HD size_t owned_record_index(uint32_t regions_x, uint32_t regions_y, uint32_t view, int32_t x, int32_t y) {
+    const size_t region = ((size_t)view * regions_y + (uint32_t)(y >> 6)) * regions_x + (uint32_t)(x >> 6);
+    return region * kOwnedStrips + (uint32_t)((y & 63) >> 3);
+}
+
 // k_raster_cover: the pixel walk of a triangle that covers region (rx, ry) (setup_covers_region) -- no edge tests.  Lane `lane`
 // owns pixel column rx * 64 + lane and walks the kRows rows from ry * 64 + row0 down; the depth is big_giant_lane's
 // (giant_depth of the same two integers, stepped by exact 64-bit additions: one row down = - 256 dx).  emit(pixel index, key,
