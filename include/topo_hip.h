@@ -710,6 +710,61 @@ int topo_summit_snap_device(topo_ctx* ctx, uint32_t n, const double* lonlat_dev,
 /* Host memory; waits. */
 int topo_summit_snap_read(topo_ctx* ctx, uint32_t n, const double* lonlat_deg, double radius_m, topo_summit_snap* out);
 
+/* ---- map views: relief, contours and the viewshed over any lon/lat grid ---------------------------------------------------------------
+ * The picture a panorama viewer puts next to the panorama: the terrain from above, shaded, with height contours and the ground the
+ * frames show.  csrc/topo_map.h states the rule and argues the kernel's shortcuts; in short:
+ * Pixel (c, r), c < nx, r < ny, lies at lon0 + c * dlon, lat0 + r * dlat (one rounded product, one rounded sum, as
+ * topo_surface_grid_device); dlon and dlat may be negative or zero.  Its terrain is what topo_surface_* finds there; a pixel with no
+ * terrain or an invalid point is VOID.
+ * TOPO_MAP_RELIEF.  The packed normals of the winning triangle's three vertices, unpacked and rotated to world as the frame does for a
+ * vertex, interpolated with the f32 weights (1 - u - v, u, v); the linear value is the frame's view_mode 1 shading of that normal under
+ * sun_direction (as topo_uniforms.sun_direction; topo_sun_direction(lon_c, lat_c, 315, 45, ...) narrowed to float is the conventional
+ * north-west light), 0.01 + 0.7 max(n . sun, 0), without the dither; the grey code g is its sRGB encoding through the frame's table.
+ * TOPO_MAP_CONTOURS, with contour_interval_m > 0.  The level of a terrain pixel is floor(height / interval).  A pixel is on a contour
+ * iff its level differs from that of its east neighbour (c + 1, r) or its south neighbour (c, r + 1); a neighbour outside the grid or
+ * void takes no part.  With index_every = n > 0 it is on an INDEX contour iff for one differing pair a multiple of n lies in (min level,
+ * max level].  An interval of 0 switches the layer off.
+ * TOPO_MAP_SEEN.  A terrain pixel is seen iff the bit of its winning (tile, cell) is set in the viewshed masks, exactly as
+ * topo_viewshed_read reports them; the masks hold every frame queued before the call, on whatever stream it ran (the call joins the
+ * frames in flight, as topo_viewshed_read does).  TOPO_ERR_INVALID if accumulation was never enabled.
+ * flags: one byte per pixel, TOPO_MAP_FLAG_* (index implies contour); 0 for a void pixel.  rgba: four bytes per pixel, always R G B A
+ * in memory: void_rgba for a void pixel; else (g, g, g, 255), g = 255 with the relief layer off; then, if seen, blended with seen_rgba
+ * by its alpha, (c * (255 - a) + s * a + 127) / 255 per colour channel in integers; then, on a contour, blended the same way with
+ * contour_rgba, or with index_rgba on an index contour.  Alpha stays 255 for terrain.  A layer that is off costs nothing and sets no flag.
+ * The calls read the resident tiles only and need no submission; they run on the context's stream (topo_set_stream) behind whatever was
+ * queued there and write nothing but their outputs.  With no tiles every pixel is void.
+ * Errors: TOPO_ERR_INVALID for null params, misaligned pointers or pitches, a zero nx or ny, non-finite grid parameters or
+ * sun_direction, a negative or non-finite interval, unknown layer bits, and ceil(nx / 64) * ny >= 2^32. */
+#define TOPO_MAP_RELIEF 1u
+#define TOPO_MAP_CONTOURS 2u
+#define TOPO_MAP_SEEN 4u
+#define TOPO_MAP_FLAG_TERRAIN 1u
+#define TOPO_MAP_FLAG_CONTOUR 2u
+#define TOPO_MAP_FLAG_INDEX 4u
+#define TOPO_MAP_FLAG_SEEN 8u
+typedef struct topo_map_params {         /* 88 bytes */
+    double lon0_deg, lat0_deg, dlon_deg, dlat_deg;
+    double contour_interval_m;
+    uint32_t nx, ny;
+    uint32_t index_every, layers;        /* layers: TOPO_MAP_RELIEF | TOPO_MAP_CONTOURS | TOPO_MAP_SEEN */
+    float sun_direction[3];
+    uint8_t void_rgba[4], seen_rgba[4], contour_rgba[4], index_rgba[4];
+    uint32_t reserved;
+} topo_map_params;
+/* Device memory; asynchronous -- except with TOPO_MAP_SEEN, where the call WAITS ON THE HOST for the frames in flight on the contexts' own
+ * streams (and, when the tile set or the masks changed since the last frame, for the context's stream) before it queues its kernel.
+ * Each output may be NULL; with both NULL the call checks its arguments and does nothing.  Pixel (c, r):
+ * four bytes at rgba_dev + r * rgba_pitch + 4 * c (pointer and pitch multiples of 4, pitch >= 4 * nx), one at flags_dev + r *
+ * flags_pitch + c (pitch >= nx); the bytes between a row's end and the pitch are left alone. */
+int topo_map_device(topo_ctx* ctx, const topo_map_params* params, uint8_t* rgba_dev, size_t rgba_pitch, uint8_t* flags_dev, size_t flags_pitch);
+/* The same into host memory, densely packed (4 * nx * ny and nx * ny bytes; each may be NULL); waits. */
+int topo_map_read(topo_ctx* ctx, const topo_map_params* params, uint8_t* rgba, uint8_t* flags);
+/* The inverse of the pixel positions, to put the observer, a view cone, peaks or a track on the image: for each of n (lon, lat) pairs
+ * in degrees the fractional (c, r) = ((lon - lon0) / dlon, (lat - lat0) / dlat) as f64, the longitude taken modulo 360 to within 180
+ * degrees of the grid's centre column.  NaN for both of an invalid point (non-finite, |lat| > 90) or params, and for the coordinate
+ * whose step is zero.  Pure: no context, no GPU. */
+void topo_map_xy(const topo_map_params* params, uint32_t n, const double* lonlat_deg, double* xy_out);
+
 /* ---- unwrap: a strip of perspective views as ONE azimuth / elevation image -------------------------------------------------------
  * A panorama strip is eight 45-degree perspective images: within a sector the azimuth per column goes with atan, the elevation of a
  * row depends on the column, and straight ridges kink at every seam.  topo_unwrap_device resamples finished views -- colour, depth --

@@ -74,6 +74,10 @@ int topo_debug_set_summit_band_rows(topo_ctx* ctx, uint32_t rows);
  * k_summit_candidates, out[1] = those that also passed k_summit_reject (the summits), summed over the bands. */
 int topo_debug_summit_counts(topo_ctx* ctx, uint64_t out[2]);
 
+/* Test accessor: R, the rows a wave of the map kernel owns (csrc/topo_map.h: kMapRows).  The map tests size their grids by it: R and
+ * R + 1 rows are the two sides of the south halo. */
+uint32_t topo_map_rows_per_wave(void);
+
 /* Test accessor: the tile's Rgba8Unorm normal texture, w*h*4 bytes, host pointer. */
 int topo_read_normals(topo_ctx* ctx, int32_t lat_deg, int32_t lon_deg, uint8_t* out);
 

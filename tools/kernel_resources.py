@@ -4,13 +4,13 @@
    k_visibility_observers, k_visibility_grid, k_visibility_list), topo_skyline.hip (the skyline queries: k_skyline), topo_sun.hip
    (the sun exposure queries: k_sun_exposure_grid, k_sun_exposure_list), topo_labels.hip (the peak labels: k_labels) and
    topo_summits.hip (the summit queries: k_summit_candidates, k_summit_scan, k_summit_scatter, k_summit_reject, k_summit_flags,
-   k_summit_isolation, k_summit_snap) -- from the code-object metadata of a device-only compile of each.
+   k_summit_isolation, k_summit_snap) and topo_map.hip (the map view: k_map) -- from the code-object metadata of a device-only compile of each.
    tools/kernel_resources.py [extra hipcc flags...]"""
 import os, re, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flags = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize --cuda-device-only -Wno-pass-failed".split()
 notes = ""
-for unit in ("topo_kernels.hip", "topo_rays.hip", "topo_surface.hip", "topo_visibility.hip", "topo_skyline.hip", "topo_sun.hip", "topo_labels.hip", "topo_summits.hip"):
+for unit in ("topo_kernels.hip", "topo_rays.hip", "topo_surface.hip", "topo_visibility.hip", "topo_skyline.hip", "topo_sun.hip", "topo_labels.hip", "topo_summits.hip", "topo_map.hip"):
     src = os.path.join(R, "topo-renderer_amd", "csrc", unit)
     subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, *sys.argv[1:], "-c", "-o", "/tmp/kr_dev.o", src])
     subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--unbundle", "--type=o", "--input=/tmp/kr_dev.o",

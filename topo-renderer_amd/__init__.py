@@ -81,6 +81,12 @@ SUMMIT_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("isolation_m",
                          ("higher_vy", "<u4")])
 SUMMIT_SNAP_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("distance_m", "<f8"), ("height_m", "<f4"), ("status", "<i4"), ("tile_lat_deg", "<i4"),
                               ("tile_lon_deg", "<i4"), ("vx", "<u4"), ("vy", "<u4")])
+MAP_RELIEF, MAP_CONTOURS, MAP_SEEN = 1, 2, 4                                # topo_map_params.layers
+MAP_FLAG_TERRAIN, MAP_FLAG_CONTOUR, MAP_FLAG_INDEX, MAP_FLAG_SEEN = 1, 2, 4, 8      # the flags byte of topo_map_*
+# topo_map_params, 88 bytes
+MAP_PARAMS_DTYPE = np.dtype([("lon0_deg", "<f8"), ("lat0_deg", "<f8"), ("dlon_deg", "<f8"), ("dlat_deg", "<f8"), ("contour_interval_m", "<f8"), ("nx", "<u4"), ("ny", "<u4"),
+                             ("index_every", "<u4"), ("layers", "<u4"), ("sun_direction", "<f4", 3), ("void_rgba", "u1", 4), ("seen_rgba", "u1", 4),
+                             ("contour_rgba", "u1", 4), ("index_rgba", "u1", 4), ("reserved", "<u4")])
 UNWRAP_EQUIRECTANGULAR, UNWRAP_CYLINDRICAL = 0, 1
 UNWRAP_NEAREST, UNWRAP_BILINEAR = 0, 1
 # topo_debug_read_cull_lists (test hook): WorkItem and FarItem of csrc/topo_kernels.h
@@ -237,6 +243,10 @@ def lib():
             "topo_summit_snap_read": (C.c_int, [vp, u32, vp, C.c_double, vp]),
             "topo_debug_set_summit_band_rows": (C.c_int, [vp, u32]),
             "topo_debug_summit_counts": (C.c_int, [vp, vp]),
+            "topo_map_device": (C.c_int, [vp, vp, vp, sz, vp, sz]),
+            "topo_map_read": (C.c_int, [vp, vp, vp, vp]),
+            "topo_map_xy": (None, [vp, u32, vp, vp]),
+            "topo_map_rows_per_wave": (u32, []),
             "topo_ecef_from_lonlat": (None, [C.c_double, C.c_double, C.c_double, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
@@ -248,6 +258,29 @@ def lib():
         L._topo_symbols = tuple(sigs)
         _lib = L
     return _lib
+
+
+def map_params(lon0: float, lat0: float, dlon: float, dlat: float, nx: int, ny: int, sun_direction=(0.0, 0.0, 1.0), contour_interval_m: float = 0.0,
+               index_every: int = 0, layers: int = MAP_RELIEF | MAP_CONTOURS | MAP_SEEN, void_rgba=(0, 0, 0, 0), seen_rgba=(255, 208, 0, 96),
+               contour_rgba=(96, 64, 32, 160), index_rgba=(64, 32, 16, 255)):
+    """One MAP_PARAMS_DTYPE record (topo_map_params): pixel (c, r) at lon0 + c * dlon, lat0 + r * dlat."""
+    p = np.zeros(1, MAP_PARAMS_DTYPE)
+    p["lon0_deg"], p["lat0_deg"], p["dlon_deg"], p["dlat_deg"], p["nx"], p["ny"] = lon0, lat0, dlon, dlat, nx, ny
+    p["contour_interval_m"], p["index_every"], p["layers"] = contour_interval_m, index_every, layers
+    p["sun_direction"][0] = np.asarray(sun_direction, np.float32)
+    for k, v in (("void_rgba", void_rgba), ("seen_rgba", seen_rgba), ("contour_rgba", contour_rgba), ("index_rgba", index_rgba)):
+        p[k][0] = np.asarray(v, np.uint8)
+    return p
+
+
+def map_xy(params, lonlat) -> np.ndarray:
+    """topo_map_xy: (n, 2) f64 (longitude, latitude) in degrees -> (n, 2) f64 fractional (column, row) of the map; NaN where there is
+    none.  Pure: no context, no GPU."""
+    p = np.ascontiguousarray(params, dtype=MAP_PARAMS_DTYPE).reshape(-1)[:1]
+    ll = np.ascontiguousarray(lonlat, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros((len(ll), 2), np.float64)
+    lib().topo_map_xy(_p(p), len(ll), _p(ll) if len(ll) else None, _p(out) if len(ll) else None)
+    return out
 
 
 def summit_params(radius_m: float, min_isolation_m: float = 0.0, min_height_m: float = -np.inf, order: int = SUMMIT_ORDER_TILE):
@@ -1011,6 +1044,28 @@ class TerrainRenderer:
         4 * c (device memory; default: densely packed), NaN where there is no terrain; queued on the context's stream."""
         self._check(lib().topo_surface_grid_device(self._h, lon0, lat0, dlon, dlat, nx, ny, C.c_void_p(out_ptr) if out_ptr else None,
                                                    4 * nx if pitch_bytes is None else pitch_bytes))
+
+    # map view: relief, contours and the viewshed over a lon / lat grid (include/topo_hip.h); no submission needed
+    def map(self, params, rgba: bool = True, flags: bool = True):
+        """topo_map_read: MAP_PARAMS_DTYPE (see map_params) -> ((ny, nx, 4) u8 R G B A or None, (ny, nx) u8 MAP_FLAG_* or None); waits."""
+        p = np.ascontiguousarray(params, dtype=MAP_PARAMS_DTYPE).reshape(-1)[:1]
+        nx, ny = int(p["nx"][0]), int(p["ny"][0])
+        img = np.zeros((ny, nx, 4), np.uint8) if rgba else None
+        flg = np.zeros((ny, nx), np.uint8) if flags else None
+        self._check(lib().topo_map_read(self._h, _p(p), _p(img) if rgba and img.size else None, _p(flg) if flags and flg.size else None))
+        return img, flg
+
+    def map_device(self, params, rgba=None, flags=None):
+        """topo_map_device: rgba a (ny, >= nx, 4) and flags a (ny, >= nx) uint8 torch tensor on the device (either may be None), each with
+        contiguous pixels and rows a stride apart; queued on the context's stream."""
+        p = np.ascontiguousarray(params, dtype=MAP_PARAMS_DTYPE).reshape(-1)[:1]
+        self.map_device_ptr(p, rgba.data_ptr() if rgba is not None else 0, rgba.stride(0) if rgba is not None else 0, flags.data_ptr() if flags is not None else 0,
+                            flags.stride(0) if flags is not None else 0)
+
+    def map_device_ptr(self, params, rgba_ptr: int, rgba_pitch: int, flags_ptr: int, flags_pitch: int):
+        """topo_map_device on raw device pointers and pitches in bytes."""
+        p = np.ascontiguousarray(params, dtype=MAP_PARAMS_DTYPE).reshape(-1)[:1]
+        self._check(lib().topo_map_device(self._h, _p(p), C.c_void_p(rgba_ptr) if rgba_ptr else None, rgba_pitch, C.c_void_p(flags_ptr) if flags_ptr else None, flags_pitch))
 
     def profile(self, ray_records, m: int, samples: bool = True):
         """topo_profile_read: RAY_DTYPE segments (finite t_min, t_max) -> (PROFILE_SUMMARY_DTYPE records, (n, m, 2) f32 (terrain,

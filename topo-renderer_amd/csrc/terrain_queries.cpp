@@ -1,7 +1,8 @@
-// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, visibility, skyline, sun exposure, peak labels, unwrap), the tile-set
+// terrain_queries.cpp -- the queries of TerrainRenderer (viewshed, horizon, ground, rays and the sunlit layer, surface, map views, visibility, skyline, sun exposure, peak labels, unwrap), the tile-set
 // tables they read and their handle on the latest submission.  The frame path is terrain_renderer.cpp (see terrain_renderer.hpp).
 #include "terrain_renderer.hpp"
 #include "topo_labels.h"
+#include "topo_map.h"
 #include "topo_surface.h"
 #include "topo_skyline.h"
 #include "topo_summits.h"
@@ -34,6 +35,9 @@ static_assert(sizeof(SummitRec) == sizeof(topo_summit) && sizeof(topo_summit) ==
                   sizeof(topo_summit_params) == 24, "summit layouts");
 static_assert(kSnapFound == TOPO_SNAP_FOUND && kSnapNone == TOPO_SNAP_NONE && kSnapInvalid == TOPO_SNAP_INVALID && kSummitOrderTile == TOPO_SUMMIT_ORDER_TILE &&
                   kSummitOrderHeight == TOPO_SUMMIT_ORDER_HEIGHT && kSummitOrderIsolation == TOPO_SUMMIT_ORDER_ISOLATION, "summit constants");
+static_assert(sizeof(topo_map_params) == 88 && kMapRelief == TOPO_MAP_RELIEF && kMapContours == TOPO_MAP_CONTOURS && kMapSeen == TOPO_MAP_SEEN &&
+                  kMapFlagTerrain == TOPO_MAP_FLAG_TERRAIN && kMapFlagContour == TOPO_MAP_FLAG_CONTOUR && kMapFlagIndex == TOPO_MAP_FLAG_INDEX && kMapFlagSeen == TOPO_MAP_FLAG_SEEN,
+              "map parameters and constants");
 static_assert(kTileSphereDoubles == kLosSphereDoubles, "the cull prefilter and the rays read the same spheres: one gather, one layout");
 
 // ---- viewshed ----------------------------------------------------------------------------------------------------------------
@@ -463,6 +467,63 @@ int TerrainRenderer::surface_grid_device(double lon0, double lat0, double dlon, 
     launch_surface_grid(ray_params(), lon0, lat0, dlon, dlat, nx, ny, out_dev, pitch_bytes, stream_);
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
+}
+
+// ---- map view -----------------------------------------------------------------------------------------------------------------
+
+// What is wrong with a map call's parameters, or null.
+static const char* map_params_error(const topo_map_params* p) {
+    if (!p) return "params is null";
+    if (p->nx == 0 || p->ny == 0) return "an empty grid";
+    if (!std::isfinite(p->lon0_deg) || !std::isfinite(p->lat0_deg) || !std::isfinite(p->dlon_deg) || !std::isfinite(p->dlat_deg)) return "grid parameters must be finite";
+    if (!(p->contour_interval_m >= 0.0) || !std::isfinite(p->contour_interval_m)) return "the contour interval must be finite and not negative";
+    if (p->layers & ~kMapLayers) return "unknown layer bits";
+    for (float s : p->sun_direction)
+        if (!std::isfinite(s)) return "sun_direction must be finite";
+    if ((((uint64_t)p->nx + 63) / 64) * p->ny > 0xFFFFFFFFull) return "grid too large";
+    return nullptr;
+}
+
+// Device variant: queued on stream_, in order.  Both outputs null: checked, and nothing else.
+int TerrainRenderer::map_device(const topo_map_params* params, uint8_t* rgba_dev, size_t rgba_pitch, uint8_t* flags_dev, size_t flags_pitch) {
+    if (const char* why = map_params_error(params)) return fail(TOPO_ERR_INVALID, why);
+    if (rgba_dev) {
+        if ((uintptr_t)rgba_dev % 4 != 0 || rgba_pitch % 4 != 0) return fail(TOPO_ERR_INVALID, "rgba_dev and its pitch must be multiples of 4 bytes");
+        if (rgba_pitch < (size_t)params->nx * 4) return fail(TOPO_ERR_INVALID, "rgba pitch smaller than a row");
+    }
+    if (flags_dev && flags_pitch < params->nx) return fail(TOPO_ERR_INVALID, "flags pitch smaller than a row");
+    if ((params->layers & kMapSeen) && !vs_ever_) return fail(TOPO_ERR_INVALID, "viewshed accumulation was never enabled");
+    if (!rgba_dev && !flags_dev) return TOPO_OK;
+    if (int rc = bind_device()) return rc;
+    if (params->layers & kMapSeen) {
+        // The frames in flight on the contexts' own streams OR into the masks: they are joined, as viewshed_read joins them (frames on
+        // stream_ itself are in order anyway).  The rank -> mask table is brought up to date with the tile table.
+        if (int rc = join()) return rc;
+        if (int rc = upload_tile_table()) return rc;
+    }
+    if (int rc = prepare_tables(kGeometryTables, stream_)) return rc;
+    const MapCall m = map_call(*params, vs_ever_ ? d_vs_table_.as<const uint32_t* const>() : nullptr, (uint32_t)(mask_bytes() / 4), tiles_.size());
+    launch_map(ray_params(), m, rgba_dev, rgba_pitch, flags_dev, flags_pitch, stream_);
+    TOPO_HIP_TRY(hipGetLastError());
+    return TOPO_OK;
+}
+
+// Host read: densely packed outputs through device buffers of the context; waits for the stream.
+int TerrainRenderer::map_read(const topo_map_params* params, uint8_t* rgba, uint8_t* flags) {
+    if (const char* why = map_params_error(params)) return fail(TOPO_ERR_INVALID, why);
+    if ((params->layers & kMapSeen) && !vs_ever_) return fail(TOPO_ERR_INVALID, "viewshed accumulation was never enabled");
+    if (!rgba && !flags) return TOPO_OK;
+    if (int rc = bind_device()) return rc;
+    const size_t px = (size_t)params->nx * params->ny;
+    if (rgba)
+        if (int rc = ensure(stream_, query_.d_map_rgba, px * 4)) return rc;
+    if (flags)
+        if (int rc = ensure(stream_, query_.d_map_flags, px)) return rc;
+    if (int rc = map_device(params, rgba ? query_.d_map_rgba.as<uint8_t>() : nullptr, (size_t)params->nx * 4, flags ? query_.d_map_flags.as<uint8_t>() : nullptr, params->nx)) return rc;
+    if (rgba) TOPO_HIP_TRY(hipMemcpyAsync(rgba, query_.d_map_rgba.p, px * 4, hipMemcpyDeviceToHost, stream_));
+    if (flags) TOPO_HIP_TRY(hipMemcpyAsync(flags, query_.d_map_flags.p, px, hipMemcpyDeviceToHost, stream_));
+    TOPO_HIP_TRY(hipStreamSynchronize(stream_));
+    return query_fold_check();
 }
 
 // What is wrong with a profile call's shape, or null.

@@ -178,6 +178,10 @@ class TerrainRenderer {
     int surface_read(uint32_t n, const double* lonlat_deg, topo_surface_point* out);
     int surface_device(uint32_t n, const double* lonlat_dev, topo_surface_point* out_dev);
     int surface_grid_device(double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny, float* out_dev, size_t pitch_bytes);
+    // the map view (topo_map_*): tile-set queries on stream_ like the surface calls; with TOPO_MAP_SEEN they join the frames in flight
+    // first, as viewshed_read does, so that the masks hold every frame queued before the call
+    int map_device(const topo_map_params* params, uint8_t* rgba_dev, size_t rgba_pitch, uint8_t* flags_dev, size_t flags_pitch);
+    int map_read(const topo_map_params* params, uint8_t* rgba, uint8_t* flags);
     int profile_device(uint32_t n, const topo_ray* segs_dev, uint32_t m, float* samples_dev, size_t segment_stride_bytes, topo_profile_summary* summary_dev);
     int profile_read(uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary);
 
@@ -405,7 +409,7 @@ class TerrainRenderer {
     // the summit calls' scratch (one band: topo_kernels.h) with their state record, and a summit read's records and count
     struct QueryBuffers {
         DeviceBuffer d_check, d_horizon_out, d_ground_q, d_ground_out, d_ray_in, d_ray_out, d_surface_in, d_surface_out, d_profile_samples, d_vis_observers, d_vis_eyes, d_vis_out,
-            d_sky_elevation, d_sky_samples, d_suns, d_sun_lit, d_sun_shadow, d_sun_exposure, d_unwrap_tab, d_label_projs, d_label_in, d_label_out, d_summit_scratch, d_summit_out, d_summit_count;
+            d_sky_elevation, d_sky_samples, d_suns, d_sun_lit, d_sun_shadow, d_sun_exposure, d_unwrap_tab, d_label_projs, d_label_in, d_label_out, d_summit_scratch, d_summit_out, d_summit_count, d_map_rgba, d_map_flags;
         PinnedBuffer h_ray_stage, h_surface_stage;
         std::vector<double> unwrap_tab;
         std::vector<uint8_t> unwrap_key;

@@ -10,6 +10,7 @@
 #include "../../include/topo_hip_test.h"      // the test hooks are defined here too (their own header: not part of the boundary)
 #include "geotiff.hpp"
 #include "terrain_renderer.hpp"
+#include "topo_map.h"
 #include "topo_surface.h"
 
 struct topo_ctx {
@@ -456,6 +457,30 @@ int topo_surface_grid_device(topo_ctx* ctx, double lon0_deg, double lat0_deg, do
     TOPO_GUARD(ctx);
     TOPO_CALL(ctx->r->surface_grid_device(lon0_deg, lat0_deg, dlon_deg, dlat_deg, nx, ny, out_dev, pitch_bytes));
 }
+
+int topo_map_device(topo_ctx* ctx, const topo_map_params* params, uint8_t* rgba_dev, size_t rgba_pitch, uint8_t* flags_dev, size_t flags_pitch) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->map_device(params, rgba_dev, rgba_pitch, flags_dev, flags_pitch));
+}
+
+int topo_map_read(topo_ctx* ctx, const topo_map_params* params, uint8_t* rgba, uint8_t* flags) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->map_read(params, rgba, flags));
+}
+
+void topo_map_xy(const topo_map_params* params, uint32_t n, const double* lonlat_deg, double* xy_out) {
+    if (!xy_out || n == 0) return;
+    for (uint32_t i = 0; i < n; ++i) {
+        double* xy = xy_out + 2 * (size_t)i;
+        xy[0] = xy[1] = __builtin_nan("");
+        if (!params || !lonlat_deg || params->nx == 0 || !std::isfinite(params->lon0_deg) || !std::isfinite(params->lat0_deg) || !std::isfinite(params->dlon_deg) ||
+            !std::isfinite(params->dlat_deg))
+            continue;
+        topo::map_xy(params->lon0_deg, params->lat0_deg, params->dlon_deg, params->dlat_deg, params->nx, lonlat_deg[2 * (size_t)i], lonlat_deg[2 * (size_t)i + 1], xy);
+    }
+}
+
+uint32_t topo_map_rows_per_wave(void) { return topo::map_rows_per_wave(); }
 
 int topo_profile_device(topo_ctx* ctx, uint32_t n, const topo_ray* segs_dev, uint32_t m, float* samples_dev, size_t segment_stride_bytes,
                         topo_profile_summary* summary_dev) {

@@ -272,6 +272,13 @@ void launch_surface_grid(const RayParams& p, double lon0, double lat0, double dl
 // m samples (terrain, line) of each of n segments at samples + i * stride bytes (samples null: none), and the segments' summaries
 void launch_profile(const RayParams& p, const LosRay* segs, uint32_t n, uint32_t m, float* samples, size_t stride, ProfileSummary* summary, hipStream_t s);
 
+// map view (topo_map_*): relief, contours and the viewshed over a lon / lat raster (topo_map.h); needs no submission.  Reads what the
+// surface queries read, the tiles' normals and, with the seen layer, the viewshed masks; writes only its outputs (each nullable).
+struct MapCall;          // the call's parameters and the masks (topo_map.h)
+// pixel (c, r): four bytes at rgba + r * rgba_pitch + 4 c, one at flags + r * flags_pitch + c; ceil(nx / 64) * ny < 2^32
+void launch_map(const RayParams& p, const MapCall& m, uint8_t* rgba, size_t rgba_pitch, uint8_t* flags, size_t flags_pitch, hipStream_t s);
+uint32_t map_rows_per_wave();      // R: the rows a wave of k_map owns (the tests are sized by it)
+
 // visibility (topo_visibility_*): what observers see of the drawn terrain (topo_visibility.h); needs no submission.  Reads what the
 // rays read (RayParams); writes only the observer table and its outputs.
 struct VisObserver;      // = topo_observer (topo_visibility.h)
