@@ -537,6 +537,32 @@ int topo_visibility_read(topo_ctx* ctx, uint32_t n_observers, const topo_observe
  * topo_ray, or the O and T above. */
 void topo_ecef_from_lonlat(double lon_deg, double lat_deg, double height_m, double out[3]);
 
+/* ---- refracted visibility: sight lines bent by atmospheric refraction ------------------------------------------------------------
+ * The sight lines above are straight segments over a spherical Earth.  Surveyors, radio planners and viewshed tools apply the
+ * standard refraction correction instead: with coefficient k (0.13 in the standard atmosphere; GDAL's viewshed calls it -cc 0.857 =
+ * 1 - k), terrain at distance s from the observer appears raised by k s^2 / (2 R0) -- 1 m at 10 km, 100 m at 100 km, 400 m at 200 km.
+ * The rule.  The refracted query of observer O with coefficient refraction_k is the visibility query above on the mesh LIFTED for O:
+ * every vertex v keeps its direction and gains radius, v' = v + (c |v - O|^2 / |v|) v with c = k / (2 R0) and |v - O| the f64 chord
+ * from the unlifted vertex to O; O itself is resolved on the unlifted mesh, exactly as above.  Everything else is the rule above on
+ * the lifted vertices: the target lies on the lifted mesh, AWAY uses the lifted triangle's normal, target_height_m is added on top,
+ * the sight line runs from T to O with the same bounds and the same skipped triangle; the classes are the same five.
+ * refraction_k == 0 gives the bytes of topo_visibility_*, bit for bit.  Each call takes the arguments of its plain counterpart plus
+ * refraction_k, and follows its contract (at most 64 observers, the no-ops, the strides, asynchrony, nothing written but the
+ * outputs); TOPO_ERR_INVALID also for a refraction_k that is not finite or lies outside 0 <= k < 1.
+ * Skyline, sun exposure, rays and rendered frames stay unrefracted. */
+#define TOPO_REFRACTION_STANDARD 0.13
+int topo_visibility_refracted_grid_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double lon0_deg, double lat0_deg, double dlon_deg,
+                                          double dlat_deg, uint32_t nx, uint32_t ny, double target_height_m, double refraction_k, uint8_t* out_dev,
+                                          size_t layer_stride_bytes, size_t pitch_bytes);
+int topo_visibility_refracted_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_dev, double target_height_m,
+                                     double refraction_k, uint8_t* out_dev, size_t list_stride_bytes);
+int topo_visibility_refracted_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m,
+                                   double refraction_k, uint8_t* out);
+/* Host helper, f64, no GPU: out = point lifted for `observer` with coefficient k (ECEF metres, the frame of topo_ecef_from_lonlat) --
+ * for callers who place their own objects in the refracted scene.  out may be point.  TOPO_ERR_INVALID for a null pointer or a k
+ * outside 0 <= k < 1 (out is left alone). */
+int topo_refraction_lift(const double observer[3], const double point[3], double k, double out[3]);
+
 /* ---- skyline: the terrain horizon by azimuth from any point ----------------------------------------------------------------------
  * "How high does the terrain stand above the horizontal in each direction from here, and which ridge forms that line?" -- solar
  * access, radio horizon, ridge labels, the vertical extent of a panorama -- without a rendered frame, its rows or its field of view.

@@ -10,7 +10,7 @@ import os, re, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flags = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize --cuda-device-only -Wno-pass-failed".split()
 notes = ""
-for unit in ("topo_kernels.hip", "topo_rays.hip", "topo_surface.hip", "topo_visibility.hip", "topo_skyline.hip", "topo_sun.hip", "topo_labels.hip", "topo_summits.hip", "topo_map.hip"):
+for unit in ("topo_kernels.hip", "topo_rays.hip", "topo_surface.hip", "topo_visibility.hip", "topo_refraction.hip", "topo_skyline.hip", "topo_sun.hip", "topo_labels.hip", "topo_summits.hip", "topo_map.hip"):
     src = os.path.join(R, "topo-renderer_amd", "csrc", unit)
     subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, *sys.argv[1:], "-c", "-o", "/tmp/kr_dev.o", src])
     subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--unbundle", "--type=o", "--input=/tmp/kr_dev.o",

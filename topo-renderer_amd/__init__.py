@@ -58,6 +58,7 @@ SURFACE_DTYPE = np.dtype([("height_m", "<f8"), ("slope_deg", "<f4"), ("aspect_de
 PROFILE_SUMMARY_DTYPE = np.dtype([("min_clearance_m", "<f4"), ("min_sample", "<u4"), ("n_terrain", "<u4"), ("kind", "<i4")])
 VIS_NONE, VIS_VISIBLE, VIS_AWAY, VIS_HIDDEN, VIS_NO_OBSERVER = 0, 1, 2, 3, 4
 OBSERVER_ABOVE_TERRAIN = 1
+REFRACTION_STANDARD = 0.13      # TOPO_REFRACTION_STANDARD: the coefficient k of the standard atmosphere
 # topo_observer, 32 bytes
 OBSERVER_DTYPE = np.dtype([("lon_deg", "<f8"), ("lat_deg", "<f8"), ("height_m", "<f8"), ("flags", "<u4"), ("_reserved", "<u4")])
 SKY_NONE, SKY_TERRAIN, SKY_NO_OBSERVER = 0, 1, 4
@@ -248,6 +249,10 @@ def lib():
             "topo_map_xy": (None, [vp, u32, vp, vp]),
             "topo_map_rows_per_wave": (u32, []),
             "topo_ecef_from_lonlat": (None, [C.c_double, C.c_double, C.c_double, vp]),
+            "topo_visibility_refracted_grid_device": (C.c_int, [vp, u32, vp, C.c_double, C.c_double, C.c_double, C.c_double, u32, u32, C.c_double, C.c_double, vp, sz, sz]),
+            "topo_visibility_refracted_device": (C.c_int, [vp, u32, vp, u32, vp, C.c_double, C.c_double, vp, sz]),
+            "topo_visibility_refracted_read": (C.c_int, [vp, u32, vp, u32, vp, C.c_double, C.c_double, vp]),
+            "topo_refraction_lift": (C.c_int, [vp, vp, C.c_double, vp]),
             "topo_unwrap_device": (C.c_int, [vp, vp, u32, vp, u32, u32, vp, sz, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz]),
             "topo_unwrap_xy": (None, [vp, u32, vp, vp]),
         }
@@ -439,6 +444,17 @@ def ecef_from_lonlat(lon_deg: float, lat_deg: float, height_m: float = 0.0) -> n
     """topo_ecef_from_lonlat: the f64 ECEF point height_m above the sphere R0 at (lon_deg, lat_deg), in the frame of the rays."""
     out = np.zeros(3, dtype=np.float64)
     lib().topo_ecef_from_lonlat(lon_deg, lat_deg, height_m, _p(out))
+    return out
+
+
+def refraction_lift(observer, point, k: float = REFRACTION_STANDARD) -> np.ndarray:
+    """topo_refraction_lift: the f64 ECEF point where `point` is seen from `observer` under refraction coefficient k along straight
+    lines -- the same direction, the radius raised by k |point - observer|^2 / (2 R0); no GPU."""
+    o, p = np.ascontiguousarray(observer, dtype=np.float64).reshape(3), np.ascontiguousarray(point, dtype=np.float64).reshape(3)
+    out = np.zeros(3, dtype=np.float64)
+    rc = lib().topo_refraction_lift(_p(o), _p(p), k, _p(out))
+    if rc != TOPO_OK:
+        raise TopoError(rc, "topo_refraction_lift: k must lie in 0 <= k < 1")
     return out
 
 
@@ -1109,6 +1125,33 @@ class TerrainRenderer:
         out = np.zeros((len(o), len(p)), np.uint8)
         self._check(lib().topo_visibility_read(self._h, len(o), _p(o) if len(o) else None, len(p), _p(p) if len(p) else None, target_height_m,
                                                _p(out) if out.size else None))
+        return out
+
+    # refracted visibility: the same three calls along sight lines bent by refraction coefficient k (include/topo_hip.h)
+    def visibility_refracted_grid_device(self, obs, lon0: float, lat0: float, dlon: float, dlat: float, nx: int, ny: int, out_ptr: int, target_height_m: float = 0.0,
+                                         refraction_k: float = REFRACTION_STANDARD, layer_stride_bytes: int = None, pitch_bytes: int = None):
+        """topo_visibility_refracted_grid_device: visibility_grid_device's bytes on the mesh lifted for each observer with
+        refraction_k (0 <= k < 1; 0 gives visibility_grid_device's bytes); queued on the context's stream."""
+        o = np.ascontiguousarray(obs, dtype=OBSERVER_DTYPE).reshape(-1)
+        pitch = nx if pitch_bytes is None else pitch_bytes
+        stride = pitch * ny if layer_stride_bytes is None else layer_stride_bytes
+        self._check(lib().topo_visibility_refracted_grid_device(self._h, len(o), _p(o) if len(o) else None, lon0, lat0, dlon, dlat, nx, ny, target_height_m, refraction_k,
+                                                                C.c_void_p(out_ptr) if out_ptr else None, stride, pitch))
+
+    def visibility_refracted_device(self, obs, lonlat_ptr: int, n: int, out_ptr: int, target_height_m: float = 0.0, refraction_k: float = REFRACTION_STANDARD,
+                                    list_stride_bytes: int = None):
+        """topo_visibility_refracted_device: visibility_device's bytes under refraction_k; queued on the context's stream."""
+        o = np.ascontiguousarray(obs, dtype=OBSERVER_DTYPE).reshape(-1)
+        self._check(lib().topo_visibility_refracted_device(self._h, len(o), _p(o) if len(o) else None, n, C.c_void_p(lonlat_ptr) if lonlat_ptr else None, target_height_m,
+                                                           refraction_k, C.c_void_p(out_ptr) if out_ptr else None, n if list_stride_bytes is None else list_stride_bytes))
+
+    def visibility_refracted(self, obs, lonlat, target_height_m: float = 0.0, refraction_k: float = REFRACTION_STANDARD) -> np.ndarray:
+        """topo_visibility_refracted_read: as visibility(), under refraction_k -> (observers, n) uint8 classes (VIS_*); waits."""
+        o = np.ascontiguousarray(obs, dtype=OBSERVER_DTYPE).reshape(-1)
+        p = np.ascontiguousarray(lonlat, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros((len(o), len(p)), np.uint8)
+        self._check(lib().topo_visibility_refracted_read(self._h, len(o), _p(o) if len(o) else None, len(p), _p(p) if len(p) else None, target_height_m, refraction_k,
+                                                         _p(out) if out.size else None))
         return out
 
     # skyline: the terrain horizon by azimuth from observers (include/topo_hip.h); no submission needed

@@ -7,6 +7,7 @@
 #include "topo_skyline.h"
 #include "topo_summits.h"
 #include "topo_sun.h"
+#include "topo_refraction.h"
 #include "topo_visibility.h"
 
 #include <algorithm>
@@ -578,11 +579,12 @@ int TerrainRenderer::profile_read(uint32_t n, const topo_ray* segs, uint32_t m, 
 
 // What every visibility call does first: its checks, the tables, and the observers -- host memory -- resolved into the context's
 // table by k_visibility_observers on stream_ (behind the kernels of an earlier call that still read it).
-int TerrainRenderer::visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m) {
+int TerrainRenderer::visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m, const double* refraction_k) {
     if (!observers) return fail(TOPO_ERR_INVALID, "null argument");
     if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
     if (!(std::isfinite(target_height_m) && target_height_m >= 0.0 && target_height_m <= kVisMaxTargetHeight))
         return fail(TOPO_ERR_INVALID, "target_height_m must be finite and lie in 0 .. 1e5");
+    if (refraction_k && !refraction_k_valid(*refraction_k)) return fail(TOPO_ERR_INVALID, "refraction_k must lie in 0 <= k < 1");
     return resolve_observers(n_observers, observers);
 }
 
@@ -600,7 +602,8 @@ int TerrainRenderer::resolve_observers(uint32_t n_observers, const topo_observer
 
 // Device variants: queued on stream_, in order.
 int TerrainRenderer::visibility_grid_device(uint32_t n_observers, const topo_observer* observers, double lon0, double lat0, double dlon, double dlat, uint32_t nx,
-                                            uint32_t ny, double target_height_m, uint8_t* out_dev, size_t layer_stride_bytes, size_t pitch_bytes) {
+                                            uint32_t ny, double target_height_m, uint8_t* out_dev, size_t layer_stride_bytes, size_t pitch_bytes,
+                                            const double* refraction_k) {
     if (n_observers == 0) return TOPO_OK;
     if (!out_dev || !observers) return fail(TOPO_ERR_INVALID, "null argument");
     if (nx == 0 || ny == 0) return fail(TOPO_ERR_INVALID, "an empty grid");
@@ -609,42 +612,55 @@ int TerrainRenderer::visibility_grid_device(uint32_t n_observers, const topo_obs
     if (layer_stride_bytes / ny < pitch_bytes || layer_stride_bytes < (size_t)ny * pitch_bytes) return fail(TOPO_ERR_INVALID, "layer stride smaller than a layer");
     if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
     if ((((uint64_t)nx + 63) / 64) * ny * n_observers > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "grid too large");
-    if (int rc = visibility_begin(n_observers, observers, target_height_m)) return rc;
-    launch_visibility_grid(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, lon0, lat0, dlon, dlat, nx, ny, target_height_m, out_dev, layer_stride_bytes,
-                           pitch_bytes, stream_);
+    if (int rc = visibility_begin(n_observers, observers, target_height_m, refraction_k)) return rc;
+    if (refraction_k)
+        launch_visibility_refracted_grid(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, lon0, lat0, dlon, dlat, nx, ny, target_height_m, *refraction_k,
+                                         out_dev, layer_stride_bytes, pitch_bytes, stream_);
+    else
+        launch_visibility_grid(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, lon0, lat0, dlon, dlat, nx, ny, target_height_m, out_dev,
+                               layer_stride_bytes, pitch_bytes, stream_);
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
 }
 
 int TerrainRenderer::visibility_device(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_dev, double target_height_m,
-                                       uint8_t* out_dev, size_t list_stride_bytes) {
+                                       uint8_t* out_dev, size_t list_stride_bytes, const double* refraction_k) {
     if (n == 0 || n_observers == 0) return TOPO_OK;
     if (!lonlat_dev || !out_dev || !observers) return fail(TOPO_ERR_INVALID, "null argument");
     if ((uintptr_t)lonlat_dev % 16 != 0) return fail(TOPO_ERR_INVALID, "lonlat_dev must be 16-byte aligned");
     if (list_stride_bytes < n) return fail(TOPO_ERR_INVALID, "list stride smaller than the list");
     if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
     if ((((uint64_t)n + 63) / 64) * n_observers > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "list too large");
-    if (int rc = visibility_begin(n_observers, observers, target_height_m)) return rc;
-    launch_visibility_list(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, lonlat_dev, n, target_height_m, out_dev, list_stride_bytes, stream_);
+    if (int rc = visibility_begin(n_observers, observers, target_height_m, refraction_k)) return rc;
+    if (refraction_k)
+        launch_visibility_refracted_list(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, lonlat_dev, n, target_height_m, *refraction_k, out_dev,
+                                         list_stride_bytes, stream_);
+    else
+        launch_visibility_list(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, lonlat_dev, n, target_height_m, out_dev, list_stride_bytes, stream_);
     TOPO_HIP_TRY(hipGetLastError());
     return TOPO_OK;
 }
 
 // Host read: observer o's classes at out + o * n.  The caller's memory is pageable, so nothing is staged (as topo_profile_read):
 // the stream is drained, the list goes up and the classes come down with blocking copies.
-int TerrainRenderer::visibility_read(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out) {
+int TerrainRenderer::visibility_read(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out,
+                                     const double* refraction_k) {
     if (n == 0 || n_observers == 0) return TOPO_OK;
     if (!lonlat_deg || !out || !observers) return fail(TOPO_ERR_INVALID, "null argument");
     if (n_observers > kVisMaxObservers) return fail(TOPO_ERR_INVALID, "at most 64 observers");
     if ((((uint64_t)n + 63) / 64) * n_observers > 0xFFFFFFFFull) return fail(TOPO_ERR_INVALID, "list too large");
-    if (int rc = visibility_begin(n_observers, observers, target_height_m)) return rc;
+    if (int rc = visibility_begin(n_observers, observers, target_height_m, refraction_k)) return rc;
     const size_t in_bytes = (size_t)n * 2 * sizeof(double), out_bytes = (size_t)n * n_observers;
     if (int rc = ensure(stream_, query_.d_surface_in, in_bytes)) return rc;
     if (int rc = ensure(stream_, query_.d_vis_out, out_bytes)) return rc;
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
     TOPO_HIP_TRY(hipMemcpy(query_.d_surface_in.p, lonlat_deg, in_bytes, hipMemcpyHostToDevice));
-    launch_visibility_list(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, query_.d_surface_in.as<const double>(), n, target_height_m,
-                           query_.d_vis_out.as<uint8_t>(), n, stream_);
+    if (refraction_k)
+        launch_visibility_refracted_list(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, query_.d_surface_in.as<const double>(), n, target_height_m,
+                                         *refraction_k, query_.d_vis_out.as<uint8_t>(), n, stream_);
+    else
+        launch_visibility_list(ray_params(), query_.d_vis_eyes.as<const VisEye>(), n_observers, query_.d_surface_in.as<const double>(), n, target_height_m,
+                               query_.d_vis_out.as<uint8_t>(), n, stream_);
     TOPO_HIP_TRY(hipGetLastError());
     TOPO_HIP_TRY(hipStreamSynchronize(stream_));
     TOPO_HIP_TRY(hipMemcpy(out, query_.d_vis_out.p, out_bytes, hipMemcpyDeviceToHost));

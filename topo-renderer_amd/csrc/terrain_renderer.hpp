@@ -185,12 +185,14 @@ class TerrainRenderer {
     int profile_device(uint32_t n, const topo_ray* segs_dev, uint32_t m, float* samples_dev, size_t segment_stride_bytes, topo_profile_summary* summary_dev);
     int profile_read(uint32_t n, const topo_ray* segs, uint32_t m, float* samples, topo_profile_summary* summary);
 
-    // visibility: what observers see of the drawn terrain -- maps and lists (topo_visibility_*): no submission needed
+    // visibility: what observers see of the drawn terrain -- maps and lists (topo_visibility_*): no submission needed.
+    // refraction_k: null for straight sight lines, else the coefficient of topo_visibility_refracted_* (0 <= k < 1)
     int visibility_grid_device(uint32_t n_observers, const topo_observer* observers, double lon0, double lat0, double dlon, double dlat, uint32_t nx, uint32_t ny,
-                               double target_height_m, uint8_t* out_dev, size_t layer_stride_bytes, size_t pitch_bytes);
+                               double target_height_m, uint8_t* out_dev, size_t layer_stride_bytes, size_t pitch_bytes, const double* refraction_k = nullptr);
     int visibility_device(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_dev, double target_height_m, uint8_t* out_dev,
-                          size_t list_stride_bytes);
-    int visibility_read(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out);
+                          size_t list_stride_bytes, const double* refraction_k = nullptr);
+    int visibility_read(uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out,
+                        const double* refraction_k = nullptr);
 
     // skyline: the terrain horizon by azimuth from observers (topo_skyline_*): no submission needed
     int skyline_device(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m,
@@ -427,7 +429,7 @@ class TerrainRenderer {
     int ground_prepare(const LatestSubmission& q);      // geometry tables + the submission's views on the device
     GroundParams ground_params(const LatestSubmission& q, uint32_t first_view, uint32_t n_views) const;
     RayParams ray_params() const;
-    int visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m);      // checks, then resolve_observers
+    int visibility_begin(uint32_t n_observers, const topo_observer* observers, double target_height_m, const double* refraction_k);      // checks, then resolve_observers
     int resolve_observers(uint32_t n_observers, const topo_observer* observers);      // the tables, and the observers resolved into d_vis_eyes on stream_
     int skyline_check(uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m, double max_range_m);
     int sun_begin(uint32_t n_suns, const topo_sun* suns);      // checks, the tables, and the suns normalised into d_suns on stream_

@@ -11,6 +11,7 @@
 #include "geotiff.hpp"
 #include "terrain_renderer.hpp"
 #include "topo_map.h"
+#include "topo_refraction.h"
 #include "topo_surface.h"
 
 struct topo_ctx {
@@ -508,6 +509,34 @@ int topo_visibility_device(topo_ctx* ctx, uint32_t n_observers, const topo_obser
 int topo_visibility_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m, uint8_t* out) {
     TOPO_GUARD(ctx);
     TOPO_CALL(ctx->r->visibility_read(n_observers, observers, n, lonlat_deg, target_height_m, out));
+}
+
+int topo_visibility_refracted_grid_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double lon0_deg, double lat0_deg, double dlon_deg,
+                                          double dlat_deg, uint32_t nx, uint32_t ny, double target_height_m, double refraction_k, uint8_t* out_dev,
+                                          size_t layer_stride_bytes, size_t pitch_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->visibility_grid_device(n_observers, observers, lon0_deg, lat0_deg, dlon_deg, dlat_deg, nx, ny, target_height_m, out_dev, layer_stride_bytes, pitch_bytes,
+                                             &refraction_k));
+}
+
+int topo_visibility_refracted_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_dev, double target_height_m,
+                                     double refraction_k, uint8_t* out_dev, size_t list_stride_bytes) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->visibility_device(n_observers, observers, n, lonlat_dev, target_height_m, out_dev, list_stride_bytes, &refraction_k));
+}
+
+int topo_visibility_refracted_read(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, uint32_t n, const double* lonlat_deg, double target_height_m,
+                                   double refraction_k, uint8_t* out) {
+    TOPO_GUARD(ctx);
+    TOPO_CALL(ctx->r->visibility_read(n_observers, observers, n, lonlat_deg, target_height_m, out, &refraction_k));
+}
+
+int topo_refraction_lift(const double observer[3], const double point[3], double k, double out[3]) {
+    if (!observer || !point || !out || !topo::refraction_k_valid(k)) return TOPO_ERR_INVALID;
+    const topo::RefLift lift = topo::refraction_make(observer, k);
+    for (int i = 0; i < 3; ++i) out[i] = point[i];
+    topo::refraction_lift(lift, out);
+    return TOPO_OK;
 }
 
 int topo_skyline_device(topo_ctx* ctx, uint32_t n_observers, const topo_observer* observers, double az0_deg, double daz_deg, uint32_t n_az, double min_range_m,

@@ -291,6 +291,12 @@ void launch_visibility_grid(const RayParams& p, const VisEye* eyes, uint32_t n_o
 // the same for n (lon, lat) pairs: out[o * list_stride + i]
 void launch_visibility_list(const RayParams& p, const VisEye* eyes, uint32_t n_observers, const double* lonlat, uint32_t n, double target_height, uint8_t* out,
                             size_t list_stride, hipStream_t s);
+// refracted visibility (topo_visibility_refracted_*): the same two forms on the mesh lifted for each observer with coefficient k
+// (topo_refraction.h; 0 <= k < 1, checked by the caller); the observers are those launch_visibility_observers resolved
+void launch_visibility_refracted_grid(const RayParams& p, const VisEye* eyes, uint32_t n_observers, double lon0, double lat0, double dlon, double dlat, uint32_t nx,
+                                      uint32_t ny, double target_height, double k, uint8_t* out, size_t layer_stride, size_t pitch, hipStream_t s);
+void launch_visibility_refracted_list(const RayParams& p, const VisEye* eyes, uint32_t n_observers, const double* lonlat, uint32_t n, double target_height, double k,
+                                      uint8_t* out, size_t list_stride, hipStream_t s);
 
 // skyline (topo_skyline_*): per (observer, azimuth) the highest terrain crossing of the vertical half-plane from the observer
 // (topo_skyline.h); needs no submission.  Reads what the rays read (RayParams) and the table of resolved observers
